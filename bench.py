@@ -16,7 +16,9 @@ stripe plus the halo rows its window operators read; histograms, PCA sums, KMean
 RCCL, and the label map equals the single-GPU result for that raster bit for bit (tests/test_gpu_dist.py).  --weak keeps H
 rows per rank instead (an (N*H) x W scene).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the line (`value`, `ms_per_step`,
+the kernel families of the timed steps); --full adds the CPU baseline and the side figures, each of which takes runs of its own.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs).
 """
 import argparse
 import json
@@ -319,7 +321,16 @@ def main():
                     help="how the all-reduces are issued: 'native' = the library's own RCCL communicator (ncclAllReduce from C on the context's "
                          "stream; default with backend nccl), 'torch' = the callback into torch.distributed.all_reduce (default with gloo)")
     ap.add_argument("--launch-selftest", action="store_true", help="no GPU: every rank joins a gloo rendezvous on the CPU and rank 0 prints one line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the CPU baseline, the side figures of one GPU (GLCM step 7, the other "
+                         "raster, uint8 bands, north_star's configuration, config 5, PCIe-inclusive rates) and the forest's node visits; "
+                         "--no-cpu-baseline / --no-extras / --no-c5-extra drop parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64, a fixed "
+                         "seeded sample of the planes, at most 64 MB): two builds compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
 
     # ---- N ranks: either torch.distributed.run started us (RANK / WORLD_SIZE set, WORLD_SIZE must equal --gpus), or
     # this process starts them itself.  Decided BEFORE torch is imported or a GPU is touched.
@@ -393,20 +404,24 @@ def main():
         forest_model = fit_c5_forest(torch, dist, device, P, rank, world, W)
         ctx.forest_load(forest_model["flat"])
 
-    def step(glcm_step=args.glcm_step, bands=bands):
+    def step_outputs(glcm_step=args.glcm_step, bands=bands):
+        """one step: (labels, KMeans meta or None, the feature planes the labels were computed from)"""
         if cfg == "c3" and world > 1:
-            labels, meta, _ = P.config3_striped(ctx, bands, nir_ext, Hg, W, r0, r1, i0, k, 7, glcm_step, 3)
-            return labels, meta
+            return P.config3_striped(ctx, bands, nir_ext, Hg, W, r0, r1, i0, k, 7, glcm_step, 3)
         if cfg == "c3":
-            labels, meta, _ = P.config3(ctx, bands, H, W, k, 7, glcm_step, 3, n_global, overlap=args.overlap)
-            return labels, meta
+            return P.config3(ctx, bands, H, W, k, 7, glcm_step, 3, n_global, overlap=args.overlap)
         if cfg == "c5" and world > 1:
             planes, _ = P.stack19_striped(ctx, bands, Hg, W, r0, r1, e0)
-            return ctx.forest_predict(P.stack19_forest_planes(ctx, planes)), None
+            fp = P.stack19_forest_planes(ctx, planes)
+            return ctx.forest_predict(fp), None, fp
         if cfg == "c5":
             planes, _ = P.feature_stack19(ctx, bands, H, W, n_global=n_global)
-            return ctx.forest_predict(P.stack19_forest_planes(ctx, planes)), None
-        return run_c2(ctx, P, bands, k, n_global)
+            fp = P.stack19_forest_planes(ctx, planes)
+            return ctx.forest_predict(fp), None, fp
+        return c2_outputs(ctx, P, bands, k, n_global)
+
+    def step(glcm_step=args.glcm_step, bands=bands):
+        return step_outputs(glcm_step, bands)[:2]
 
     def barrier():
         if world > 1:
@@ -426,10 +441,11 @@ def main():
     barrier()
     t0 = time.perf_counter()
     verbose = os.environ.get("RSSEG_BENCH_VERBOSE")
+    planes = None
     for _ in range(args.steps):
         ts = time.perf_counter()
-        labels = None
-        labels, meta = step()
+        labels = planes = None
+        labels, meta, planes = step_outputs()
         if verbose:  # per-step wall time (adds a device synchronisation per step: diagnostics only)
             torch.cuda.synchronize()
             print(f"[bench] step {(time.perf_counter() - ts) * 1e3:.2f} ms", file=sys.stderr, flush=True)
@@ -450,8 +466,11 @@ def main():
     comm_ms, comm_cnt = ctx.prof_get("allreduce")
     host_syncs = ctx.host_syncs()
     ctx.prof_enable(False)
+    if args.dump_outputs:
+        dump_outputs(torch, dist, args.dump_outputs, labels, meta, planes, r0 * W, n_own, n_global, rank, world)
+    planes = None
 
-    # ---- side measurements (rank 0, N = 1): GLCM step 7, the other synthetic raster, north_star's literal configuration,
+    # ---- side measurements (--full; rank 0, N = 1): GLCM step 7, the other synthetic raster, north_star's literal configuration,
     # and the PCIe-inclusive rates — never the bench `value` ----
     extras = {}
 
@@ -478,7 +497,7 @@ def main():
                         "ms_lloyd": round(lms / reps, 2)})
         return out
 
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         if cfg == "c3" and args.glcm_step == 1:
             extras["glcm_step7"] = dict(timed(lambda: step(7)), note="same path with step_size=7 (the reference's non-overlapping windows, SURVEY.md 8d)")
         if cfg in ("c2", "c3"):
@@ -513,7 +532,7 @@ def main():
         table = family_table(cfg, F, args.glcm_step, k, n_pca)
         kernels = []
         visits = (forest_visits_per_px(torch, P, ctx, bands, H, W, n_global, forest_model["model"])
-                  if (cfg == "c5" and world == 1 and "forest" in fams) else None)
+                  if (args.full and cfg == "c5" and world == 1 and "forest" in fams) else None)
         for fam, (ms, cnt) in sorted(fams.items(), key=lambda kv: -kv[1][0]):
             bound, bpp = table[fam]
             per_launch_s = ms / cnt / 1e3
@@ -569,7 +588,7 @@ def main():
             roof["kernels"] = kernels
             roof["kernels_ms_per_step"] = round(sum(e["ms_per_step"] for e in kernels), 2)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(bands, H, W, min(args.cpu_crop, 1024) if cfg == "c5" else args.cpu_crop, cfg, k, args.glcm_step,
                                forest_model["model"] if forest_model else None)
         scene = f"{Hg}x{W}x7 synthetic TM raster" + (f", row-striped over {world} GPUs ({r1 - r0} rows per rank + halo rows)" if world > 1 else "")
@@ -856,11 +875,66 @@ def pcie_inclusive(torch, device, ctx, bands, step, n_global, step_qb=None):
         return {"error": repr(e), "trace": traceback.format_exc()[-800:]}
 
 
-def run_c2(ctx, P, bands, k, n_global):
+def c2_outputs(ctx, P, bands, k, n_global):
     lohi = P.band_lohi(ctx, bands[:5], n_global)
     idx, _ = P.spectral_indices(ctx, bands, lohi)
     planes = [idx[n] for n in P.INDEX_NAMES]
-    return ctx.kmeans_fit_predict(planes, k)
+    labels, meta = ctx.kmeans_fit_predict(planes, k)
+    return labels, meta, planes
+
+
+def run_c2(ctx, P, bands, k, n_global):
+    return c2_outputs(ctx, P, bands, k, n_global)[:2]
+
+
+DUMP_BYTES = 64 * 2 ** 20
+DUMP_SAMPLE_SEED = 20240611
+KMEANS_DUMP_KEYS = ("n_iter", "relocated", "tol", "scale", "min", "mean", "init_indices", "centers")   # meta without its timings
+
+
+def dump_outputs(torch, dist, outdir, labels, meta, planes, g_off, n_own, n_global, rank, world):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files in DIR, at most DUMP_BYTES in all.
+      labels_count.npy     (classes, 2) float64: every label value of the WHOLE map and how many pixels carry it
+      sample_index.npy     (m,) float64: a fixed, seeded set of global pixel indices (all pixels when the raster is small enough)
+      labels_sample.npy    (m,) float32: the labels at those pixels
+      features_sample.npy  (F, m) float32: the feature planes the labels were computed from, at those pixels
+      kmeans_<key>.npy     float64: the fitted KMeans state (seeds, iterations, scaling, centres) where the step is a KMeans
+    The sample depends on the raster size and the number of planes only, so a run on N GPUs (strong scaling) writes the same
+    files as a run on one; every rank gathers the sampled pixels of its own rows and rank 0 writes."""
+    F = len(planes)
+    m = min(n_global, (DUMP_BYTES - 2 * 2 ** 20) // (8 + 4 + 4 * F))
+    if m == n_global:
+        idx = np.arange(n_global, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, n_global, m, dtype=np.int64))
+    assert labels.numel() == n_own and all(p.numel() == n_own for p in planes), "outputs do not cover this rank's rows"
+    mine = idx[(idx >= g_off) & (idx < g_off + n_own)]
+    loc = torch.from_numpy(mine - g_off).to(labels.device)
+    part = {"index": mine,
+            "labels": labels[loc].to(torch.float32).cpu().numpy(),
+            "features": torch.stack([p[loc].to(torch.float32) for p in planes]).cpu().numpy() if F else np.zeros((0, mine.size), np.float32),
+            "counts": dict(zip(*[t.cpu().tolist() for t in torch.unique(labels, return_counts=True)]))}
+    parts = [part]
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, part)
+    if rank != 0:
+        return
+    counts = {}
+    for p in parts:
+        for v, c in p["counts"].items():
+            counts[v] = counts.get(v, 0) + c
+    out = {"labels_count": np.array(sorted(counts.items()), np.float64).reshape(-1, 2),
+           "sample_index": np.concatenate([p["index"] for p in parts]).astype(np.float64),
+           "labels_sample": np.concatenate([p["labels"] for p in parts]).astype(np.float32),
+           "features_sample": np.concatenate([p["features"] for p in parts], axis=1).astype(np.float32)}
+    assert out["sample_index"].size == idx.size
+    for key in KMEANS_DUMP_KEYS if meta else ():
+        out[f"kmeans_{key}"] = np.asarray(meta[key], np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, f"{name}.npy"), a)
 
 
 if __name__ == "__main__":

@@ -11,7 +11,7 @@ for cfg in c3 c5; do
   rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/${cfg}_write -o w --output-format csv -- $B --config $cfg --steps 1 --warmup 0 > /dev/null 2> $O/${cfg}_write.err && echo ${cfg}_write ok
   rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_BUSY_CYCLES --kernel-trace -d $O/${cfg}_sq -o s --output-format csv -- $B --config $cfg --steps 1 --warmup 0 > /dev/null 2> $O/${cfg}_sq.err && echo ${cfg}_sq ok
 done
-python3 $R/bench.py > $O/bench_c3.json 2> $O/bench_c3.err && echo bench_c3 ok
-python3 $R/bench.py --config c5 > $O/bench_c5.json 2> $O/bench_c5.err && echo bench_c5 ok
-python3 $R/bench.py --config c2 > $O/bench_c2.json 2> $O/bench_c2.err && echo bench_c2 ok
+python3 $R/bench.py --full > $O/bench_c3.json 2> $O/bench_c3.err && echo bench_c3 ok
+python3 $R/bench.py --full --config c5 > $O/bench_c5.json 2> $O/bench_c5.err && echo bench_c5 ok
+python3 $R/bench.py --full --config c2 > $O/bench_c2.json 2> $O/bench_c2.err && echo bench_c2 ok
 ls $O

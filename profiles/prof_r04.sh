@@ -24,10 +24,10 @@ cp $(find $O/c3_stats -name "*kernel_stats.csv" | head -1) $O/r04_c3_16384_kerne
 cp $(find $O/c3h_stats -name "*kernel_stats.csv" | head -1) $O/r04_c3_hard_16384_kernel_stats.csv
 cp $(find $O/c5_stats -name "*kernel_stats.csv" | head -1) $O/r04_c5_16384_kernel_stats.csv
 rm -rf $O/c3_stats $O/c3h_stats $O/c5_stats $O/*_fetch $O/*_write $O/*_sq
-python3 $R/bench.py > $O/r04_bench_c3.json 2> $O/bench_c3.err && echo bench_c3 ok
-python3 $R/bench.py --data hard --no-extras > $O/r04_bench_c3_hard.json 2> $O/bench_c3h.err && echo bench_c3_hard ok
-python3 $R/bench.py --config c5 > $O/r04_bench_c5.json 2> $O/bench_c5.err && echo bench_c5 ok
-python3 $R/bench.py --config c2 > $O/r04_bench_c2.json 2> $O/bench_c2.err && echo bench_c2 ok
+python3 $R/bench.py --full > $O/r04_bench_c3.json 2> $O/bench_c3.err && echo bench_c3 ok
+python3 $R/bench.py --full --data hard --no-extras > $O/r04_bench_c3_hard.json 2> $O/bench_c3h.err && echo bench_c3_hard ok
+python3 $R/bench.py --full --config c5 > $O/r04_bench_c5.json 2> $O/bench_c5.err && echo bench_c5 ok
+python3 $R/bench.py --full --config c2 > $O/r04_bench_c2.json 2> $O/bench_c2.err && echo bench_c2 ok
 # every collective of a step through a ONE-rank RCCL communicator: driven by the library itself (native), through the
 # torch.distributed callback, and the same call without any communication path
 python3 $R/bench.py --no-extras --no-cpu-baseline --rccl-single --comm native > $O/r04_bench_c3_rccl_single_rank.json 2> $O/rccl_native.err && echo rccl_native ok

@@ -999,6 +999,41 @@ def test_bench_raster_whole_path_vs_cpu_oracle(ctx, oracle, kind):
 BENCH_RASTER_LABEL_BOUND = {"easy": 16, "hard": 4096}
 
 
+def test_bench_dump_outputs_are_what_the_timed_step_computes(ctx, tmp_path):
+    """`bench.py --dump-outputs DIR` writes what its last timed step computed: the dumped sample equals config 3 run here on the
+    same raster (labels, the 15 feature planes, the KMeans state), the label histogram covers every pixel, the files are float32 /
+    float64 and stay under 64 MB.  The plain line carries the headline only: no CPU baseline, no side figures."""
+    import json
+    import subprocess
+    import sys as _sys
+    import torch
+    import bench
+    from rsseg import pipeline as P
+    H = W = 1024
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    e = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([_sys.executable, os.path.join(root, "bench.py"), "--size", str(H), "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")], env=e, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["cpu_baseline"] is None
+    assert not {"glcm_step7", "hard_raster", "uint8_resident", "pcie_inclusive", "c5_16384"} & set(line["config"])
+    files = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert sum(os.path.getsize(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")) <= 64 * 2 ** 20
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    bands = bench.synth_rows(torch, ctx.device, W, 0, H)
+    labels, meta, planes = P.config3(ctx, bands, H, W, 8, 7, 1, 3, H * W)
+    idx = files["sample_index"].astype(np.int64)
+    assert 0 < idx.size < H * W and np.all(np.diff(idx) > 0) and idx[-1] < H * W
+    got = host(labels)
+    assert np.array_equal(files["labels_sample"], got[idx].astype(np.float32))
+    assert np.array_equal(files["features_sample"], np.stack([host(p)[idx] for p in planes]))
+    vals, cnt = np.unique(got, return_counts=True)
+    assert np.array_equal(files["labels_count"], np.stack([vals, cnt], 1).astype(np.float64))
+    assert files["kmeans_n_iter"] == meta["n_iter"] and np.array_equal(files["kmeans_centers"], meta["centers"])
+    assert np.array_equal(files["kmeans_init_indices"], np.asarray(meta["init_indices"], np.float64))
+
+
 @pytest.mark.parametrize("seed", [20, 22, 25, 26, 29, 30])
 def test_kmeans_empty_cluster_relocation(ctx, oracle, seed):
     """Duplicate-heavy data with more clusters than distinct points: clusters run empty and are re-seeded
