@@ -97,6 +97,12 @@ int ws_reserve(rsseg_ctx *ctx, size_t bytes);
 int pin_reserve(rsseg_ctx *ctx, size_t bytes);
 // all-reduce of a small host array through the device comm buffer (no-op when world == 1)
 int comm_allreduce_host(rsseg_ctx *ctx, void *host, int64_t count, int dtype, int op);
+// all-reduce of `count` elements at byte `byte_off` of the device comm buffer, in place and ordered on ctx->stream: no
+// staging copy, no host synchronisation (include/rsseg.h, rsseg_allreduce_fn; no-op when no hook is installed)
+__attribute__((visibility("hidden"))) int comm_allreduce_dev(rsseg_ctx *ctx, int64_t byte_off, int64_t count, int dtype, int op);
+// raises `kernel`'s dynamic-LDS limit on ctx's device to at least `bytes`: hipFuncSetAttribute runs only when the largest
+// limit granted so far to that kernel on that device is smaller.  (Both hidden: they are not part of the exported symbols.)
+__attribute__((visibility("hidden"))) int set_max_dyn_lds(rsseg_ctx *ctx, const void *kernel, size_t bytes);
 int stream_sync(rsseg_ctx *ctx);
 
 // scoped kernel timer (HIP events on ctx->stream) — active only when profiling is on

@@ -252,6 +252,16 @@ extern "C" int rsseg_ctx_set_comm(rsseg_ctx *ctx, int rank, int world, rsseg_all
     return RSSEG_OK;
 }
 
+// the installed all-reduce on `count` elements at byte `offset` of the comm buffer; a failure names RCCL's message
+static int comm_hook(rsseg_ctx *ctx, int64_t offset, int64_t count, int dtype, int op)
+{
+    const int rc = ctx->allreduce(ctx->comm_user, offset, count, dtype, op);
+    if (rc == 0) return RSSEG_OK;
+    char why[sizeof(ctx->err)];      // the native provider leaves RCCL's message in ctx->err: copy before formatting into it
+    snprintf(why, sizeof(why), "%s", ctx->rccl_comm ? ctx->err : "");
+    return rs_fail(ctx, RSSEG_ERR_COMM, "all-reduce returned %d%s%.400s", rc, why[0] ? ": " : "", why);
+}
+
 extern "C" int rsseg_ctx_allreduce(rsseg_ctx *ctx, int64_t offset, int64_t count, int dtype, int op)
 {
     if (!ctx) return RSSEG_ERR_INVALID;
@@ -260,13 +270,7 @@ extern "C" int rsseg_ctx_allreduce(rsseg_ctx *ctx, int64_t offset, int64_t count
         (size_t)offset + (dtype == RSSEG_F32 ? 4 : 8) * (size_t)count > ctx->comm_bytes)
         return rs_fail(ctx, RSSEG_ERR_INVALID, "allreduce: bad dtype / op / range");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int rc = ctx->allreduce(ctx->comm_user, offset, count, dtype, op);
-    if (rc != 0) {
-        char why[sizeof(ctx->err)];      // the native provider leaves RCCL's message in ctx->err: copy before formatting into it
-        snprintf(why, sizeof(why), "%s", ctx->rccl_comm ? ctx->err : "");
-        return rs_fail(ctx, RSSEG_ERR_COMM, "all-reduce returned %d%s%.400s", rc, why[0] ? ": " : "", why);
-    }
-    return RSSEG_OK;
+    return comm_hook(ctx, offset, count, dtype, op);
 }
 
 int ws_reserve(rsseg_ctx *ctx, size_t bytes)
@@ -342,6 +346,34 @@ int comm_allreduce_host(rsseg_ctx *ctx, void *host, int64_t count, int dtype, in
         e.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         e.launches++;
     }
+    return RSSEG_OK;
+}
+
+int comm_allreduce_dev(rsseg_ctx *ctx, int64_t byte_off, int64_t count, int dtype, int op)
+{
+    if (!ctx->comm_on) return RSSEG_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    RSCHK(comm_hook(ctx, byte_off, count, dtype, op));
+    if (ctx->prof_on) {  // host wall time of enqueuing the collective, name "allreduce"
+        prof_entry &e = ctx->prof["allreduce"];
+        e.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        e.launches++;
+    }
+    return RSSEG_OK;
+}
+
+int set_max_dyn_lds(rsseg_ctx *ctx, const void *kernel, size_t bytes)
+{
+    static std::mutex mu;     // contexts of several threads (one per rank in the threaded tests) may arrive together
+    static struct { int device; const void *kernel; size_t bytes; } granted[1024];
+    static int used = 0;
+    std::lock_guard<std::mutex> g(mu);
+    int i = 0;
+    while (i < used && (granted[i].device != ctx->device || granted[i].kernel != kernel)) i++;
+    if (i == used && used < 1024) granted[used++] = {ctx->device, kernel, 0};   // a full table only costs repeated calls
+    if (i < used && granted[i].bytes >= bytes) return RSSEG_OK;
+    HIPCHK(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (i < used) granted[i].bytes = bytes;
     return RSSEG_OK;
 }
 

@@ -592,7 +592,7 @@ extern "C" int rsseg_forest_predict(rsseg_ctx *ctx, const float *const *d_planes
         const int cap = rf_lds_cap(F, TH);
         const size_t lds = (size_t)(F | 1) * TH * 4 + (size_t)cap * sizeof(rf_node) + 16;
         auto launch = [&](auto kern) -> int {
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            RSCHK(set_max_dyn_lds(ctx, (const void *)kern, lds));
             prof_scope ps(ctx, "forest");
             hipLaunchKernelGGL(kern, dim3(grid), dim3(TH / RF_PX), lds, ctx->stream, pl, F, n, (const rf_node *)fd.d_nodes, d_trees,
                                (const rf_group *)fd.d_groups, fd.n_groups, cap / 2, fd.max_depth >= 10 ? 1 : 0, fd.n_trees, (const double *)fd.d_leafval, fd.n_classes, d_classes,
@@ -617,7 +617,7 @@ extern "C" int rsseg_forest_predict(rsseg_ctx *ctx, const float *const *d_planes
         while (ntop > 256 && (size_t)F * TH * 4 + (size_t)RF_C * ntop * sizeof(rf_node) > 158 * 1024) ntop -= 256;
         const size_t lds = (size_t)F * TH * 4 + (size_t)RF_C * ntop * sizeof(rf_node);
         auto launch = [&](auto kern) -> int {
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            RSCHK(set_max_dyn_lds(ctx, (const void *)kern, lds));
             prof_scope ps(ctx, "forest");
             hipLaunchKernelGGL(kern, dim3(grid), dim3(TH), lds, ctx->stream, pl, F, n, (const rf_node *)fd.d_nodes, d_trees, fd.n_trees, ntop,
                                (const double *)fd.d_leafval, fd.n_classes, d_classes, (long long *)d_out);

@@ -6,7 +6,6 @@
 // builds LDS-private histograms per workgroup (one 2048-bin table per distinct key prefix still
 // alive) and flushes the non-zero bins to HBM with 64-bit atomics.  HBM-bound: 12 B/px for any
 // number of ranks <= RSSEG_MAX_RANKS.
-#include <mutex>
 
 #include "common.h"
 
@@ -236,21 +235,14 @@ static int order_stats_core(rsseg_ctx *ctx, const float *const *d_planes, int P,
     if (ctx->comm_on && (size_t)P * hist_bytes > ctx->comm_bytes)
         return rs_fail(ctx, RSSEG_ERR_COMM, "order_stats: %d planes may need a %zu-byte communication buffer", P, (size_t)P * hist_bytes);
 
-    static bool attr_done[64] = {false};  // hipFuncSetAttribute is per device
-    static std::mutex attr_mu;            // contexts of several threads (one per rank in the threaded tests) may arrive together
     const int SEL_BATCH = 8;  // live prefixes per launch: 8 * (8 KB counters + 2 KB lookup) + 2 KB of LDS
-    std::unique_lock<std::mutex> attr_lock(attr_mu);
-    if (!attr_done[ctx->device & 63]) {
-        const int l1 = SEL_BATCH * SEL_BINS * 4 + SEL_BINS, l2 = SEL_BATCH * SEL_BINS * 5 + SEL_BINS, l0 = P0_COPIES * P0_STRIDE * 4;
-#define SEL_ATTR(TH)                                                                                                       \
-    HIPCHK(ctx, hipFuncSetAttribute((const void *)k1_hist<0, TH, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, l0));    \
-    HIPCHK(ctx, hipFuncSetAttribute((const void *)k1_hist<1, TH, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, l1));    \
-    HIPCHK(ctx, hipFuncSetAttribute((const void *)k1_hist<2, TH, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, l2));    \
-    HIPCHK(ctx, hipFuncSetAttribute((const void *)k1_hist<3, TH, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, l0));
-        SEL_ATTR(1024)
-        attr_done[ctx->device & 63] = true;
+    {
+        const size_t l1 = SEL_BATCH * SEL_BINS * 4 + SEL_BINS, l2 = SEL_BATCH * SEL_BINS * 5 + SEL_BINS, l0 = P0_COPIES * P0_STRIDE * 4;
+        RSCHK(set_max_dyn_lds(ctx, (const void *)k1_hist<0, 1024, 4>, l0));
+        RSCHK(set_max_dyn_lds(ctx, (const void *)k1_hist<1, 1024, 4>, l1));
+        RSCHK(set_max_dyn_lds(ctx, (const void *)k1_hist<2, 1024, 4>, l2));
+        RSCHK(set_max_dyn_lds(ctx, (const void *)k1_hist<3, 1024, 4>, l0));
     }
-    attr_lock.unlock();
     const int threads = 1024;
     // 512 workgroups = the two per CU that are resident anyway (66 KB of LDS each): every workgroup clears and flushes its
     // tables once.  profiles/r04_k1_sweep.json: 0.174 ms per 16384^2 plane (6.2 TB/s) against 0.200 ms with 2048 workgroups

@@ -15,13 +15,13 @@
 //     fixed-point sum (quantum 2^-40), so results do not depend on the launch geometry, on atomics
 //     or on how the raster is sharded over GPUs.
 //
-// Data movement per Lloyd iteration: F planes read once (4F B/px for float32) + 1 B/px label read
-// + 1 B/px label write; a lane keeps the F values of its pixels in registers from one batch of loads, so the
-// per-cluster accumulation (LDS atomics on bank-private copies) needs no second read.  HBM-bound.
+// Data movement per Lloyd iteration of the device-resident loop: F planes read once (4F B/px for float32) and nothing
+// else — its update sweeps neither read nor write labels (r04); only the final E-step and the tracked sweeps of the
+// host-side loop touch a label plane.  A lane keeps the F values of its pixels in registers from one batch of loads, so
+// the per-cluster accumulation (LDS atomics on bank-private copies) needs no second read.  HBM-bound.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <mutex>
 #include <type_traits>
 
 #include "common.h"
@@ -1130,7 +1130,6 @@ template <typename T> struct km_state {
     T current_pot;
     u128 rank_tot[RSSEG_MAX_RANKS];                         // every rank's total of the closest-distance sums
 };
-template <typename T> using lloyd_state = km_state<T>;
 
 template <typename T> __device__ __forceinline__ T t_sqrt(T x);
 template <> __device__ __forceinline__ float t_sqrt<float>(float x) { return __fsqrt_rn(x); }
@@ -1155,7 +1154,7 @@ template <typename T> __device__ __forceinline__ void kl_fill_cenT(const km_stat
 
 // cenT[f * KMAX + j] = C[j][f] (zeros elsewhere), csq[j] = fma chain of C[j][f]^2 over f — row_norms(centers, squared=True)
 template <typename T>
-__global__ __launch_bounds__(KM_THREADS) void kl_prepare(const lloyd_state<T> *__restrict__ st, int k, int F, int KMAX, T *__restrict__ cenT,
+__global__ __launch_bounds__(KM_THREADS) void kl_prepare(const km_state<T> *__restrict__ st, int k, int F, int KMAX, T *__restrict__ cenT,
                                                          int force)
 {
     if (st->done && !force) return;
@@ -1184,7 +1183,7 @@ template <typename T> __device__ T dev_pairwise_sum(const T *a, int n)   // nump
 
 // red: [M][2] limb sums of this iteration over all ranks (km_reduce_cols, all-reduced), M = KMAX * F + KMAX + 1
 template <typename T>
-__global__ __launch_bounds__(KM_THREADS) void kl_update(lloyd_state<T> *st, int k, int F, int KMAX, const long long *__restrict__ red,
+__global__ __launch_bounds__(KM_THREADS) void kl_update(km_state<T> *st, int k, int F, int KMAX, const long long *__restrict__ red,
                                                         long long *__restrict__ red_saved, T *__restrict__ cenT)
 {
     if (st->done) return;
@@ -1648,176 +1647,255 @@ double now_ms()
 // combine {hi, lo} limb sums (km_reduce_cols) into one signed 128-bit value
 i128 limbs(long long hi, long long lo) { return ((i128)hi << 32) + (i128)lo; }
 
-template <typename T, int KMAX, int FR>
-int launch_lloyd2(rsseg_ctx *ctx, bool update, int64_t nchunks, size_t lds, planes_t pl, int F, int k, int64_t n,
-                  const scaler_t<T> *sp, const T *cenT, const T *csq, uint8_t *labels, long long *partial, int ncopies, const int *done,
-                  int32_t *out32)
+// ---- the launch table: which instantiation serves (T, KMAX, F) ----
+// A kernel holds FR = 8, 16 or 32 planes of its pixels in registers, or KM_BLOCKED for 33 ... RSSEG_MAX_FEATURES planes:
+// km_kpp_blk / km_lloyd_blk then hold one block of KM_FB planes at a time, km_farthest<T, KMAX, 64> all of them.
+constexpr int KM_BLOCKED = 64;
+static_assert(RSSEG_MAX_FEATURES <= KM_BLOCKED, "km_farthest<T, KMAX, KM_BLOCKED> holds every plane");
+constexpr int km_width(int F) { return F <= 8 ? 8 : (F <= 16 ? 16 : (F <= 32 ? 32 : KM_BLOCKED)); }
+constexpr int km_kmax(int k) { return k <= 8 ? 8 : (k <= 16 ? 16 : (k <= 32 ? 32 : 64)); }
+
+// The Lloyd kernel of (T, KMAX, F).  float64 planes with 33 ... 64 clusters: the register-resident kernels for 9 ... 32 planes
+// would need more than 512 registers (252 - 628 bytes of scratch per lane in the r03 code object), so they take
+// the feature-blocked kernel, which holds one block of planes at a time (346 - 370 registers), same arithmetic, same bits.
+template <typename T> constexpr int lloyd_form(int KMAX, int F)
 {
-    if (update) {
-        // per device: the dynamic-LDS limit already granted to this instantiation (contexts of several threads may race here)
-        static std::mutex mu;
-        static size_t attr[64] = {0};
-        {
-            std::lock_guard<std::mutex> g(mu);
-            size_t &have = attr[ctx->device & 63];
-            if (have == 0) have = 48 * 1024;  // default limit without the attribute
-            if (lds > have) {
-                HIPCHK(ctx, hipFuncSetAttribute((const void *)km_lloyd<T, KMAX, FR, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                have = lds;
-            }
-        }
-        hipLaunchKernelGGL((km_lloyd<T, KMAX, FR, true>), dim3((unsigned)nchunks), dim3(KM_THREADS), lds, ctx->stream, pl, F, k, n, sp,
-                           cenT, csq, labels, partial, nchunks, ncopies, done, (int32_t *)nullptr);
-    } else {
-        hipLaunchKernelGGL((km_lloyd<T, KMAX, FR, false>), dim3((unsigned)nchunks), dim3(KM_THREADS), 0, ctx->stream, pl, F, k, n, sp,
-                           cenT, csq, labels, partial, nchunks, ncopies, done, out32);
+    return std::is_same<T, double>::value && KMAX == 64 && F > 8 ? KM_BLOCKED : km_width(F);
+}
+// Only the register-resident kernels write the caller's int32 plane themselves (km_lloyd's out32, final E-step).
+template <typename T> constexpr bool lloyd_writes_int32(int KMAX, int F) { return lloyd_form<T>(KMAX, F) != KM_BLOCKED; }
+
+// runtime value -> template argument: fn(std::integral_constant<int, V>) for V = KMAX (8, 16, 32, 64) or a width (8, 16, 32, KM_BLOCKED)
+template <int V> using ic = std::integral_constant<int, V>;
+template <typename Fn> auto with_kmax(int KMAX, Fn &&fn)
+{
+    switch (KMAX) {
+    case 8: return fn(ic<8>());
+    case 16: return fn(ic<16>());
+    case 32: return fn(ic<32>());
+    default: return fn(ic<64>());
     }
-    return RSSEG_OK;
+}
+template <typename Fn> auto with_width(int FR, Fn &&fn)
+{
+    switch (FR) {
+    case 8: return fn(ic<8>());
+    case 16: return fn(ic<16>());
+    case 32: return fn(ic<32>());
+    default: return fn(ic<KM_BLOCKED>());
+    }
 }
 
-template <typename T, int KMAX>
-int launch_lloyd(rsseg_ctx *ctx, bool update, int64_t nchunks, size_t lds, planes_t pl, int F, int k, int64_t n,
+// one E-step sweep over the chunks; with `update` also the per-cluster partial sums (`lds` bytes of accumulator copies)
+template <typename T>
+int launch_lloyd(rsseg_ctx *ctx, bool update, int64_t nchunks, size_t lds, planes_t pl, int F, int k, int KMAX, int64_t n,
                  const scaler_t<T> *sp, const T *cenT, const T *csq, uint8_t *labels, long long *partial, int ncopies, const int *done,
-                 int32_t *out32 = nullptr)
+                 int32_t *out32)
 {
-    // out32: only the register-resident kernels (F <= 32) write the int32 plane themselves; lloyd_writes_int32() tells the caller
-    // float64 planes with 33 ... 64 clusters: the register-resident kernels for 9 ... 32 planes need more than 512 registers
-    // (252 - 628 bytes of scratch per lane in the r03 code object) — the feature-blocked kernel below holds one
-    // block of planes at a time and does not spill at any size (346 - 370 registers), same arithmetic, same bits
-    constexpr bool wide64 = std::is_same<T, double>::value && KMAX == 64;
-    if (F <= 8) return launch_lloyd2<T, KMAX, 8>(ctx, update, nchunks, lds, pl, F, k, n, sp, cenT, csq, labels, partial, ncopies, done, out32);
-    if (!wide64) {
-        if (F <= 16) return launch_lloyd2<T, KMAX, 16>(ctx, update, nchunks, lds, pl, F, k, n, sp, cenT, csq, labels, partial, ncopies, done, out32);
-        if (F <= 32) return launch_lloyd2<T, KMAX, 32>(ctx, update, nchunks, lds, pl, F, k, n, sp, cenT, csq, labels, partial, ncopies, done, out32);
-    }
-    // 32 < F <= RSSEG_MAX_FEATURES: the feature-blocked kernel
-    if (update) {
-        static std::mutex mu;
-        static size_t attr[64] = {0};
-        {
-            std::lock_guard<std::mutex> g(mu);
-            size_t &have = attr[ctx->device & 63];
-            if (have == 0) have = 48 * 1024;
-            if (lds > have) {
-                HIPCHK(ctx, hipFuncSetAttribute((const void *)km_lloyd_blk<T, KMAX, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                have = lds;
+    return with_kmax(KMAX, [&](auto kmax_c) {
+        constexpr int KM = decltype(kmax_c)::value;
+        return with_width(lloyd_form<T>(KMAX, F), [&](auto fr_c) -> int {
+            constexpr int FR = decltype(fr_c)::value;
+            const dim3 grid((unsigned)nchunks), block(KM_THREADS);
+            if constexpr (lloyd_form<T>(KM, FR) != FR) {
+                return RSSEG_OK;   // the table never picks this width for (T, KM): not instantiated
+            } else if constexpr (FR == KM_BLOCKED) {
+                if (update) {
+                    RSCHK(set_max_dyn_lds(ctx, (const void *)km_lloyd_blk<T, KM, true>, lds));
+                    hipLaunchKernelGGL((km_lloyd_blk<T, KM, true>), grid, block, lds, ctx->stream, pl, F, k, n, sp, cenT, csq, labels, partial,
+                                       nchunks, ncopies, done);
+                } else {
+                    hipLaunchKernelGGL((km_lloyd_blk<T, KM, false>), grid, block, 0, ctx->stream, pl, F, k, n, sp, cenT, csq, labels, partial,
+                                       nchunks, ncopies, done);
+                }
+            } else {
+                if (update) {
+                    RSCHK(set_max_dyn_lds(ctx, (const void *)km_lloyd<T, KM, FR, true>, lds));
+                    hipLaunchKernelGGL((km_lloyd<T, KM, FR, true>), grid, block, lds, ctx->stream, pl, F, k, n, sp, cenT, csq, labels, partial,
+                                       nchunks, ncopies, done, (int32_t *)nullptr);
+                } else {
+                    hipLaunchKernelGGL((km_lloyd<T, KM, FR, false>), grid, block, 0, ctx->stream, pl, F, k, n, sp, cenT, csq, labels, partial,
+                                       nchunks, ncopies, done, out32);
+                }
             }
-        }
-        hipLaunchKernelGGL((km_lloyd_blk<T, KMAX, true>), dim3((unsigned)nchunks), dim3(KM_THREADS), lds, ctx->stream, pl, F, k, n, sp,
-                           cenT, csq, labels, partial, nchunks, ncopies, done);
-    } else {
-        hipLaunchKernelGGL((km_lloyd_blk<T, KMAX, false>), dim3((unsigned)nchunks), dim3(KM_THREADS), 0, ctx->stream, pl, F, k, n, sp,
-                           cenT, csq, labels, partial, nchunks, ncopies, done);
-    }
-    return RSSEG_OK;
+            return RSSEG_OK;
+        });
+    });
 }
 
-template <typename T, int NL, int FR>
-void launch_kpp3(rsseg_ctx *ctx, int64_t nchunks, planes_t pl, int F, int64_t n, const scaler_t<T> *sp, const double *cand, const double *cc,
-                 int L, int mode, T *closest, unsigned long long *partial)
-{
-#define KPP_GO(M) hipLaunchKernelGGL((km_kpp<T, NL, FR, M>), dim3((unsigned)nchunks), dim3(KM_THREADS), 0, ctx->stream, pl, F, n, sp, cand, cc, L, closest, partial, nchunks)
-    if constexpr (NL == 1) {
-        KPP_GO(0);
-    } else {
-        if (mode == 1) KPP_GO(1);
-        else KPP_GO(2);
-    }
-#undef KPP_GO
-}
-template <typename T, int NL>
-void launch_kpp2(rsseg_ctx *ctx, int64_t nchunks, planes_t pl, int F, int64_t n, const scaler_t<T> *sp, const double *cand, const double *cc,
-                 int L, int mode, T *closest, unsigned long long *partial)
-{
-    if (F <= 8) launch_kpp3<T, NL, 8>(ctx, nchunks, pl, F, n, sp, cand, cc, L, mode, closest, partial);
-    else if (F <= 16) launch_kpp3<T, NL, 16>(ctx, nchunks, pl, F, n, sp, cand, cc, L, mode, closest, partial);
-    else if (F <= 32) launch_kpp3<T, NL, 32>(ctx, nchunks, pl, F, n, sp, cand, cc, L, mode, closest, partial);
-    else {   // feature-blocked kernels; the variance rows of the first pass come from km_var
-#define KPP_GOB(M) hipLaunchKernelGGL((km_kpp_blk<T, NL, M>), dim3((unsigned)nchunks), dim3(KM_THREADS), 0, ctx->stream, pl, F, n, sp, cand, cc, L, closest, partial, nchunks)
-        if constexpr (NL == 1) {
-            KPP_GOB(0);
-            hipLaunchKernelGGL((km_var<T>), dim3((unsigned)nchunks, F), dim3(KM_THREADS), 0, ctx->stream, pl, n, sp, partial, nchunks);
-        } else {
-            if (mode == 1) KPP_GOB(1);
-            else KPP_GOB(2);
-        }
-#undef KPP_GOB
-    }
-}
 // mode 0: first centre (L == 1, no per-pixel output); 1: first sampling round; 2: later rounds
 template <typename T>
 void launch_kpp(rsseg_ctx *ctx, int64_t nchunks, planes_t pl, int F, int64_t n, const scaler_t<T> *sp, const double *cand, const double *cc,
                 int L, int mode, T *closest, unsigned long long *partial)
 {
-    if (mode == 0) launch_kpp2<T, 1>(ctx, nchunks, pl, F, n, sp, cand, cc, 1, 0, closest, partial);
-    else if (L <= 4) launch_kpp2<T, 4>(ctx, nchunks, pl, F, n, sp, cand, cc, L, mode, closest, partial);
-    else launch_kpp2<T, 8>(ctx, nchunks, pl, F, n, sp, cand, cc, L, mode, closest, partial);
-}
-
-template <typename T, int KMAX>
-void launch_farthest(rsseg_ctx *ctx, int64_t nchunks, planes_t pl, int F, int64_t n, int64_t offset, const scaler_t<T> *sp,
-                     const T *cenT, const uint8_t *labels, const taken_t &tk, T *pdist, long long *pidx)
-{
-    if (F <= 8) hipLaunchKernelGGL((km_farthest<T, KMAX, 8>), dim3((unsigned)nchunks), dim3(KM_THREADS), 0, ctx->stream, pl, F, n, offset, sp, cenT, labels, tk, pdist, pidx);
-    else if (F <= 16) hipLaunchKernelGGL((km_farthest<T, KMAX, 16>), dim3((unsigned)nchunks), dim3(KM_THREADS), 0, ctx->stream, pl, F, n, offset, sp, cenT, labels, tk, pdist, pidx);
-    else if (F <= 32) hipLaunchKernelGGL((km_farthest<T, KMAX, 32>), dim3((unsigned)nchunks), dim3(KM_THREADS), 0, ctx->stream, pl, F, n, offset, sp, cenT, labels, tk, pdist, pidx);
-    else hipLaunchKernelGGL((km_farthest<T, KMAX, 64>), dim3((unsigned)nchunks), dim3(KM_THREADS), 0, ctx->stream, pl, F, n, offset, sp, cenT, labels, tk, pdist, pidx);
+    auto go = [&](auto nl_c, auto mode_c) {
+        constexpr int NL = decltype(nl_c)::value, MODE = decltype(mode_c)::value;
+        with_width(km_width(F), [&](auto fr_c) {
+            constexpr int FR = decltype(fr_c)::value;
+            const dim3 grid((unsigned)nchunks), block(KM_THREADS);
+            if constexpr (FR != KM_BLOCKED) {
+                hipLaunchKernelGGL((km_kpp<T, NL, FR, MODE>), grid, block, 0, ctx->stream, pl, F, n, sp, cand, cc, L, closest, partial, nchunks);
+            } else {   // feature-blocked kernels; the variance rows of the first pass come from km_var
+                hipLaunchKernelGGL((km_kpp_blk<T, NL, MODE>), grid, block, 0, ctx->stream, pl, F, n, sp, cand, cc, L, closest, partial, nchunks);
+                if constexpr (MODE == 0)
+                    hipLaunchKernelGGL((km_var<T>), dim3((unsigned)nchunks, F), block, 0, ctx->stream, pl, n, sp, partial, nchunks);
+            }
+        });
+    };
+    if (mode == 0) go(ic<1>(), ic<0>());
+    else if (L <= 4) mode == 1 ? go(ic<4>(), ic<1>()) : go(ic<4>(), ic<2>());
+    else mode == 1 ? go(ic<8>(), ic<1>()) : go(ic<8>(), ic<2>());
 }
 
 template <typename T>
-int kmeans_fit(rsseg_ctx *ctx, const void *const *d_planes, int F, int64_t n, int k, uint32_t seed, int max_iter, double tol_in,
-               int32_t *d_labels, double *centers_out, rsseg_kmeans_info *info, const double *known_min, const double *known_max)
+void launch_farthest(rsseg_ctx *ctx, int KMAX, int64_t nchunks, planes_t pl, int F, int64_t n, int64_t offset, const scaler_t<T> *sp,
+                     const T *cenT, const uint8_t *labels, const taken_t &tk, T *pdist, long long *pidx)
 {
-    const double t_start = now_ms();
-    const int KMAX = k <= 8 ? 8 : (k <= 16 ? 16 : (k <= 32 ? 32 : 64));
-    const int L = 2 + (int)std::log((double)k);
-    if (L > KPP_MAXL) return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "kmeans: too many local trials");
-    constexpr int TILE = km_tile<T>();
-    constexpr int CHUNK = km_chunk<T>();
-    const int64_t nchunks = std::max<int64_t>(1, ceil_div64(n, CHUNK));
-    const int nblk = (int)std::min<int64_t>(2048, std::max<int64_t>(1, ceil_div64(n, (int64_t)KM_THREADS * vt<T>::PXL)));
-    const int M = KMAX * F + KMAX + 1;
+    with_kmax(KMAX, [&](auto kmax_c) {
+        with_width(km_width(F), [&](auto fr_c) {
+            hipLaunchKernelGGL((km_farthest<T, decltype(kmax_c)::value, decltype(fr_c)::value>), dim3((unsigned)nchunks), dim3(KM_THREADS), 0,
+                               ctx->stream, pl, F, n, offset, sp, cenT, labels, tk, pdist, pidx);
+        });
+    });
+}
 
-    // ---- rank geometry: every rank's pixel count travels in the MinMax all-reduce below (one collective fewer) ----
+// exchange regions of a k-means++ round inside the exchange area: the sampled rows at byte 0, the candidates' potentials behind them
+constexpr size_t LIM_OFF = ((sizeof(double) * KPP_MAXL * (1 + RSSEG_MAX_FEATURES)) + 511) & ~(size_t)511;
+constexpr size_t UP_SLOT = 64 * 1024;   // one slot of the pinned upload ring
+
+// One kmeans_fit call: its geometry, workspace, pinned upload ring and host mirror, and one member per phase.  Everything from
+// the column means to the final labels is driven from device-resident state (km_state): the host enqueues sweeps, small control
+// kernels and (world > 1) stream-ordered all-reduces, and waits only for the Lloyd loop's convergence flag and for the final
+// read-back.
+template <typename T> struct km_fit {
+    static constexpr int CHUNK = km_chunk<T>();
+    rsseg_ctx *ctx = nullptr;
+    hipStream_t st = nullptr;
+    planes_t pl;
+    int max_iter = 0;
+    // ---- geometry (N, offset, n_all, last_rank: from scale_and_ranks) ----
+    int F = 0, k = 0, KMAX = 0, L = 0, M = 0, nblk = 0;
+    int64_t n = 0, nchunks = 0, N = 0, offset = 0;
     int64_t n_all[RSSEG_MAX_RANKS] = {0};
-    n_all[ctx->rank] = n;
-    int64_t N = 0, offset = 0;
-    // ---- workspace layout ----
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_sp = carve(sizeof(scaler_t<T>));
-    // centres + their squared norms, candidates + theirs: each pair contiguous, so that one copy uploads both
-    const size_t o_cen = carve(sizeof(T) * ((size_t)KMAX * RSSEG_MAX_FEATURES + KMAX));
-    const size_t o_cand = carve(sizeof(double) * ((size_t)KPP_STRIDE * RSSEG_MAX_FEATURES + KPP_STRIDE));
-    const size_t o_row = carve(sizeof(T) * RSSEG_MAX_FEATURES);
-    const size_t o_samp = carve(sizeof(double) * KPP_MAXL * (1 + RSSEG_MAX_FEATURES));
-    const size_t o_qv = carve(sizeof(unsigned long long) * KPP_MAXL * (size_t)CHUNK);
-    const size_t o_red = carve(sizeof(long long) * std::max<size_t>({(size_t)2 * M, (size_t)3 * RSSEG_MAX_FEATURES + 2 * RSSEG_MAX_RANKS,
-                                                                    (size_t)2 * KPP_MAXL * RSSEG_MAX_RANKS + KPP_MAXL * (1 + RSSEG_MAX_FEATURES) + 64}));
-    const size_t o_sa = carve(sizeof(kpp_sample_args));
-    const size_t o_redsave = carve(sizeof(long long) * 2 * M);
-    const size_t o_lst = carve(sizeof(lloyd_state<T>));
-    const size_t o_mm = carve(sizeof(T) * 2 * (size_t)nblk * F);
-    const size_t o_mom = carve(sizeof(long long) * (size_t)nblk * F);
-    const size_t o_part = carve(sizeof(long long) * std::max<size_t>((size_t)M, KPP_MAXL) * (size_t)nchunks);
-    const size_t dist_stride = (sizeof(T) * (size_t)std::max<int64_t>(n, 1) + 255) & ~(size_t)255;
-    const size_t o_closest = carve(dist_stride);            // the ONE closest-distance plane of k-means++
-    const size_t o_lab = carve((size_t)std::max<int64_t>(n, 1) + 64);
-    RSCHK(ws_reserve(ctx, off));
-    const size_t pin_need = std::max<size_t>({sizeof(T) * 2 * (size_t)nblk * F, sizeof(long long) * (size_t)nblk * F + sizeof(double) * RSSEG_MAX_FEATURES + 64,
-                                              sizeof(long long) * (size_t)std::max(KPP_MAXL, F + 1) * (size_t)nchunks, sizeof(T) * (size_t)CHUNK,
-                                              sizeof(long long) * 2 * (size_t)M + sizeof(km_state<T>), (size_t)65536});
-    // small host-to-device uploads (the state, centres of the host-side iterations) go through a ring of 4 pinned slots behind
-    // the read-back area: the copy is then asynchronous for real and needs no synchronisation before the stack buffer it came
-    // from dies.  Invariant: a slot is reused only after a host synchronisation since its last use — the device-resident
-    // loop makes at most two uploads between two waits today, and the ring enforces it: a fifth upload without a wait in
-    // between (ctx->host_syncs is the epoch) waits for the stream first.
-    constexpr size_t UP_SLOT = 64 * 1024;
-    const size_t pin_main = (pin_need + 255) & ~(size_t)255;
-    RSCHK(pin_reserve(ctx, pin_main + 4 * UP_SLOT));
+    int last_rank = 0;
+    // ---- workspace, carved once (layout) ----
+    struct {
+        scaler_t<T> *sp;
+        T *cen, *csq;          // centres (transposed) + their squared norms, contiguous: one copy uploads both
+        double *cand, *cc;     // k-means++ candidates + theirs, likewise
+        T *row;
+        unsigned long long *qv;
+        long long *red;        // the exchange area when no all-reduce is installed
+        kpp_sample_args *sa;
+        long long *redsave;
+        km_state<T> *lst;
+        T *mm;
+        long long *mom, *part;
+        T *closest;            // the ONE closest-distance plane of k-means++
+        uint8_t *lab;
+    } d;
+    // values that cross ranks: in the communication buffer when an all-reduce is installed (the hook reduces them in place),
+    // else d.red
+    long long *x = nullptr;
+    // ---- pinned upload ring ----
+    size_t pin_main = 0;
     unsigned up_i = 0, up_since_sync = 0;
-    long long up_epoch = ctx->host_syncs;
-    auto upload = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
+    long long up_epoch = 0;
+    // ---- Lloyd accumulators ----
+    int ncopies = KM_COPIES;
+    size_t lds = 0;
+    // ---- host mirror ----
+    scaler_t<T> sp;
+    T C[RSSEG_MAX_CLUSTERS][RSSEG_MAX_FEATURES];
+    int64_t init_idx[RSSEG_MAX_CLUSTERS];
+    T tol = (T)0;                 // known on the host only after the state has come back
+    int it = 0, relocated = 0;
+    bool strict = false;
+
+    int setup(rsseg_ctx *c, int F_, int64_t n_, int k_, int max_iter_)
+    {
+        ctx = c;
+        st = c->stream;
+        F = F_, n = n_, k = k_, max_iter = max_iter_;
+        KMAX = km_kmax(k);
+        L = 2 + (int)std::log((double)k);
+        if (L > KPP_MAXL) return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "kmeans: too many local trials");
+        M = KMAX * F + KMAX + 1;
+        nchunks = std::max<int64_t>(1, ceil_div64(n, CHUNK));
+        nblk = (int)std::min<int64_t>(2048, std::max<int64_t>(1, ceil_div64(n, (int64_t)KM_THREADS * vt<T>::PXL)));
+        // Lloyd accumulator copies: 32 when they fit in ~48 KB (3 workgroups per CU), fewer for large k * F
+        while (ncopies > 1 && sizeof(long long) * (size_t)ncopies * km_copy_stride(KMAX, F) > 48 * 1024) ncopies >>= 1;
+        lds = sizeof(long long) * (size_t)ncopies * km_copy_stride(KMAX, F);
+        if (lds > 150 * 1024) return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "kmeans: F=%d, k=%d needs %zu B of LDS", F, k, lds);
+        return RSSEG_OK;
+    }
+
+    // workspace, exchange area, pinned area, planes
+    int layout(const void *const *d_planes)
+    {
+        // the exchange area holds, one at a time: the column sums + first row (3F), np.var + rank totals (2F + 2 world), a
+        // k-means++ round (sampled rows, then the potentials at LIM_OFF), the Lloyd sums (2M)
+        const size_t x_bytes = sizeof(long long) * std::max<size_t>({(size_t)2 * M, (size_t)3 * F, (size_t)2 * F + 2 * (size_t)ctx->world,
+                                                                     LIM_OFF / sizeof(long long) + 2 * (size_t)L * ctx->world});
+        if (ctx->comm_on && x_bytes > ctx->comm_bytes) return rs_fail(ctx, RSSEG_ERR_COMM, "kmeans: comm buffer too small (%zu > %zu)", x_bytes, ctx->comm_bytes);
+        size_t off = 0;
+        auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+        const size_t o_sp = carve(sizeof(scaler_t<T>));
+        const size_t o_cen = carve(sizeof(T) * ((size_t)KMAX * RSSEG_MAX_FEATURES + KMAX));
+        const size_t o_cand = carve(sizeof(double) * ((size_t)KPP_STRIDE * RSSEG_MAX_FEATURES + KPP_STRIDE));
+        const size_t o_row = carve(sizeof(T) * RSSEG_MAX_FEATURES);
+        const size_t o_qv = carve(sizeof(unsigned long long) * KPP_MAXL * (size_t)CHUNK);
+        const size_t o_red = carve(x_bytes);
+        const size_t o_sa = carve(sizeof(kpp_sample_args));
+        const size_t o_redsave = carve(sizeof(long long) * 2 * M);
+        const size_t o_lst = carve(sizeof(km_state<T>));
+        const size_t o_mm = carve(sizeof(T) * 2 * (size_t)nblk * F);
+        const size_t o_mom = carve(sizeof(long long) * (size_t)nblk * F);
+        const size_t o_part = carve(sizeof(long long) * std::max<size_t>((size_t)M, KPP_MAXL) * (size_t)nchunks);
+        const size_t o_closest = carve((sizeof(T) * (size_t)std::max<int64_t>(n, 1) + 255) & ~(size_t)255);
+        const size_t o_lab = carve((size_t)std::max<int64_t>(n, 1) + 64);
+        RSCHK(ws_reserve(ctx, off));
+        char *ws = ctx->d_ws;
+        d.sp = (scaler_t<T> *)(ws + o_sp);
+        d.cen = (T *)(ws + o_cen);
+        d.csq = d.cen + (size_t)KMAX * RSSEG_MAX_FEATURES;
+        d.cand = (double *)(ws + o_cand);
+        d.cc = d.cand + (size_t)KPP_STRIDE * RSSEG_MAX_FEATURES;
+        d.row = (T *)(ws + o_row);
+        d.qv = (unsigned long long *)(ws + o_qv);
+        d.red = (long long *)(ws + o_red);
+        d.sa = (kpp_sample_args *)(ws + o_sa);
+        d.redsave = (long long *)(ws + o_redsave);
+        d.lst = (km_state<T> *)(ws + o_lst);
+        d.mm = (T *)(ws + o_mm);
+        d.mom = (long long *)(ws + o_mom);
+        d.part = (long long *)(ws + o_part);
+        d.closest = (T *)(ws + o_closest);
+        d.lab = (uint8_t *)(ws + o_lab);
+        x = ctx->comm_on ? (long long *)ctx->d_comm : d.red;
+        // host read-backs at the head of the pinned area, the upload ring behind them
+        const size_t pin_need = std::max<size_t>({sizeof(T) * 2 * (size_t)nblk * F, sizeof(long long) * (size_t)nblk * F + sizeof(double) * RSSEG_MAX_FEATURES + 64,
+                                                  sizeof(long long) * (size_t)std::max(KPP_MAXL, F + 1) * (size_t)nchunks, sizeof(T) * (size_t)CHUNK,
+                                                  sizeof(long long) * 2 * (size_t)M + sizeof(km_state<T>), (size_t)65536});
+        pin_main = (pin_need + 255) & ~(size_t)255;
+        RSCHK(pin_reserve(ctx, pin_main + 4 * UP_SLOT));
+        up_epoch = ctx->host_syncs;
+        memset(&pl, 0, sizeof(pl));
+        for (int f = 0; f < F; f++) {
+            // a rank without pixels (n_local == 0) may pass anything, also NULL: its planes are never read
+            if (n > 0 && (!d_planes[f] || ((uintptr_t)d_planes[f] & 15))) return rs_fail(ctx, RSSEG_ERR_INVALID, "kmeans: plane %d null or not 16-byte aligned", f);
+            pl.p[f] = d_planes[f];
+        }
+        return RSSEG_OK;
+    }
+
+    // Small host-to-device uploads (the state, centres of the host-side iterations) go through a ring of 4 pinned slots behind
+    // the read-back area: the copy is then asynchronous for real and needs no synchronisation before the buffer it came from
+    // dies.  Invariant: a slot is reused only after a host synchronisation since its last use — the device-resident loop makes
+    // at most two uploads between two waits today, and the ring enforces it: a fifth upload without a wait in between
+    // (ctx->host_syncs is the epoch) waits for the stream first.
+    hipError_t upload(void *dst, const void *src, size_t bytes)
+    {
         if (ctx->host_syncs != up_epoch) { up_epoch = ctx->host_syncs; up_since_sync = 0; }
         if (up_since_sync == 4) {          // every slot is (possibly) still being copied
             const hipError_t e = rs_sync(ctx);
@@ -1828,44 +1906,18 @@ int kmeans_fit(rsseg_ctx *ctx, const void *const *d_planes, int F, int64_t n, in
         up_since_sync++;
         char *slot = ctx->h_pin + pin_main + (size_t)(up_i++ & 3u) * UP_SLOT;
         memcpy(slot, src, bytes);
-        return hipMemcpyAsync(dst, slot, bytes, hipMemcpyHostToDevice, ctx->stream);
-    };
-    char *ws = ctx->d_ws;
-    scaler_t<T> *d_sp = (scaler_t<T> *)(ws + o_sp);
-    T *d_cen = (T *)(ws + o_cen);
-    T *d_csq = d_cen + (size_t)KMAX * RSSEG_MAX_FEATURES;
-    double *d_cand = (double *)(ws + o_cand);
-    double *d_cc = d_cand + (size_t)KPP_STRIDE * RSSEG_MAX_FEATURES;
-    T *d_row = (T *)(ws + o_row);
-    double *d_samp = (double *)(ws + o_samp);
-    unsigned long long *d_qv = (unsigned long long *)(ws + o_qv);
-    long long *d_red = (long long *)(ws + o_red);
-    long long *d_redsave = (long long *)(ws + o_redsave);
-    lloyd_state<T> *d_lst = (lloyd_state<T> *)(ws + o_lst);
-    T *d_mm = (T *)(ws + o_mm);
-    long long *d_mom = (long long *)(ws + o_mom);
-    long long *d_part = (long long *)(ws + o_part);
-    T *d_closest = (T *)(ws + o_closest);
-    uint8_t *d_lab = (uint8_t *)(ws + o_lab);
-    hipStream_t st = ctx->stream;
-
-    planes_t pl;
-    memset(&pl, 0, sizeof(pl));
-    for (int f = 0; f < F; f++) {
-        // a rank without pixels (n_local == 0) may pass anything, also NULL: its planes are never read
-        if (n > 0 && (!d_planes[f] || ((uintptr_t)d_planes[f] & 15))) return rs_fail(ctx, RSSEG_ERR_INVALID, "kmeans: plane %d null or not 16-byte aligned", f);
-        pl.p[f] = d_planes[f];
+        return hipMemcpyAsync(dst, slot, bytes, hipMemcpyHostToDevice, st);
     }
 
-    // ---- MinMaxScaler.fit ----
-    scaler_t<T> sp;
-    memset(&sp, 0, sizeof(sp));
+    // ---- MinMaxScaler.fit; every rank's pixel count travels in the same all-reduce (rank geometry) ----
+    int scale_and_ranks(const double *known_min, const double *known_max)
     {
+        memset(&sp, 0, sizeof(sp));
         const bool known = known_min != nullptr && known_max != nullptr;  // this rank's extrema came with the planes
         if (n > 0 && !known) {
-            hipLaunchKernelGGL((km_minmax<T>), dim3(nblk, F), dim3(KM_THREADS), 0, st, pl, n, d_mm, d_mm + (size_t)nblk * F);
+            hipLaunchKernelGGL((km_minmax<T>), dim3(nblk, F), dim3(KM_THREADS), 0, st, pl, n, d.mm, d.mm + (size_t)nblk * F);
             HIPCHK(ctx, hipGetLastError());
-            HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d_mm, sizeof(T) * 2 * (size_t)nblk * F, hipMemcpyDeviceToHost, st));
+            HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d.mm, sizeof(T) * 2 * (size_t)nblk * F, hipMemcpyDeviceToHost, st));
             HIPCHK(ctx, rs_sync(ctx));
         }
         const T *hmn = (const T *)ctx->h_pin, *hmx = hmn + (size_t)nblk * F;
@@ -1889,6 +1941,7 @@ int kmeans_fit(rsseg_ctx *ctx, const void *const *d_planes, int F, int64_t n, in
             n_all[r] = (int64_t)mm[2 * F + r];
             if (r < ctx->rank) offset += n_all[r];
             N += n_all[r];
+            if (n_all[r] > 0) last_rank = r;
         }
         if (N <= 0) return rs_fail(ctx, RSSEG_ERR_INVALID, "kmeans: no pixels");
         if (N < k) return rs_fail(ctx, RSSEG_ERR_INVALID, "kmeans: n_samples=%lld should be >= n_clusters=%d", (long long)N, k);
@@ -1902,159 +1955,107 @@ int kmeans_fit(rsseg_ctx *ctx, const void *const *d_planes, int F, int64_t n, in
             sp.scale[f] = sc;
             sp.minv[f] = mv;
         }
-    }
-    HIPCHK(ctx, hipMemcpyAsync(d_sp, &sp, sizeof(sp), hipMemcpyHostToDevice, st));
-
-    // ---- everything from here to the final labels is driven from device-resident state (km_state): the host enqueues
-    // sweeps, small control kernels and (world > 1) stream-ordered all-reduces, and waits only for the Lloyd loop's
-    // convergence flag and for the final read-back ----
-    mt19937 rng(seed);
-    T C[RSSEG_MAX_CLUSTERS][RSSEG_MAX_FEATURES];
-    int64_t init_idx[RSSEG_MAX_CLUSTERS];
-    int last_rank = 0;
-    for (int rk = 0; rk < ctx->world; rk++)
-        if (n_all[rk] > 0) last_rank = rk;
-    // values that cross ranks: in the communication buffer when world > 1 (the hook reduces them in place), else in the workspace
-    const size_t x_need = sizeof(long long) * std::max<size_t>({(size_t)2 * M, (size_t)3 * F, (size_t)2 * F + 2 * (size_t)ctx->world,
-                                                                (size_t)2 * KPP_MAXL * RSSEG_MAX_RANKS + KPP_MAXL * (1 + RSSEG_MAX_FEATURES) + 64});
-    if (ctx->comm_on && x_need > ctx->comm_bytes) return rs_fail(ctx, RSSEG_ERR_COMM, "kmeans: comm buffer too small (%zu > %zu)", x_need, ctx->comm_bytes);
-    long long *d_x = ctx->comm_on ? (long long *)ctx->d_comm : d_red;
-    auto dev_allreduce = [&](int64_t byte_off, int64_t count, int dtype, int op) -> int {   // stream-ordered: no staging copy, no host synchronisation
-        if (!ctx->comm_on) return RSSEG_OK;
-        const auto t0c = std::chrono::steady_clock::now();
-        const int rc = ctx->allreduce(ctx->comm_user, byte_off, count, dtype, op);
-        if (rc != 0) return rs_fail(ctx, RSSEG_ERR_COMM, "all-reduce hook returned %d", rc);
-        if (ctx->prof_on) {
-            prof_entry &e = ctx->prof["allreduce"];
-            e.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0c).count();
-            e.launches++;
-        }
+        HIPCHK(ctx, hipMemcpyAsync(d.sp, &sp, sizeof(sp), hipMemcpyHostToDevice, st));
         return RSSEG_OK;
-    };
-    {
-        // The first k-means++ centre (RandomState.choice over N equal weights: the first draw of the generator) is known as
-        // soon as N is; the uniform(size=L) draws of the later rounds follow in the generator's order.
-        km_state<T> hs;
-        memset(&hs, 0, sizeof(hs));
-        const double u0 = rng.random_sample();
-        init_idx[0] = uniform_choice(N, std::is_same<T, float>::value ? RSSEG_F32 : RSSEG_F64, u0);
-        if (init_idx[0] >= N) init_idx[0] = N - 1;
-        for (int i = 0; i < (k - 1) * L; i++) hs.uniforms[i] = rng.random_sample();
-        hs.init_idx[0] = init_idx[0];
-        hs.max_iter = max_iter;
-        for (int r = 0; r < ctx->world; r++) hs.n_all[r] = n_all[r];
-        hs.N = N; hs.offset = offset; hs.n_local = n; hs.nchunks = nchunks;
-        hs.rank = ctx->rank; hs.world = ctx->world; hs.k = k; hs.F = F; hs.L = L; hs.last_rank = last_rank;
-        hs.tol_in = tol_in;
-        static_assert(sizeof(hs) <= UP_SLOT, "upload slot too small");
-        HIPCHK(ctx, upload(d_lst, &hs, sizeof(hs)));
     }
-    kpp_sample_args *d_sa = (kpp_sample_args *)(ws + o_sa);
-    // ---- X.mean(axis=0): exact sums; the first centre's row rides on the same all-reduce (the owner gathers the scaled,
-    // NOT yet centred row — the scaler on the device still has mean 0) ----
+
+    // ---- the device state, X.mean(axis=0) and the first centre ----
+    int means_and_first_seed(uint32_t seed, double tol_in)
     {
+        {
+            // The first k-means++ centre (RandomState.choice over N equal weights: the first draw of the generator) is known as
+            // soon as N is; the uniform(size=L) draws of the later rounds follow in the generator's order.
+            mt19937 rng(seed);
+            km_state<T> hs;
+            memset(&hs, 0, sizeof(hs));
+            const double u0 = rng.random_sample();
+            init_idx[0] = uniform_choice(N, std::is_same<T, float>::value ? RSSEG_F32 : RSSEG_F64, u0);
+            if (init_idx[0] >= N) init_idx[0] = N - 1;
+            for (int i = 0; i < (k - 1) * L; i++) hs.uniforms[i] = rng.random_sample();
+            hs.init_idx[0] = init_idx[0];
+            hs.max_iter = max_iter;
+            for (int r = 0; r < ctx->world; r++) hs.n_all[r] = n_all[r];
+            hs.N = N; hs.offset = offset; hs.n_local = n; hs.nchunks = nchunks;
+            hs.rank = ctx->rank; hs.world = ctx->world; hs.k = k; hs.F = F; hs.L = L; hs.last_rank = last_rank;
+            hs.tol_in = tol_in;
+            static_assert(sizeof(hs) <= UP_SLOT, "upload slot too small");
+            HIPCHK(ctx, upload(d.lst, &hs, sizeof(hs)));
+        }
+        // exact sums; the first centre's row rides on the same all-reduce (the owner gathers the scaled, NOT yet centred row —
+        // the scaler on the device still has mean 0)
         const int64_t li0 = init_idx[0] - offset;
         const bool own0 = li0 >= 0 && li0 < n;
         if (n > 0) {
             {
                 prof_scope ps(ctx, "moment");
-                hipLaunchKernelGGL((km_moment<T>), dim3(nblk, F), dim3(KM_THREADS), 0, st, pl, n, d_sp, d_mom);
+                hipLaunchKernelGGL((km_moment<T>), dim3(nblk, F), dim3(KM_THREADS), 0, st, pl, n, d.sp, d.mom);
             }
-            if (own0) hipLaunchKernelGGL((km_gather_row<T>), dim3(1), dim3(64), 0, st, pl, F, li0, d_sp, d_row);
+            if (own0) hipLaunchKernelGGL((km_gather_row<T>), dim3(1), dim3(64), 0, st, pl, F, li0, d.sp, d.row);
+            hipLaunchKernelGGL(km_reduce_cols, dim3(F), dim3(KM_THREADS), 0, st, (const long long *)d.mom, (int64_t)nblk, x, (const int *)nullptr, 1, 0);
         }
-        if (n > 0) hipLaunchKernelGGL(km_reduce_cols, dim3(F), dim3(KM_THREADS), 0, st, (const long long *)d_mom, (int64_t)nblk, d_x, (const int *)nullptr, 1, 0);
-        hipLaunchKernelGGL((kc_mean_pack<T>), dim3(1), dim3(64), 0, st, (const km_state<T> *)d_lst, (const T *)d_row, own0 ? 1 : 0, d_x);
+        hipLaunchKernelGGL((kc_mean_pack<T>), dim3(1), dim3(64), 0, st, (const km_state<T> *)d.lst, (const T *)d.row, own0 ? 1 : 0, x);
         HIPCHK(ctx, hipGetLastError());
-        RSCHK(dev_allreduce(0, 3 * F, RSSEG_I64, RSSEG_SUM));
-        hipLaunchKernelGGL((kc_mean_apply<T>), dim3(1), dim3(KM_THREADS), 0, st, d_lst, d_sp, (const long long *)d_x, d_cand);
+        RSCHK(comm_allreduce_dev(ctx, 0, 3 * F, RSSEG_I64, RSSEG_SUM));
+        hipLaunchKernelGGL((kc_mean_apply<T>), dim3(1), dim3(KM_THREADS), 0, st, d.lst, d.sp, (const long long *)x, d.cand);
         HIPCHK(ctx, hipGetLastError());
+        return RSSEG_OK;
     }
-    if (info)
-        for (int f = 0; f < F; f++) {
-            info->scale[f] = (double)sp.scale[f];
-            info->min[f] = (double)sp.minv[f];
-        }
 
     // ---- k-means++ (_kmeans.py:213-270) ----
-    // fetch scaled+centred rows of global pixel indices; every rank ends up with all rows (empty-cluster relocation only)
-    auto fetch_rows = [&](const int64_t *gidx, int cnt, T rows[][RSSEG_MAX_FEATURES]) -> int {
-        double buf[KPP_MAXL * RSSEG_MAX_FEATURES];
-        memset(buf, 0, sizeof(buf));
-        for (int l = 0; l < cnt; l++) {
-            int64_t li = gidx[l] - offset;
-            if (li >= 0 && li < n) {
-                hipLaunchKernelGGL((km_gather_row<T>), dim3(1), dim3(64), 0, st, pl, F, li, d_sp, d_row);
-                HIPCHK(ctx, hipGetLastError());
-                HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d_row, sizeof(T) * F, hipMemcpyDeviceToHost, st));
-                HIPCHK(ctx, rs_sync(ctx));
-                for (int f = 0; f < F; f++) buf[l * F + f] = (double)((const T *)ctx->h_pin)[f];
-            }
-        }
-        RSCHK(comm_allreduce_host(ctx, buf, (int64_t)cnt * F, RSSEG_F64, RSSEG_SUM));
-        for (int l = 0; l < cnt; l++)
-            for (int f = 0; f < F; f++) rows[l][f] = (T)buf[l * F + f];
-        return RSSEG_OK;
-    };
-    // first sweep: the potential of the first centre per chunk (row 0) and the np.var numerators (rows 1..F)
-    if (n > 0) {
-        prof_scope ps(ctx, "kpp");
-        launch_kpp<T>(ctx, nchunks, pl, F, n, d_sp, d_cand, d_cc, 1, 0, d_closest, (unsigned long long *)d_part);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    {   // np.var(X, axis=0) and every rank's total of row 0 in ONE all-reduce: x = [F limb pairs][world limb pairs]
-        HIPCHK(ctx, hipMemsetAsync(d_x, 0, sizeof(long long) * (2 * (size_t)F + 2 * (size_t)ctx->world), st));
-        if (n > 0) {
-            hipLaunchKernelGGL(km_reduce_cols, dim3(F), dim3(KM_THREADS), 0, st, (const long long *)d_part + nchunks, nchunks, d_x, (const int *)nullptr, 1, 0);
-            hipLaunchKernelGGL(km_reduce_cols, dim3(1), dim3(KM_THREADS), 0, st, (const long long *)d_part, nchunks, d_x + 2 * F, (const int *)nullptr, 1, ctx->rank);
-        }
-        HIPCHK(ctx, hipGetLastError());
-        RSCHK(dev_allreduce(0, 2 * F + 2 * ctx->world, RSSEG_I64, RSSEG_SUM));
-        hipLaunchKernelGGL((kc_tol<T>), dim3(1), dim3(KM_THREADS), 0, st, d_lst, (const long long *)d_x);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    // exchange regions of a round inside x: the sampled rows at byte 0, the candidates' potentials behind them
-    constexpr size_t LIM_OFF = ((sizeof(double) * KPP_MAXL * (1 + RSSEG_MAX_FEATURES)) + 511) & ~(size_t)511;
-    double *d_xbuf = (double *)d_x;
-    long long *d_lim = (long long *)((char *)d_x + LIM_OFF);
-    for (int c = 1; c < k; c++) {
-        // centre c-1 is pending: its distances are folded into the closest plane by this round's sweep, and by
-        // km_kpp_chunkq for the chunks the samples fall into.  (The previous round's choice is made at the head of this kernel.)
-        hipLaunchKernelGGL((kc_targets<T>), dim3(1), dim3(KM_THREADS), 0, st, d_lst, c, c > 1 ? c - 1 : 0, (const unsigned long long *)d_part, d_cand, d_sa,
-                           d_xbuf, d_lim);
-        // xbuf[l] = {global pixel index, its F scaled+centred values}: filled by the rank that owns the pixel, zeros
-        // elsewhere, so ONE sum all-reduce hands every rank both the sampled indices and the candidate rows
-        if (n > 0) {
-            hipLaunchKernelGGL((km_kpp_chunkq<T>), dim3((unsigned)(CHUNK / KM_THREADS), L), dim3(KM_THREADS), 0, st, pl, F, d_sp, d_cand, d_cc,
-                               (const T *)d_closest, (const kpp_sample_args *)d_sa, d_qv);
-            hipLaunchKernelGGL((km_kpp_sample<T>), dim3(L), dim3(KM_THREADS), 0, st, pl, F, d_sp, (const unsigned long long *)d_qv, (const kpp_sample_args *)d_sa, d_xbuf);
-        }
-        HIPCHK(ctx, hipGetLastError());
-        RSCHK(dev_allreduce(0, (int64_t)L * (1 + RSSEG_MAX_FEATURES), RSSEG_F64, RSSEG_SUM));
-        hipLaunchKernelGGL((kc_cands<T>), dim3(1), dim3(KM_THREADS), 0, st, d_lst, (const double *)d_xbuf, d_cand);
+    int kpp_rounds()
+    {
+        // first sweep: the potential of the first centre per chunk (row 0) and the np.var numerators (rows 1..F)
         if (n > 0) {
             prof_scope ps(ctx, "kpp");
-            launch_kpp<T>(ctx, nchunks, pl, F, n, d_sp, d_cand, d_cc, L, c > 1 ? 2 : 1, d_closest, (unsigned long long *)d_part);
+            launch_kpp<T>(ctx, nchunks, pl, F, n, d.sp, d.cand, d.cc, 1, 0, d.closest, (unsigned long long *)d.part);
         }
         HIPCHK(ctx, hipGetLastError());
-        // potentials of all L candidates with ONE all-reduce: slot [l][rank] = this rank's chunk-sum total
-        if (n > 0) hipLaunchKernelGGL(km_reduce_cols, dim3(L), dim3(KM_THREADS), 0, st, (const long long *)d_part, nchunks, d_lim, (const int *)nullptr, ctx->world, ctx->rank);
-        RSCHK(dev_allreduce((int64_t)LIM_OFF, 2 * (int64_t)L * ctx->world, RSSEG_I64, RSSEG_SUM));
-    }
-    if (k > 1) {
-        hipLaunchKernelGGL((kc_pick<T>), dim3(1), dim3(KM_THREADS), 0, st, d_lst, k - 1, (const long long *)d_lim);
+        // np.var(X, axis=0) and every rank's total of row 0 in ONE all-reduce: x = [F limb pairs][world limb pairs]
+        HIPCHK(ctx, hipMemsetAsync(x, 0, sizeof(long long) * (2 * (size_t)F + 2 * (size_t)ctx->world), st));
+        if (n > 0) {
+            hipLaunchKernelGGL(km_reduce_cols, dim3(F), dim3(KM_THREADS), 0, st, (const long long *)d.part + nchunks, nchunks, x, (const int *)nullptr, 1, 0);
+            hipLaunchKernelGGL(km_reduce_cols, dim3(1), dim3(KM_THREADS), 0, st, (const long long *)d.part, nchunks, x + 2 * F, (const int *)nullptr, 1, ctx->rank);
+        }
         HIPCHK(ctx, hipGetLastError());
+        RSCHK(comm_allreduce_dev(ctx, 0, 2 * F + 2 * ctx->world, RSSEG_I64, RSSEG_SUM));
+        hipLaunchKernelGGL((kc_tol<T>), dim3(1), dim3(KM_THREADS), 0, st, d.lst, (const long long *)x);
+        HIPCHK(ctx, hipGetLastError());
+        double *xbuf = (double *)x;
+        long long *lim = (long long *)((char *)x + LIM_OFF);
+        for (int c = 1; c < k; c++) {
+            // centre c-1 is pending: its distances are folded into the closest plane by this round's sweep, and by
+            // km_kpp_chunkq for the chunks the samples fall into.  (The previous round's choice is made at the head of this kernel.)
+            hipLaunchKernelGGL((kc_targets<T>), dim3(1), dim3(KM_THREADS), 0, st, d.lst, c, c > 1 ? c - 1 : 0, (const unsigned long long *)d.part, d.cand, d.sa,
+                               xbuf, lim);
+            // xbuf[l] = {global pixel index, its F scaled+centred values}: filled by the rank that owns the pixel, zeros
+            // elsewhere, so ONE sum all-reduce hands every rank both the sampled indices and the candidate rows
+            if (n > 0) {
+                hipLaunchKernelGGL((km_kpp_chunkq<T>), dim3((unsigned)(CHUNK / KM_THREADS), L), dim3(KM_THREADS), 0, st, pl, F, d.sp, d.cand, d.cc,
+                                   (const T *)d.closest, (const kpp_sample_args *)d.sa, d.qv);
+                hipLaunchKernelGGL((km_kpp_sample<T>), dim3(L), dim3(KM_THREADS), 0, st, pl, F, d.sp, (const unsigned long long *)d.qv, (const kpp_sample_args *)d.sa, xbuf);
+            }
+            HIPCHK(ctx, hipGetLastError());
+            RSCHK(comm_allreduce_dev(ctx, 0, (int64_t)L * (1 + RSSEG_MAX_FEATURES), RSSEG_F64, RSSEG_SUM));
+            hipLaunchKernelGGL((kc_cands<T>), dim3(1), dim3(KM_THREADS), 0, st, d.lst, (const double *)xbuf, d.cand);
+            if (n > 0) {
+                prof_scope ps(ctx, "kpp");
+                launch_kpp<T>(ctx, nchunks, pl, F, n, d.sp, d.cand, d.cc, L, c > 1 ? 2 : 1, d.closest, (unsigned long long *)d.part);
+            }
+            HIPCHK(ctx, hipGetLastError());
+            // potentials of all L candidates with ONE all-reduce: slot [l][rank] = this rank's chunk-sum total
+            if (n > 0) hipLaunchKernelGGL(km_reduce_cols, dim3(L), dim3(KM_THREADS), 0, st, (const long long *)d.part, nchunks, lim, (const int *)nullptr, ctx->world, ctx->rank);
+            RSCHK(comm_allreduce_dev(ctx, (int64_t)LIM_OFF, 2 * (int64_t)L * ctx->world, RSSEG_I64, RSSEG_SUM));
+        }
+        if (k > 1) {
+            hipLaunchKernelGGL((kc_pick<T>), dim3(1), dim3(KM_THREADS), 0, st, d.lst, k - 1, (const long long *)lim);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        return RSSEG_OK;
     }
-    const double t_init = now_ms();
-    T tol = (T)0;   // known on the host only after the state has come back (empty-cluster path, info)
 
-    // ---- Lloyd (_kmeans_single_lloyd) ----
-    // accumulator copies: 32 when they fit in ~48 KB (3 workgroups per CU), fewer for large k * F
-    int ncopies = KM_COPIES;
-    while (ncopies > 1 && sizeof(long long) * (size_t)ncopies * km_copy_stride(KMAX, F) > 48 * 1024) ncopies >>= 1;
-    const size_t lds = sizeof(long long) * (size_t)ncopies * km_copy_stride(KMAX, F);
-    if (lds > 150 * 1024) return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "kmeans: F=%d, k=%d needs %zu B of LDS", F, k, lds);
-    // one E-step (+ per-cluster sums when `update`).  from_state: the centres come from the device state (kl_prepare builds
-    // their transposed copy and norms; `done`-guarded unless forced); otherwise from the host array C.
+    // One E-step (+ per-cluster sums when `update`).  from_state: the centres come from the device state (kl_prepare builds
+    // their transposed copy and norms before the first iteration, kl_update after each; `done`-guarded unless forced);
+    // otherwise from the host array C.
     // track: the sweep reads the previous labels of the uint8 working plane, counts the changes and writes the new ones.
     // The device-resident loop runs its update sweeps UNTRACKED (r04): "no label changed" only lets sklearn skip the final
     // E-step — with centres that are exact integer sums / counts, equal labels give bit-equal centres, so the shift is
@@ -2063,10 +2064,9 @@ int kmeans_fit(rsseg_ctx *ctx, const void *const *d_planes, int F, int64_t n, in
     // strictly converged case, and every update sweep loses its read-modify-write plane (62 -> 60 B/px and a read-only
     // stream: 2.9 -> 2.6 ms at 16384^2).  The host-side loop (empty clusters: relocation makes the centres depend on more
     // than the labels) keeps tracking.
-    auto run_lloyd = [&](bool update, bool from_state, bool force, int32_t *out32 = nullptr, bool track = true) -> int {
-        if (from_state) {
-            // d_cen already holds the transposed centres of the state: kl_prepare before the first iteration, kl_update after each
-        } else {
+    int lloyd_sweep(bool update, bool from_state, bool force, int32_t *out32 = nullptr, bool track = true)
+    {
+        if (!from_state) {
             // upload centres (transposed) and their squared norms (fma chain in T, row_norms of centres)
             T cenT[RSSEG_MAX_FEATURES * RSSEG_MAX_CLUSTERS + RSSEG_MAX_CLUSTERS];  // [MAX_FEATURES][KMAX] centres, then KMAX norms
             T *csq = cenT + (size_t)KMAX * RSSEG_MAX_FEATURES;
@@ -2080,35 +2080,173 @@ int kmeans_fit(rsseg_ctx *ctx, const void *const *d_planes, int F, int64_t n, in
                 csq[j] = a;
             }
             static_assert(sizeof(cenT) <= UP_SLOT, "upload slot too small");
-            HIPCHK(ctx, upload(d_cen, cenT, sizeof(T) * ((size_t)KMAX * RSSEG_MAX_FEATURES + KMAX)));
+            HIPCHK(ctx, upload(d.cen, cenT, sizeof(T) * ((size_t)KMAX * RSSEG_MAX_FEATURES + KMAX)));
         }
-        const int *dflag = (from_state && !force) ? &d_lst->done : nullptr;
-        if (n > 0) {
-            {
-                prof_scope ps(ctx, "lloyd");
-                const size_t l2 = update ? lds : 0;
-                uint8_t *lab_arg = (update && !track) ? nullptr : d_lab;
-                int lrc;
-                switch (KMAX) {
-                case 8: lrc = launch_lloyd<T, 8>(ctx, update, nchunks, l2, pl, F, k, n, d_sp, d_cen, d_csq, lab_arg, d_part, ncopies, dflag, out32); break;
-                case 16: lrc = launch_lloyd<T, 16>(ctx, update, nchunks, l2, pl, F, k, n, d_sp, d_cen, d_csq, lab_arg, d_part, ncopies, dflag, out32); break;
-                case 32: lrc = launch_lloyd<T, 32>(ctx, update, nchunks, l2, pl, F, k, n, d_sp, d_cen, d_csq, lab_arg, d_part, ncopies, dflag, out32); break;
-                default: lrc = launch_lloyd<T, 64>(ctx, update, nchunks, l2, pl, F, k, n, d_sp, d_cen, d_csq, lab_arg, d_part, ncopies, dflag, out32); break;
-                }
-                if (lrc != RSSEG_OK) return lrc;
+        if (n <= 0) return RSSEG_OK;
+        {
+            prof_scope ps(ctx, "lloyd");
+            RSCHK(launch_lloyd<T>(ctx, update, nchunks, update ? lds : 0, pl, F, k, KMAX, n, d.sp, d.cen, d.csq, (update && !track) ? nullptr : d.lab,
+                                  d.part, ncopies, (from_state && !force) ? &d.lst->done : nullptr, out32));
+        }
+        HIPCHK(ctx, hipGetLastError());
+        return RSSEG_OK;
+    }
+
+    // ---- device-resident Lloyd (_kmeans_single_lloyd): batches of speculatively enqueued iterations, one look at the state
+    // per batch.  Ends with the state on the host; host_mode: a cluster ran empty, the host loop takes over ----
+    int lloyd_device(bool &host_mode)
+    {
+        bool finished = false;
+        host_mode = false;
+        int batch = 4;
+        km_state<T> *h_state = (km_state<T> *)ctx->h_pin;
+        hipLaunchKernelGGL((kl_prepare<T>), dim3(1), dim3(KM_THREADS), 0, st, (const km_state<T> *)d.lst, k, F, KMAX, d.cen, 1);
+        HIPCHK(ctx, hipGetLastError());
+        while (!finished && !host_mode) {
+            const int todo = std::min(batch, max_iter - it);
+            for (int b = 0; b < todo; b++) {
+                RSCHK(lloyd_sweep(true, true, false, nullptr, false));
+                hipLaunchKernelGGL(km_reduce_cols, dim3(M), dim3(KM_THREADS), 0, st, (const long long *)d.part, nchunks, x, (const int *)&d.lst->done, 1, 0);
+                HIPCHK(ctx, hipGetLastError());
+                if (n <= 0) HIPCHK(ctx, hipMemsetAsync(x, 0, sizeof(long long) * 2 * M, st));   // a rank without pixels adds zeros
+                RSCHK(comm_allreduce_dev(ctx, 0, 2 * (int64_t)M, RSSEG_I64, RSSEG_SUM));
+                hipLaunchKernelGGL((kl_update<T>), dim3(1), dim3(KM_THREADS), 0, st, d.lst, k, F, KMAX, (const long long *)x, d.redsave, d.cen);
+                HIPCHK(ctx, hipGetLastError());
             }
-            HIPCHK(ctx, hipGetLastError());
+            // one look at the state (all of it: when the loop has ended, the centres, tolerance, means and seeds are here already)
+            HIPCHK(ctx, hipMemcpyAsync(h_state, d.lst, sizeof(km_state<T>), hipMemcpyDeviceToHost, st));
+            HIPCHK(ctx, rs_sync(ctx));
+            const int it_new = h_state->it, done = h_state->done;
+            prof_retag(ctx, "lloyd", todo - (it_new - it) - (done == 3 ? 1 : 0), "lloyd_noop");   // launches that returned at once
+            it = it_new;
+            if (done == 1 || done == 2 || done == 4) {
+                strict = done == 1;
+                finished = true;
+            } else if (done == 3) {
+                host_mode = true;
+            } else if (it >= max_iter) {
+                finished = true;
+            }
+            batch = std::max(2, it / 3);   // short fits are not over-enqueued, long ones are looked at ever more rarely
+        }
+        // the state the device loop ended with: centres, tolerance, means, seeds (the host reports them, or continues from them)
+        if (host_mode) {
+            HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin + sizeof(km_state<T>), d.redsave, sizeof(long long) * 2 * M, hipMemcpyDeviceToHost, st));
+            HIPCHK(ctx, rs_sync(ctx));   // lloyd_host picks them up
+        }
+        memcpy(C, h_state->C, sizeof(C));
+        tol = h_state->tol;
+        for (int f = 0; f < F; f++) sp.mean[f] = h_state->mean[f];
+        for (int j = 0; j < k; j++) init_idx[j] = h_state->init_idx[j];
+        return RSSEG_OK;
+    }
+
+    // ---- host-side Lloyd, from the iteration in which a cluster ran empty: its E-step and its (all-reduced) sums exist, the
+    // centres the kernels used (d.cen) are still those of that E-step — finish it here, then iterate on the host.  The
+    // untracked sweeps wrote no labels: the relocation (distance to the ASSIGNED centre) and the tracked iterations that
+    // follow need them, so that E-step is repeated once, labels only.  (Its change count is known to be non-zero: a cluster
+    // that holds pixels in one iteration and none in the next has lost them.) ----
+    int lloyd_host()
+    {
+        std::vector<long long> red((size_t)2 * M);   // the reduced sums of the iteration being finished
+        memcpy(red.data(), ctx->h_pin + sizeof(km_state<T>), sizeof(long long) * 2 * M);   // lloyd_device read them back
+        RSCHK(lloyd_sweep(false, true, true));
+        bool end;
+        RSCHK(host_iteration(red, end));
+        while (!end) {
+            RSCHK(lloyd_sweep(true, false, true));
+            if (n > 0) {
+                hipLaunchKernelGGL(km_reduce_cols, dim3(M), dim3(KM_THREADS), 0, st, (const long long *)d.part, nchunks, d.red, (const int *)nullptr, 1, 0);
+                HIPCHK(ctx, hipGetLastError());
+                HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d.red, sizeof(long long) * 2 * M, hipMemcpyDeviceToHost, st));
+                HIPCHK(ctx, rs_sync(ctx));
+                memcpy(red.data(), ctx->h_pin, sizeof(long long) * 2 * M);
+            } else {
+                std::fill(red.begin(), red.end(), 0ll);
+            }
+            RSCHK(comm_allreduce_host(ctx, red.data(), 2 * M, RSSEG_I64, RSSEG_SUM));
+            RSCHK(host_iteration(red, end));
         }
         return RSSEG_OK;
-    };
+    }
 
-    bool strict = false;
-    int it = 0, relocated = 0;
-    std::vector<long long> red((size_t)2 * M);
+    // scaled+centred row of global pixel `gidx` on every rank (empty-cluster relocation)
+    int fetch_row(int64_t gidx, T row[RSSEG_MAX_FEATURES])
+    {
+        double buf[RSSEG_MAX_FEATURES];
+        memset(buf, 0, sizeof(buf));
+        const int64_t li = gidx - offset;
+        if (li >= 0 && li < n) {
+            hipLaunchKernelGGL((km_gather_row<T>), dim3(1), dim3(64), 0, st, pl, F, li, d.sp, d.row);
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d.row, sizeof(T) * F, hipMemcpyDeviceToHost, st));
+            HIPCHK(ctx, rs_sync(ctx));
+            for (int f = 0; f < F; f++) buf[f] = (double)((const T *)ctx->h_pin)[f];
+        }
+        RSCHK(comm_allreduce_host(ctx, buf, F, RSSEG_F64, RSSEG_SUM));
+        for (int f = 0; f < F; f++) row[f] = (T)buf[f];
+        return RSSEG_OK;
+    }
 
-    // What _kmeans_single_lloyd does between two E-steps, on the host: used from the iteration in which a cluster ran
-    // empty (the device loop hands over with that iteration's reduced sums in `red`).  Returns 1 when the loop ends.
-    auto host_finish_iteration = [&]() -> int {
+    // _relocate_empty_clusters_dense: the e-th empty cluster takes the e-th farthest pixel (S: exact per-cluster sums)
+    int relocate(int64_t *cnt, int n_empty, std::vector<i128> &Sv)
+    {
+        auto S = [&](int j, int f) -> i128 & { return Sv[(size_t)j * RSSEG_MAX_FEATURES + f]; };
+        taken_t tk;
+        tk.n = 0;
+        T dmax_all = (T)0;
+        int e = 0;
+        for (int j = 0; j < k && e < n_empty; j++) {
+            if (cnt[j] != 0) continue;
+            double best[2] = {-1.0, 0.0};
+            long long bidx = 0x7fffffffffffffffLL;
+            if (n > 0) {
+                T *pd = (T *)d.part;
+                long long *pi = d.part + nchunks;  // after the distances (sizeof(T) <= 8)
+                launch_farthest<T>(ctx, KMAX, nchunks, pl, F, n, offset, d.sp, d.cen, d.lab, tk, pd, pi);
+                HIPCHK(ctx, hipGetLastError());
+                HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d.part, sizeof(long long) * 2 * (size_t)nchunks, hipMemcpyDeviceToHost, st));
+                HIPCHK(ctx, rs_sync(ctx));
+                const T *hd = (const T *)ctx->h_pin;
+                const long long *hi = (const long long *)ctx->h_pin + nchunks;
+                for (int64_t c2 = 0; c2 < nchunks; c2++)
+                    if ((double)hd[c2] > best[0] || ((double)hd[c2] == best[0] && hi[c2] < bidx)) { best[0] = (double)hd[c2]; bidx = hi[c2]; }
+            }
+            double gmax = best[0];
+            RSCHK(comm_allreduce_host(ctx, &gmax, 1, RSSEG_F64, RSSEG_MAX));
+            double gidx = (best[0] == gmax && bidx != 0x7fffffffffffffffLL) ? (double)bidx : 9.0e18;
+            RSCHK(comm_allreduce_host(ctx, &gidx, 1, RSSEG_F64, RSSEG_MIN));
+            if (e == 0) dmax_all = (T)gmax;
+            if (dmax_all == (T)0 || gidx >= 9.0e18) break;  // np.max(distances) == 0: relocation is pointless
+            const int64_t far = (int64_t)gidx;
+            tk.idx[tk.n++] = far;
+            T row[RSSEG_MAX_FEATURES];
+            RSCHK(fetch_row(far, row));
+            double oldlab = 0.0;
+            if (far >= offset && far < offset + n) {
+                HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d.lab + (far - offset), 1, hipMemcpyDeviceToHost, st));
+                HIPCHK(ctx, rs_sync(ctx));
+                oldlab = (double)((const uint8_t *)ctx->h_pin)[0];
+            }
+            RSCHK(comm_allreduce_host(ctx, &oldlab, 1, RSSEG_F64, RSSEG_SUM));
+            const int oj = (int)oldlab;
+            for (int f = 0; f < F; f++) {
+                const i128 q = (i128)llrint((double)row[f] * 1099511627776.0);
+                S(oj, f) -= q;
+                S(j, f) = q;
+            }
+            cnt[j] = 1;
+            cnt[oj] -= 1;
+            relocated++;
+            e++;
+        }
+        return RSSEG_OK;
+    }
+
+    // What _kmeans_single_lloyd does between two E-steps, from the reduced sums `red`: relocation, _average_centers, the
+    // centre shift and the stopping rules.  end: the loop is over.
+    int host_iteration(const std::vector<long long> &red, bool &end)
+    {
         int64_t cnt[RSSEG_MAX_CLUSTERS];
         int n_empty = 0;
         for (int j = 0; j < k; j++) {
@@ -2121,62 +2259,7 @@ int kmeans_fit(rsseg_ctx *ctx, const void *const *d_planes, int F, int64_t n, in
         auto S = [&](int j, int f) -> i128 & { return Sv[(size_t)j * RSSEG_MAX_FEATURES + f]; };
         for (int j = 0; j < k; j++)
             for (int f = 0; f < F; f++) S(j, f) = limbs(red[2 * (j * F + f)], red[2 * (j * F + f) + 1]);
-        if (n_empty > 0) {
-            // _relocate_empty_clusters_dense: the e-th empty cluster takes the e-th farthest pixel
-            taken_t tk;
-            tk.n = 0;
-            T dmax_all = (T)0;
-            int e = 0;
-            for (int j = 0; j < k && e < n_empty; j++) {
-                if (cnt[j] != 0) continue;
-                double best[2] = {-1.0, 0.0};
-                long long bidx = 0x7fffffffffffffffLL;
-                if (n > 0) {
-                    T *pd = (T *)d_part;
-                    long long *pi = d_part + nchunks;  // after the distances (sizeof(T) <= 8)
-                    switch (KMAX) {
-                    case 8: launch_farthest<T, 8>(ctx, nchunks, pl, F, n, offset, d_sp, d_cen, d_lab, tk, pd, pi); break;
-                    case 16: launch_farthest<T, 16>(ctx, nchunks, pl, F, n, offset, d_sp, d_cen, d_lab, tk, pd, pi); break;
-                    case 32: launch_farthest<T, 32>(ctx, nchunks, pl, F, n, offset, d_sp, d_cen, d_lab, tk, pd, pi); break;
-                    default: launch_farthest<T, 64>(ctx, nchunks, pl, F, n, offset, d_sp, d_cen, d_lab, tk, pd, pi); break;
-                    }
-                    HIPCHK(ctx, hipGetLastError());
-                    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d_part, sizeof(long long) * 2 * (size_t)nchunks, hipMemcpyDeviceToHost, st));
-                    HIPCHK(ctx, rs_sync(ctx));
-                    const T *hd = (const T *)ctx->h_pin;
-                    const long long *hi = (const long long *)ctx->h_pin + nchunks;
-                    for (int64_t c2 = 0; c2 < nchunks; c2++)
-                        if ((double)hd[c2] > best[0] || ((double)hd[c2] == best[0] && hi[c2] < bidx)) { best[0] = (double)hd[c2]; bidx = hi[c2]; }
-                }
-                double gmax = best[0];
-                RSCHK(comm_allreduce_host(ctx, &gmax, 1, RSSEG_F64, RSSEG_MAX));
-                double gidx = (best[0] == gmax && bidx != 0x7fffffffffffffffLL) ? (double)bidx : 9.0e18;
-                RSCHK(comm_allreduce_host(ctx, &gidx, 1, RSSEG_F64, RSSEG_MIN));
-                if (e == 0) dmax_all = (T)gmax;
-                if (dmax_all == (T)0 || gidx >= 9.0e18) break;  // np.max(distances) == 0: relocation is pointless
-                const int64_t far = (int64_t)gidx;
-                tk.idx[tk.n++] = far;
-                T rows[KPP_MAXL][RSSEG_MAX_FEATURES];
-                RSCHK(fetch_rows(&far, 1, rows));
-                double oldlab = 0.0;
-                if (far >= offset && far < offset + n) {
-                    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d_lab + (far - offset), 1, hipMemcpyDeviceToHost, st));
-                    HIPCHK(ctx, rs_sync(ctx));
-                    oldlab = (double)((const uint8_t *)ctx->h_pin)[0];
-                }
-                RSCHK(comm_allreduce_host(ctx, &oldlab, 1, RSSEG_F64, RSSEG_SUM));
-                const int oj = (int)oldlab;
-                for (int f = 0; f < F; f++) {
-                    const i128 q = (i128)llrint((double)rows[0][f] * 1099511627776.0);
-                    S(oj, f) -= q;
-                    S(j, f) = q;
-                }
-                cnt[j] = 1;
-                cnt[oj] -= 1;
-                relocated++;
-                e++;
-            }
-        }
+        if (n_empty > 0) RSCHK(relocate(cnt, n_empty, Sv));
         // _average_centers
         T Cnew[RSSEG_MAX_CLUSTERS][RSSEG_MAX_FEATURES];
         int argmax_w = 0;
@@ -2211,8 +2294,8 @@ int kmeans_fit(rsseg_ctx *ctx, const void *const *d_planes, int F, int64_t n, in
                 b += 4;
             }
             for (int r = 0; r < rem; r++) {
-                volatile T d = a[r] - b[r];
-                volatile T t = d * d;
+                volatile T dd = a[r] - b[r];
+                volatile T t = dd * dd;
                 result = result + t;
             }
             volatile T sh = std::sqrt((T)result);
@@ -2223,121 +2306,69 @@ int kmeans_fit(rsseg_ctx *ctx, const void *const *d_planes, int F, int64_t n, in
         it++;
         if (changed == 0) {
             strict = true;
-            return 1;
+            end = true;
+        } else {
+            end = np_pairwise_sum<T>(shift2, k) <= tol || it >= max_iter;
         }
-        const T tot = np_pairwise_sum<T>(shift2, k);
-        if (tot <= tol) return 1;
-        return it >= max_iter ? 1 : 0;
-    };
+        return RSSEG_OK;
+    }
 
-    // ---- device-resident loop: batches of speculatively enqueued iterations, one look at the state per batch ----
-    long long *d_sums = ctx->comm_on ? (long long *)ctx->d_comm : d_red;   // where km_reduce_cols leaves the limb sums
-    if (ctx->comm_on && sizeof(long long) * 2 * (size_t)M > ctx->comm_bytes) return rs_fail(ctx, RSSEG_ERR_COMM, "kmeans: comm buffer too small");
-    bool finished = false, host_mode = false;
-    int batch = 4;
-    km_state<T> *h_state = (km_state<T> *)ctx->h_pin;
-    hipLaunchKernelGGL((kl_prepare<T>), dim3(1), dim3(KM_THREADS), 0, st, (const lloyd_state<T> *)d_lst, k, F, KMAX, d_cen, 1);
-    HIPCHK(ctx, hipGetLastError());
-    while (!finished && !host_mode) {
-        const int todo = std::min(batch, max_iter - it);
-        for (int b = 0; b < todo; b++) {
-            RSCHK(run_lloyd(true, true, false, nullptr, false));
-            hipLaunchKernelGGL(km_reduce_cols, dim3(M), dim3(KM_THREADS), 0, st, (const long long *)d_part, nchunks, d_sums, (const int *)&d_lst->done, 1, 0);
-            HIPCHK(ctx, hipGetLastError());
-            if (ctx->comm_on) {   // stream-ordered: no staging copy, no host synchronisation (include/rsseg.h, rsseg_allreduce_fn)
-                const auto t0c = std::chrono::steady_clock::now();
-                if (n <= 0) HIPCHK(ctx, hipMemsetAsync(d_sums, 0, sizeof(long long) * 2 * M, st));
-                const int rc = ctx->allreduce(ctx->comm_user, 0, 2 * (int64_t)M, RSSEG_I64, RSSEG_SUM);
-                if (rc != 0) return rs_fail(ctx, RSSEG_ERR_COMM, "all-reduce hook returned %d", rc);
-                if (ctx->prof_on) {
-                    prof_entry &e = ctx->prof["allreduce"];
-                    e.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0c).count();
-                    e.launches++;
-                }
-            }
-            hipLaunchKernelGGL((kl_update<T>), dim3(1), dim3(KM_THREADS), 0, st, d_lst, k, F, KMAX, (const long long *)d_sums, d_redsave, d_cen);
+    // ---- the final E-step: labels of the final centres, skipped when the last iteration changed no label.  Its kernel writes
+    // the caller's int32 plane itself when it can (lloyd_writes_int32, 16-byte aligned plane); otherwise the uint8 plane is widened ----
+    int final_labels(int32_t *d_labels)
+    {
+        const bool direct = !strict && n > 0 && ((uintptr_t)d_labels & 15) == 0 && lloyd_writes_int32<T>(KMAX, F);
+        if (!strict) RSCHK(lloyd_sweep(false, false, true, direct ? d_labels : nullptr));
+        if (n > 0 && !direct) {
+            prof_scope ps(ctx, "labels");
+            hipLaunchKernelGGL(km_labels_out, dim3((unsigned)std::min<int64_t>(4096, ceil_div64(n, KM_THREADS))), dim3(KM_THREADS), 0, st,
+                               d.lab, d_labels, n);
             HIPCHK(ctx, hipGetLastError());
         }
-        // one look at the state (all of it: when the loop has ended, the centres, tolerance, means and seeds are here already)
-        HIPCHK(ctx, hipMemcpyAsync(h_state, d_lst, sizeof(km_state<T>), hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, rs_sync(ctx));
-        const int it_new = h_state->it, done = h_state->done;
-        prof_retag(ctx, "lloyd", todo - (it_new - it) - (done == 3 ? 1 : 0), "lloyd_noop");   // launches that returned at once
-        it = it_new;
-        if (done == 1 || done == 2 || done == 4) {
-            strict = done == 1;
-            finished = true;
-        } else if (done == 3) {
-            host_mode = true;
-        } else if (it >= max_iter) {
-            finished = true;
-        }
-        batch = std::max(2, it / 3);   // short fits are not over-enqueued, long ones are looked at ever more rarely
+        return RSSEG_OK;
     }
-    {   // the state the device loop ended with: centres, tolerance, means, seeds (the host reports them, or continues from them)
-        if (host_mode) {
-            HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin + sizeof(km_state<T>), d_redsave, sizeof(long long) * 2 * M, hipMemcpyDeviceToHost, st));
-            HIPCHK(ctx, rs_sync(ctx));
+
+    void report(double *centers_out, rsseg_kmeans_info *info, double t_start, double t_init)
+    {
+        if (centers_out)
+            for (int j = 0; j < k; j++)
+                for (int f = 0; f < F; f++) {
+                    volatile T v = C[j][f] + sp.mean[f];  // best_centers += X_mean
+                    centers_out[j * F + f] = (double)v;
+                }
+        if (!info) return;
+        for (int f = 0; f < F; f++) {
+            info->scale[f] = (double)sp.scale[f];
+            info->min[f] = (double)sp.minv[f];
+            info->mean[f] = (double)sp.mean[f];
         }
-        memcpy(C, h_state->C, sizeof(C));
-        tol = h_state->tol;
-        for (int f = 0; f < F; f++) sp.mean[f] = h_state->mean[f];
-        for (int j = 0; j < k; j++) init_idx[j] = h_state->init_idx[j];
-        if (host_mode) memcpy(red.data(), ctx->h_pin + sizeof(km_state<T>), sizeof(long long) * 2 * M);
-        if (info) {
-            info->tol = (double)tol;
-            for (int f = 0; f < F; f++) info->mean[f] = (double)sp.mean[f];
-            for (int j = 0; j < k; j++) info->init_indices[j] = init_idx[j];
-        }
-    }
-    if (host_mode) {
-        // the iteration in which a cluster ran empty: its E-step and its (all-reduced) sums exist, the centres the kernels
-        // used (d_cen) are still those of that E-step — finish it here, then iterate on the host.  The untracked sweeps wrote
-        // no labels: the relocation (distance to the ASSIGNED centre) and the tracked iterations that follow need them, so
-        // that E-step is repeated once, labels only.  (Its change count is known to be non-zero: a cluster that holds
-        // pixels in one iteration and none in the next has lost them.)
-        RSCHK(run_lloyd(false, true, true));
-        int end = host_finish_iteration();
-        if (end < 0) return end;
-        while (!end) {
-            RSCHK(run_lloyd(true, false, true));
-            if (n > 0) {
-                hipLaunchKernelGGL(km_reduce_cols, dim3(M), dim3(KM_THREADS), 0, st, (const long long *)d_part, nchunks, d_red, (const int *)nullptr, 1, 0);
-                HIPCHK(ctx, hipGetLastError());
-                HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d_red, sizeof(long long) * 2 * M, hipMemcpyDeviceToHost, st));
-                HIPCHK(ctx, rs_sync(ctx));
-                        memcpy(red.data(), ctx->h_pin, sizeof(long long) * 2 * M);
-            } else {
-                std::fill(red.begin(), red.end(), 0ll);
-            }
-            RSCHK(comm_allreduce_host(ctx, red.data(), 2 * M, RSSEG_I64, RSSEG_SUM));
-            end = host_finish_iteration();
-            if (end < 0) return end;
-        }
-    }
-    // the final E-step (labels of the final centres; skipped when the last iteration changed no label) writes the caller's
-    // int32 plane itself when its kernel can (F <= 32, 16-byte aligned plane); otherwise the uint8 plane is widened
-    const bool direct = !strict && n > 0 && ((uintptr_t)d_labels & 15) == 0 && (F <= 8 || (F <= 32 && !(std::is_same<T, double>::value && KMAX == 64)));
-    if (!strict) RSCHK(run_lloyd(false, false, true, direct ? d_labels : nullptr));
-    if (n > 0 && !direct) {
-        prof_scope ps(ctx, "labels");
-        hipLaunchKernelGGL(km_labels_out, dim3((unsigned)std::min<int64_t>(4096, ceil_div64(n, KM_THREADS))), dim3(KM_THREADS), 0, st,
-                           d_lab, d_labels, n);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    HIPCHK(ctx, rs_sync(ctx));
-    if (centers_out)
-        for (int j = 0; j < k; j++)
-            for (int f = 0; f < F; f++) {
-                volatile T v = C[j][f] + sp.mean[f];  // best_centers += X_mean
-                centers_out[j * F + f] = (double)v;
-            }
-    if (info) {
+        for (int j = 0; j < k; j++) info->init_indices[j] = init_idx[j];
+        info->tol = (double)tol;
         info->n_iter = it;
         info->relocated = relocated;
         info->ms_init = t_init - t_start;
         info->ms_lloyd = now_ms() - t_init;
     }
+};
+
+template <typename T>
+int kmeans_fit(rsseg_ctx *ctx, const void *const *d_planes, int F, int64_t n, int k, uint32_t seed, int max_iter, double tol_in,
+               int32_t *d_labels, double *centers_out, rsseg_kmeans_info *info, const double *known_min, const double *known_max)
+{
+    const double t_start = now_ms();
+    km_fit<T> fit;
+    RSCHK(fit.setup(ctx, F, n, k, max_iter));
+    RSCHK(fit.layout(d_planes));
+    RSCHK(fit.scale_and_ranks(known_min, known_max));
+    RSCHK(fit.means_and_first_seed(seed, tol_in));
+    RSCHK(fit.kpp_rounds());
+    const double t_init = now_ms();
+    bool host_mode;
+    RSCHK(fit.lloyd_device(host_mode));
+    if (host_mode) RSCHK(fit.lloyd_host());
+    RSCHK(fit.final_labels(d_labels));
+    fit.report(centers_out, info, t_start, t_init);
     return RSSEG_OK;
 }
 

@@ -1528,3 +1528,68 @@ def test_full_size_depth16_forest_vs_sklearn(ctx):
     assert len(np.unique(want)) >= 6   # a real multi-class map, not one label
     del planes, fp, bands, got
     torch.cuda.empty_cache()
+
+
+# The stream schedule of three fixed fits: host synchronisations per fit and launches per profiling family (bench.py reads
+# these families).  With the one-rank all-reduce hook installed the stream-ordered collectives run too.  Recorded on the
+# MI355X at commit f2d07fa, before the k-means host driver was split into phases; a change here is a change of schedule.
+KMEANS_SCHEDULE_FAMILIES = ("moment", "kpp", "lloyd", "lloyd_noop", "labels", "allreduce")
+
+
+def _kmeans_schedule_fit(name):
+    if name == "config3_f32":      # 15 float32 planes, k = 8 (the bench's KMeans shape)
+        rng = np.random.default_rng(3)
+        n, F, k, dt = 300_000, 15, 8, np.float32
+        cent = rng.random((k + 3, F))
+        X = (cent[rng.integers(0, k + 3, n)] + rng.normal(0, 0.08, (n, F))).astype(dt)
+    elif name == "relocation":     # the data of test_kmeans_empty_cluster_relocation[20]
+        rng = np.random.default_rng(20)
+        n = int(rng.integers(20, 120)); F = int(rng.integers(1, 4)); k = int(rng.integers(6, 14))
+        X = rng.random((n, F)).astype(np.float32)
+        X = (np.round(X * rng.integers(2, 6)) / 4.0).astype(np.float32)
+    else:                          # "blocked_f64": float64, F > 32 -> the feature-blocked kernels
+        rng = np.random.default_rng(20 * 100 + 40)
+        n, F, k = 20011, 40, 20
+        cent = rng.random((k + 3, F))
+        X = (cent[rng.integers(0, k + 3, n)] + rng.normal(0, 0.08, (n, F))).astype(np.float64)
+    return [np.ascontiguousarray(X[:, f]) for f in range(F)], k
+
+
+def kmeans_schedule(name, hooked):
+    """{host_syncs, launches per family, n_iter, relocated} of the second of two identical fits on a fresh context."""
+    from rsseg.runtime import Context
+    planes, k = _kmeans_schedule_fit(name)
+    c = Context(0, use_dist=False)
+    try:
+        if hooked:
+            c.install_comm_hook(0, 1, lambda buf, offset, count, dtype, op: None)   # one rank: the identity
+        d = [c.to_device(p) for p in planes]
+        c.kmeans_fit_predict(d, k)   # sizes the workspace and the pinned buffers (their first reservation synchronises)
+        c.sync()
+        c.prof_enable(True)
+        c.prof_reset()
+        c.host_syncs(reset=True)
+        _, meta = c.kmeans_fit_predict(d, k)
+        out = {"host_syncs": c.host_syncs()}
+        out.update({f: c.prof_get(f)[1] for f in KMEANS_SCHEDULE_FAMILIES})
+        out.update(n_iter=meta["n_iter"], relocated=meta["relocated"])
+        c.prof_enable(False)
+        return out
+    finally:
+        c.close()
+
+
+KMEANS_SCHEDULE = {
+    ("config3_f32", False): {"host_syncs": 3, "moment": 1, "kpp": 8, "lloyd": 4, "lloyd_noop": 1, "labels": 0, "allreduce": 0, "n_iter": 3, "relocated": 0},
+    ("config3_f32", True): {"host_syncs": 4, "moment": 1, "kpp": 8, "lloyd": 4, "lloyd_noop": 1, "labels": 0, "allreduce": 21, "n_iter": 3, "relocated": 0},
+    ("relocation", False): {"host_syncs": 18, "moment": 1, "kpp": 8, "lloyd": 3, "lloyd_noop": 3, "labels": 1, "allreduce": 0, "n_iter": 2, "relocated": 4},
+    ("relocation", True): {"host_syncs": 38, "moment": 1, "kpp": 8, "lloyd": 3, "lloyd_noop": 3, "labels": 1, "allreduce": 40, "n_iter": 2, "relocated": 4},
+    ("blocked_f64", False): {"host_syncs": 3, "moment": 1, "kpp": 20, "lloyd": 4, "lloyd_noop": 1, "labels": 1, "allreduce": 0, "n_iter": 3, "relocated": 0},
+    ("blocked_f64", True): {"host_syncs": 4, "moment": 1, "kpp": 20, "lloyd": 4, "lloyd_noop": 1, "labels": 1, "allreduce": 45, "n_iter": 3, "relocated": 0},
+}
+
+
+@pytest.mark.parametrize("hooked", [False, True])
+@pytest.mark.parametrize("name", ["config3_f32", "relocation", "blocked_f64"])
+def test_kmeans_stream_schedule_is_pinned(name, hooked):
+    assert kmeans_schedule(name, hooked) == KMEANS_SCHEDULE[(name, hooked)]
