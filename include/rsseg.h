@@ -220,9 +220,19 @@ int rsseg_indices_pca_u8(rsseg_ctx *ctx, const uint8_t *const *d_bands, int nb, 
  * ((band*(levels-1)).astype(uint8), :268), H x W.  Writes the five property maps
  * (contrast, dissimilarity, homogeneity, energy, correlation), each ((H-win)/step+1) x
  * ((W-win)/step+1) float32, mean over the 4 angles (0, 45, 90, 135 degrees, distance 1),
- * symmetric + normalised co-occurrence. Any of d_props[i] may be NULL. */
+ * symmetric + normalised co-occurrence. Any of d_props[i] may be NULL.  levels 2..256 (65..256: win <= 255);
+ * RSSEG_ERR_UNSUPPORTED for levels > 256. */
 int rsseg_glcm_u8(rsseg_ctx *ctx, const uint8_t *d_q, int H, int W, int levels, int win, int step,
                   float *const *d_props);
+/* The same for any list of graycomatrix (distance, angle) entries (indices.py:288-290): offsets holds n pairs (dr, dc) in
+ * entry order (distance-major, angle-minor), dr = round(sin(angle) * distance), dc = round(cos(angle) * distance)
+ * (rsseg/pipeline.py::glcm_offset_plan).  Pixel (r, c) pairs with (r + dr, c + dc) inside the window; an offset that
+ * leaves the window gives the empty matrix, whose properties are (0, 0, 0, 0, 1).  Each map is the float32 of the plain
+ * mean over the n entries; each entry's properties come from exact integer statistics in float64 (k4_glcm_offsets.hip).
+ * The default list (0,1), (1,1), (1,0), (1,-1) is rsseg_glcm_u8 itself, bit for bit.  RSSEG_ERR_UNSUPPORTED: levels > 256;
+ * a non-default list with win > 255; more than 512 entries or 64 distinct offsets (o and -o are one offset). */
+int rsseg_glcm_offsets_u8(rsseg_ctx *ctx, const uint8_t *d_q, int H, int W, int levels, int win, int step,
+                          const int32_t *offsets, int n, float *const *d_props);
 /* float32 plane in [0,1] -> uint8 by truncation of x*mult (indices.py:268, 415, 458). */
 int rsseg_quantize_u8(rsseg_ctx *ctx, const float *d_x, int64_t n, float mult, uint8_t *d_q);
 /* robust_normalize(x) with the given percentiles, then the truncation of rsseg_quantize_u8, in one pass (the texture

@@ -27,66 +27,13 @@
 #include <mutex>
 
 #include "common.h"
+#include "k4_glcm.h"
 
 __constant__ long long c_glcm_hq[256];
 __device__ long long g_glcm_hq2[1024];  // pair sums hq[dA] + hq[dB] at [dB * 32 + dA] (levels <= 32)
 
 static const int H_DR[4] = {0, 1, 1, 1};
 static const int H_DC[4] = {1, 1, 0, -1};
-
-struct glcm_out {
-    float *p[5];  // contrast, dissimilarity, homogeneity, energy, correlation
-};
-
-struct glcm_stats {
-    long long np, S1, S2, Hq, M1, M2, Mx, A;
-};
-
-// correlation of one angle from exact integers (oracle.c mode 1)
-__device__ __forceinline__ double glcm_corr(long long np, long long M1, long long M2, long long Mx)
-{
-    const long long den = M2 * (2 * np) - M1 * M1, num = Mx * (2 * np) - M1 * M1;
-    return den == 0 ? 1.0 : (double)num / (double)den;
-}
-
-// group sums: g0 = angles 0 and 90 degrees (na pairs each), g1 = 45 and 135 degrees (nb pairs each)
-struct glcm_group {
-    long long S1, S2, Hq;
-    double sq;  // sqrt(A_a) + sqrt(A_b)
-};
-
-// RN(a / b) for a divisor known on the host: with y = RN(1/b), q = RN(a*y) is a faithful quotient, the fma residual
-// r = a - q*b is exact and RN(q + r*y) is the correctly rounded quotient (Markstein) - three instructions instead of
-// the ~12-instruction IEEE sequence.  The host checks the precondition (significand of b not all ones).
-__device__ __forceinline__ double div_const(double a, double b, double y)
-{
-    const double q = a * y;
-    const double r = fma(-q, b, a);
-    return fma(r, y, q);
-}
-
-struct glcm_consts {
-    double den4, den8, rden4, rden8;  // 4*na*nb, 8*na*nb and their correctly rounded reciprocals
-};
-
-__device__ __forceinline__ void glcm_finish(const glcm_group &g0, const glcm_group &g1, long long na, long long nb, double r0,
-                                            double r1, double r2, double r3, size_t o, const glcm_out &out, const glcm_consts &gc)
-{
-    const double dna = (double)na, dnb = (double)nb;
-    if (out.p[0]) out.p[0][o] = (float)div_const((double)(g0.S2 * nb + g1.S2 * na), gc.den4, gc.rden4);
-    if (out.p[1]) out.p[1][o] = (float)div_const((double)(g0.S1 * nb + g1.S1 * na), gc.den4, gc.rden4);
-    if (out.p[2]) {
-        const double t1 = (double)g1.Hq * dna;
-        const double num = fma((double)g0.Hq, dnb, t1);
-        out.p[2][o] = (float)(div_const(num, gc.den4, gc.rden4) * (1.0 / 4503599627370496.0));
-    }
-    if (out.p[3]) {
-        const double t1 = g1.sq * dna;
-        const double num = fma(g0.sq, dnb, t1);
-        out.p[3][o] = (float)div_const(num, gc.den8, gc.rden8);
-    }
-    if (out.p[4]) out.p[4][o] = (float)((((r0 + r1) + r2) + r3) * 0.25);
-}
 
 // ---- compile-time machinery: every register array below is indexed by constants only ----------
 template <typename F, int... I> __device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>)
@@ -1103,6 +1050,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 // 2 KB LDS tables of packed 16-bit counters (a window has fewer than 65536 pairs); no workgroup barrier anywhere — a wave's
 // LDS operations execute in order, so its own atomics are complete before its reads.  This is the reference's default
 // geometry (window 21, step 21: indices.py:248) — k4_glcm_wg spent most of its 21 us per window in 20 barriers.
+// SPLIT: windows above 45 (2048 pairs or more per angle), whose per-angle int64 homogeneity sum would overflow: the lanes'
+// partials are reduced split (k4_glcm.h).  Below, the per-angle sums are exact in int64 and only the two-angle group sums
+// (which overflow from window 33 on) are formed exactly, on lane 0.
+template <bool SPLIT>
 __global__ __launch_bounds__(256) void k4_glcm_wave(const uint8_t *__restrict__ q, int H, int W, int levels, int win, int step, int oh,
                                                     int ow, glcm_out out, glcm_consts gc)
 {
@@ -1116,6 +1067,7 @@ __global__ __launch_bounds__(256) void k4_glcm_wave(const uint8_t *__restrict__ 
 #pragma unroll
     for (int t = 0; t < 8; t++) reinterpret_cast<uint4 *>(hist)[t * 64 + lane] = make_uint4(0, 0, 0, 0);
     long long sums[4][6];  // per angle: S1 S2 Hq M1 M2 Mx (this lane's share)
+    glcm_hq_sum hqs[4];    // SPLIT: per angle Hq split (k4_glcm.h), reduced exactly however large the window
     for (int a = 0; a < 4; a++) {
         const int dr = a == 0 ? 0 : 1, dc = a == 0 ? 1 : (a == 1 ? 1 : (a == 2 ? 0 : -1));
         const int r1 = dr > 0 ? win - dr : win, c0 = dc < 0 ? -dc : 0, c1 = dc > 0 ? win - dc : win;
@@ -1133,7 +1085,8 @@ __global__ __launch_bounds__(256) void k4_glcm_wave(const uint8_t *__restrict__ 
             s1 += d; s2 += d * d; hq += c_glcm_hq[d];
             m1 += x + y; m2 += x * x + y * y; mx += 2 * x * y;
         }
-        sums[a][0] = s1; sums[a][1] = s2; sums[a][2] = hq; sums[a][3] = m1; sums[a][4] = m2; sums[a][5] = mx;
+        sums[a][0] = s1; sums[a][1] = s2; sums[a][2] = SPLIT ? 0 : hq; sums[a][3] = m1; sums[a][4] = m2; sums[a][5] = mx;
+        if constexpr (SPLIT) hqs[a] = hq_split(hq);  // a lane holds at most ceil(254 * 255 / 64) = 1012 terms of at most 2^52
     }
     long long A[4];
     for (int a = 0; a < 4; a++) {
@@ -1146,18 +1099,29 @@ __global__ __launch_bounds__(256) void k4_glcm_wave(const uint8_t *__restrict__ 
         }
         A[a] = wave_sum(acc);
 #pragma unroll
-        for (int t = 0; t < 6; t++) sums[a][t] = wave_sum(sums[a][t]);
+        for (int t = 0; t < 6; t++)
+            if (!SPLIT || t != 2) sums[a][t] = wave_sum(sums[a][t]);
+        if constexpr (SPLIT) {
+            hqs[a].hi = wave_sum(hqs[a].hi);
+            hqs[a].lo = wave_sum(hqs[a].lo);
+        }
     }
     if (lane == 0) {
         const long long na = (long long)win * (win - 1), nb = (long long)(win - 1) * (win - 1);
         glcm_group g0, g1;
-        g0.S1 = sums[0][0] + sums[2][0]; g0.S2 = sums[0][1] + sums[2][1]; g0.Hq = sums[0][2] + sums[2][2];
+        g0.S1 = sums[0][0] + sums[2][0]; g0.S2 = sums[0][1] + sums[2][1]; g0.Hq = 0;
         g0.sq = sqrt((double)A[0]) + sqrt((double)A[2]);
-        g1.S1 = sums[1][0] + sums[3][0]; g1.S2 = sums[1][1] + sums[3][1]; g1.Hq = sums[1][2] + sums[3][2];
+        g1.S1 = sums[1][0] + sums[3][0]; g1.S2 = sums[1][1] + sums[3][1]; g1.Hq = 0;
         g1.sq = sqrt((double)A[1]) + sqrt((double)A[3]);
+        if constexpr (!SPLIT) {
+#pragma unroll
+            for (int a = 0; a < 4; a++) hqs[a] = hq_split(sums[a][2]);
+        }
+        const double hq0 = hq_to_double(glcm_hq_sum{hqs[0].hi + hqs[2].hi, hqs[0].lo + hqs[2].lo});
+        const double hq1 = hq_to_double(glcm_hq_sum{hqs[1].hi + hqs[3].hi, hqs[1].lo + hqs[3].lo});
         double r[4];
         for (int a = 0; a < 4; a++) r[a] = glcm_corr((a & 1) ? nb : na, sums[a][3], sums[a][4], sums[a][5]);
-        glcm_finish(g0, g1, na, nb, r[0], r[1], r[2], r[3], (size_t)oy * ow + ox, out, gc);
+        glcm_finish_hq(g0, g1, hq0, hq1, na, nb, r[0], r[1], r[2], r[3], (size_t)oy * ow + ox, out, gc);
     }
 }
 
@@ -1165,8 +1129,8 @@ __global__ __launch_bounds__(256) void k4_glcm_wg(const uint8_t *__restrict__ q,
                                                   int oh, int ow, glcm_out out, glcm_consts gc)
 {
     extern __shared__ unsigned int hist[];  // levels*levels
-    __shared__ long long red[4][8];
-    __shared__ long long sst[4][8];
+    __shared__ long long red[4][9];
+    __shared__ long long sst[4][9];
     const int ox = blockIdx.x, oy = blockIdx.y;
     const uint8_t *wp = q + (size_t)(oy * step) * W + (size_t)ox * step;
     const int LL = levels * levels;
@@ -1176,13 +1140,14 @@ __global__ __launch_bounds__(256) void k4_glcm_wg(const uint8_t *__restrict__ q,
         const int pw = c1 - c0, P = r1 * pw;
         for (int i = threadIdx.x; i < LL; i += 256) hist[i] = 0;
         __syncthreads();
-        long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // np S1 S2 Hq M1 M2 Mx A
+        long long st[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // np S1 S2 Hq.hi M1 M2 Mx A Hq.lo (Hq split: k4_glcm.h)
         for (int p = threadIdx.x; p < P; p += 256) {
             const int r = p / pw, c = c0 + p % pw;
             const int x = wp[(size_t)r * W + c], y = wp[(size_t)(r + dr) * W + (c + dc)];
             atomicAdd(&hist[x * levels + y], 1u);
             const int d = x > y ? x - y : y - x;
-            st[0] += 1; st[1] += d; st[2] += d * d; st[3] += c_glcm_hq[d];
+            const long long hq = c_glcm_hq[d];
+            st[0] += 1; st[1] += d; st[2] += d * d; st[3] += hq >> GLCM_HQ_SPLIT; st[8] += hq & ((1ll << GLCM_HQ_SPLIT) - 1);
             st[4] += x + y; st[5] += x * x + y * y; st[6] += 2 * x * y;
         }
         __syncthreads();
@@ -1192,24 +1157,26 @@ __global__ __launch_bounds__(256) void k4_glcm_wg(const uint8_t *__restrict__ q,
             st[7] += g * g;
         }
 #pragma unroll
-        for (int t = 0; t < 8; t++) {
+        for (int t = 0; t < 9; t++) {
             long long s = wave_sum(st[t]);
             if (lane_id() == 0) red[threadIdx.x >> 6][t] = s;
         }
         __syncthreads();
-        if (threadIdx.x < 8) sst[a][threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+        if (threadIdx.x < 9) sst[a][threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        // sst[a] = np S1 S2 Hq M1 M2 Mx A ; all pixels are < levels, so np depends on the geometry only
+        // sst[a] = np S1 S2 Hq.hi M1 M2 Mx A Hq.lo ; all pixels are < levels, so np depends on the geometry only
         glcm_group g0, g1;
-        g0.S1 = sst[0][1] + sst[2][1]; g0.S2 = sst[0][2] + sst[2][2]; g0.Hq = sst[0][3] + sst[2][3];
+        g0.S1 = sst[0][1] + sst[2][1]; g0.S2 = sst[0][2] + sst[2][2]; g0.Hq = 0;
         g0.sq = sqrt((double)sst[0][7]) + sqrt((double)sst[2][7]);
-        g1.S1 = sst[1][1] + sst[3][1]; g1.S2 = sst[1][2] + sst[3][2]; g1.Hq = sst[1][3] + sst[3][3];
+        g1.S1 = sst[1][1] + sst[3][1]; g1.S2 = sst[1][2] + sst[3][2]; g1.Hq = 0;
         g1.sq = sqrt((double)sst[1][7]) + sqrt((double)sst[3][7]);
+        const double hq0 = hq_to_double(glcm_hq_sum{sst[0][3] + sst[2][3], sst[0][8] + sst[2][8]});
+        const double hq1 = hq_to_double(glcm_hq_sum{sst[1][3] + sst[3][3], sst[1][8] + sst[3][8]});
         double r[4];
         for (int a = 0; a < 4; a++) r[a] = glcm_corr(sst[a][0], sst[a][4], sst[a][5], sst[a][6]);
-        glcm_finish(g0, g1, (long long)win * (win - 1), (long long)(win - 1) * (win - 1), r[0], r[1], r[2], r[3],
+        glcm_finish_hq(g0, g1, hq0, hq1, (long long)win * (win - 1), (long long)(win - 1) * (win - 1), r[0], r[1], r[2], r[3],
                     (size_t)oy * ow + ox, out, gc);
     }
 }
@@ -1221,8 +1188,10 @@ extern "C" int rsseg_glcm_u8(rsseg_ctx *ctx, const uint8_t *d_q, int H, int W, i
                              float *const *d_props)
 {
     if (!ctx) return RSSEG_ERR_INVALID;
-    if (!d_q || !d_props || H < 1 || W < 1 || levels < 2 || levels > 256 || win < 2 || win > H || win > W || step < 1)
+    if (!d_q || !d_props || H < 1 || W < 1 || levels < 2 || win < 2 || win > H || win > W || step < 1)
         return rs_fail(ctx, RSSEG_ERR_INVALID, "glcm: bad arguments (H=%d W=%d levels=%d win=%d step=%d)", H, W, levels, win, step);
+    if (levels > 256)   // the quantised plane is uint8; NumPy's astype(uint8) of values above 255 is platform-defined
+        return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "glcm: levels=%d > 256 not supported (the quantised plane is uint8)", levels);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::unique_lock<std::mutex> hq_lock(g_hq_mu);
     if (!g_hq_ready[ctx->device & 63]) {
@@ -1241,27 +1210,18 @@ extern "C" int rsseg_glcm_u8(rsseg_ctx *ctx, const uint8_t *d_q, int H, int W, i
     {
         prof_scope ps(ctx, "glcm");
         const dim3 tg((ow + 63) / 64, (oh + 3) / 4);
-        if (levels > 64) return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "glcm: levels > 64 not supported");
         glcm_consts gc;
-        {
-            const long long na = (long long)win * (win - 1), nb = (long long)(win - 1) * (win - 1);
-            gc.den4 = (double)(4 * na * nb);
-            gc.den8 = (double)(8 * na * nb);
-            gc.rden4 = 1.0 / gc.den4;
-            gc.rden8 = 1.0 / gc.den8;
-            // div_const needs a divisor whose significand is not all ones: true for these small integers, checked anyway
-            for (double dv : {gc.den4, gc.den8}) {
-                uint64_t b;
-                memcpy(&b, &dv, 8);
-                if ((b & 0xfffffffffffffull) == 0xfffffffffffffull) return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "glcm: window size %d not supported", win);
-            }
-        }
+        // div_const needs a divisor whose significand is not all ones: true for these small integers, checked anyway
+        if (!glcm_make_consts(win, gc)) return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "glcm: window size %d not supported", win);
 #define GLCM_THREAD(WN)                                                                                                           \
     do {                                                                                                                          \
         if (levels <= 32) hipLaunchKernelGGL((k4_glcm_thread<WN, 3>), tg, dim3(256), 0, ctx->stream, d_q, H, W, step, oh, ow, out, gc); \
         else hipLaunchKernelGGL((k4_glcm_thread<WN, 2>), tg, dim3(256), 0, ctx->stream, d_q, H, W, step, oh, ow, out, gc);          \
     } while (0)
-        if (win == 7 && step == 1 && levels <= 32) {
+        if (levels > 64) {   // 65..256 levels: the unordered-cell table of k4_glcm_offsets.hip, finished over the same denominators
+            static const int32_t def[8] = {0, 1, 1, 1, 1, 0, 1, -1};
+            RSCHK(glcm_offsets_launch(ctx, d_q, H, W, levels, win, step, def, 4, out, true, gc));
+        } else if (win == 7 && step == 1 && levels <= 32) {
             const char *kv = getenv("RSSEG_GLCM_DENSE");      // "pair": the r02 kernel (two windows per thread), for A/B runs
             if (kv && !strcmp(kv, "pair")) {
                 const dim3 pg((ow + 127) / 128, (oh + 3) / 4);   // two adjacent windows per thread
@@ -1275,8 +1235,11 @@ extern "C" int rsseg_glcm_u8(rsseg_ctx *ctx, const uint8_t *d_q, int H, int W, i
         else if (win == 3) GLCM_THREAD(3);
         else {
             if (levels <= 32 && win < 256) {
-                hipLaunchKernelGGL(k4_glcm_wave, dim3((unsigned)ceil_div64((int64_t)oh * ow, 4)), dim3(256), 0, ctx->stream, d_q, H, W, levels, win, step, oh,
-                                   ow, out, gc);
+                const dim3 wg((unsigned)ceil_div64((int64_t)oh * ow, 4));
+                if (win <= 45)   // fewer than 2048 pairs per angle: the per-angle int64 homogeneity sums are exact
+                    hipLaunchKernelGGL(k4_glcm_wave<false>, wg, dim3(256), 0, ctx->stream, d_q, H, W, levels, win, step, oh, ow, out, gc);
+                else
+                    hipLaunchKernelGGL(k4_glcm_wave<true>, wg, dim3(256), 0, ctx->stream, d_q, H, W, levels, win, step, oh, ow, out, gc);
             } else if (ow > 2147483647 || oh > 65535) return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "glcm: output map too tall for the workgroup-per-window kernel");
             else hipLaunchKernelGGL(k4_glcm_wg, dim3(ow, oh), dim3(256), sizeof(unsigned int) * levels * levels, ctx->stream, d_q, H, W,
                                levels, win, step, oh, ow, out, gc);

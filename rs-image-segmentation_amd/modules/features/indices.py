@@ -153,13 +153,13 @@ def perform_pca(bands_data, n_components=None, use_robust_scaling=True):
 
 def calculate_glcm_features(band, distances=[1], angles=[0, np.pi / 4, np.pi / 2, 3 * np.pi / 4], levels=32, window_size=21,
                             step_size=21):
-    """reference indices.py:248-318"""
-    if list(distances) != [1] or not np.allclose(list(angles), [0, np.pi / 4, np.pi / 2, 3 * np.pi / 4]):
-        raise ValueError("calculate_glcm_features: only distances=[1] and the four default angles are implemented")
+    """reference indices.py:248-318: any finite distances / angles (graycomatrix's offsets, rsseg.pipeline.glcm_offset_plan),
+    levels 2..256"""
     d, (h, w) = _dev(band)
+    _P.glcm_offset_plan(distances, angles)   # ValueError for empty or non-finite lists (after _dev's float64 refusal)
     ctx = _ctx()
     nir2 = _P.renormalize(ctx, d)
-    feats, _ = _P.glcm_features(ctx, nir2, h, w, levels, window_size, step_size)
+    feats, _ = _P.glcm_features(ctx, nir2, h, w, levels, window_size, step_size, distances=distances, angles=angles)
     return {k: _host(v, (h, w)) for k, v in feats.items()}
 
 

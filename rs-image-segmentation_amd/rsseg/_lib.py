@@ -81,6 +81,7 @@ SIGNATURES = {
                                                C.POINTER(C.c_float)]),
     "rsseg_normalize_quantize_u8": (_int, [_vp, _vp, _i64, C.c_float, C.c_float, C.c_float, _vp]),
     "rsseg_glcm_u8": (_int, [_vp, _vp, _int, _int, _int, _int, _int, _PP]),
+    "rsseg_glcm_offsets_u8": (_int, [_vp, _vp, _int, _int, _int, _int, _int, C.POINTER(C.c_int32), _int, _PP]),
     "rsseg_quantize_u8": (_int, [_vp, _vp, _i64, C.c_float, _vp]),
     "rsseg_u8_to_unit_f32": (_int, [_vp, _vp, _i64, _vp]),
     "rsseg_u8_to_f32": (_int, [_vp, _vp, _i64, _vp]),

@@ -7,6 +7,7 @@ the bands already resident in HBM.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -126,17 +127,53 @@ def renormalize(ctx: Context, plane, n_global: Optional[int] = None):
     return ctx.normalize(plane, float(lo), float(hi))
 
 
-def glcm_features(ctx: Context, nir_norm, H: int, W: int, levels=32, window_size=21, step_size=21, upsample=True, renorm=None, q=None):
+GLCM_DEFAULT_DISTANCES = [1]
+GLCM_DEFAULT_ANGLES = [0, math.pi / 4, math.pi / 2, 3 * math.pi / 4]
+
+
+def glcm_offset_plan(distances, angles):
+    """graycomatrix's pixel offsets (scikit-image 0.18 feature/_texture.pyx::_glcm_loop) for the entries of
+    (distances x angles) in C order (distance-major, angle-minor): dr = round(sin(angle) * distance),
+    dc = round(cos(angle) * distance) with libm's sin / cos on float64 and Python's round (ties to even).
+    Returns (entries, distinct, index): the (dr, dc) of every entry, the distinct offsets (o and -o give the same
+    symmetric matrix: one of them, (dr, dc) with dr > 0 or dr == 0 <= dc), and each entry's index into `distinct`.
+    Empty lists and non-finite values raise ValueError, as graycomatrix does."""
+    d = np.asarray(distances, dtype=np.float64).reshape(-1)
+    a = np.asarray(angles, dtype=np.float64).reshape(-1)
+    if d.size == 0 or a.size == 0:
+        raise ValueError("glcm: distances and angles must be non-empty")
+    if not (np.all(np.isfinite(d)) and np.all(np.isfinite(a))):
+        raise ValueError("glcm: distances and angles must be finite")
+    entries, distinct, index, seen = [], [], [], {}
+    for dist in d.tolist():
+        for ang in a.tolist():
+            dr, dc = round(math.sin(ang) * dist), round(math.cos(ang) * dist)
+            entries.append((dr, dc))
+            key = (dr, dc) if dr > 0 or (dr == 0 and dc >= 0) else (-dr, -dc)
+            if key not in seen:
+                seen[key] = len(distinct)
+                distinct.append(key)
+            index.append(seen[key])
+    return entries, distinct, index
+
+
+def glcm_features(ctx: Context, nir_norm, H: int, W: int, levels=32, window_size=21, step_size=21, upsample=True, renorm=None, q=None,
+                  distances=None, angles=None):
     """calculate_glcm_features (indices.py:248-318) on an already re-normalised band, or — renorm=(lo, hi) — on the band
     as the function receives it, re-normalised with its percentiles and quantised in one pass, or — q — on the already
-    quantised uint8 plane (the fused index / PCA pass can write it)."""
+    quantised uint8 plane (the fused index / PCA pass can write it).  distances / angles: graycomatrix's (None: [1] and
+    the four angles 0, pi/4, pi/2, 3 pi/4)."""
+    offsets = None
+    if distances is not None or angles is not None:
+        offsets, _, _ = glcm_offset_plan(GLCM_DEFAULT_DISTANCES if distances is None else distances,
+                                         GLCM_DEFAULT_ANGLES if angles is None else angles)
     if q is not None:
         pass
     elif renorm is None:
         q = ctx.quantize_u8(nir_norm, float(levels - 1))
     else:
         q = ctx.normalize_quantize_u8(nir_norm, float(renorm[0]), float(renorm[1]), float(levels - 1))
-    small, (oh, ow) = ctx.glcm(q, H, W, levels, window_size, step_size)
+    small, (oh, ow) = ctx.glcm(q, H, W, levels, window_size, step_size, offsets=offsets)
     if not upsample:
         return dict(zip(GLCM_NAMES, small)), (oh, ow)
     return dict(zip(GLCM_NAMES, ctx.resize_bilinear_multi(small, oh, ow, 0, oh, H, W, 0, H))), (oh, ow)   # five maps, one launch

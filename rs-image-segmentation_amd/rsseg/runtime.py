@@ -514,11 +514,20 @@ class Context:
         return idx, norms, pcs, comp, ratio, mean, ev
 
     # ---- K4..K8 --------------------------------------------------------------------------------
-    def glcm(self, q, H: int, W: int, levels: int, win: int, step: int):
+    def glcm(self, q, H: int, W: int, levels: int, win: int, step: int, offsets=None):
+        """The five GLCM property maps of the windows of q.  offsets: the (dr, dc) entries of pipeline.glcm_offset_plan in
+        entry order (None: the four default angles at distance 1, rsseg_glcm_u8)."""
         torch = _torch()
         oh, ow = (H - win) // step + 1, (W - win) // step + 1
         outs = [self.empty(oh * ow, torch.float32) for _ in range(5)]
-        self._chk(self.lib.rsseg_glcm_u8(self.h, C.c_void_p(q.data_ptr()), H, W, levels, win, step, self._pp(outs)))
+        if offsets is None:
+            self._chk(self.lib.rsseg_glcm_u8(self.h, C.c_void_p(q.data_ptr()), H, W, levels, win, step, self._pp(outs)))
+            return outs, (oh, ow)
+        # an offset at least 2^15 long leaves every window: its sign is kept, its length clamped to fit 16 bits
+        flat = [max(-32767, min(32767, int(v))) for o in offsets for v in o]
+        arr = (C.c_int32 * len(flat))(*flat)
+        self._chk(self.lib.rsseg_glcm_offsets_u8(self.h, C.c_void_p(q.data_ptr()), H, W, levels, win, step, arr, len(offsets),
+                                                 self._pp(outs)))
         return outs, (oh, ow)
 
     def resize_bilinear(self, src, sh: int, sw: int, dh: int, dw: int):
