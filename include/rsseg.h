@@ -38,6 +38,11 @@ extern "C" {
 #define RSSEG_F32 0
 #define RSSEG_F64 1
 #define RSSEG_I64 2
+/* integer label planes (rsseg_confusion_counts) */
+#define RSSEG_U8 3
+#define RSSEG_I16 4
+#define RSSEG_U16 5
+#define RSSEG_I32 6
 
 #define RSSEG_SUM 0
 #define RSSEG_MIN 1
@@ -109,7 +114,8 @@ int rsseg_ctx_allreduce(rsseg_ctx *ctx, int64_t offset, int64_t count, int dtype
 /* Per-kernel timing (HIP events on the context's stream, around each launch of the named
  * kernel family).  Used by bench.py for the roofline object.  name: "glcm", "lloyd", "indices", "normalize", "quantize", "range",
  * "select", "kpp", "moment" (KMeans' column means), "labels" (uint8 -> int32 label plane), "box" (one plane), "ctxmean" (several planes per launch), "morph", "filt_max" / "filt_write" (the two passes
- * of Sobel / Laplacian), "project", "indices_project" (the fused pass of rsseg_indices_pca_*), "gram", "forest", "resize", and "allreduce" (host wall time of the hook calls). */
+ * of Sobel / Laplacian), "project", "indices_project" (the fused pass of rsseg_indices_pca_*), "gram", "forest", "resize", "eval_range" / "eval_table"
+ * (the two passes of rsseg_confusion_counts), and "allreduce" (host wall time of the hook calls). */
 /* Number of times the library has made the host wait for the context's stream since the last reset (every result
  * read-back, every all-reduce staged through the host): what a step costs in launch-pipeline bubbles. */
 int rsseg_ctx_host_syncs(rsseg_ctx *ctx, int reset, int64_t *count);
@@ -386,6 +392,26 @@ int rsseg_rank_entropy_u8(rsseg_ctx *ctx, const uint8_t *d_q, int H, int W, int 
 int rsseg_gaussian_blur_u8(rsseg_ctx *ctx, const uint8_t *d_q, int H, int W, int ksize, uint8_t *d_out);
 /* host-only: the ksize taps of that blur in 8 fractional bits (they sum to 256). */
 int rsseg_host_gaussian_kernel_fixed(int ksize, int *taps);
+
+/* ---- K14: accuracy assessment -------------------------------------------------------------- */
+/* The joint count table of (truth value, predicted value) over the pixels where truth > 0 (truth <= 0 is excluded, as
+ * `valid_mask = roi_mask > 0` of scripts/4_evaluate.py:83 and `y_true > 0` of modules/evaluation.py:40 exclude it): the
+ * np.unique / boolean-mask passes of ClassificationEvaluator.extract_valid_samples and map_clusters_to_classes
+ * (scripts/4_evaluate.py:72-128) and the counting inside confusion_matrix, accuracy_score, cohen_kappa_score and
+ * classification_report (:130-160, modules/evaluation.py:44-63).  Every one of those metrics follows exactly from the table.
+ * d_truth: n_local labels of truth_dtype (RSSEG_U8, RSSEG_I16, RSSEG_U16, RSSEG_I32, RSSEG_I64); d_pred: n_local labels of
+ * pred_dtype (RSSEG_U8, RSSEG_I32, RSSEG_I64); both 16-byte aligned.
+ * known_range: NULL, or {tmin, tmax, pmin, pmax} the caller already knows to hold every valid pixel (KMeans labels 0..k-1,
+ * a three-class map 0..3): the range pass is skipped; a valid pixel outside it is RSSEG_ERR_INVALID.  Otherwise one pass
+ * finds the range: range_out = {tmin, tmax, pmin, pmax} of the valid pixels ({0, -1, 0, -1} and *n_valid = 0, no table,
+ * when there is none).  counts (host, cap cells): the int64 table, row-major, cell (t - tmin) * np + (p - pmin) with
+ * np = pmax - pmin + 1; *n_valid = the number of valid pixels.  A table of more than min(cap, 4096) cells is
+ * RSSEG_ERR_UNSUPPORTED with range_out (and *n_valid, after a range pass) filled in.  Synchronous (results on the host).
+ * With a communication path every rank's ranges go through the hook (RSSEG_I64 SUM of the count, MIN, MAX) and so does
+ * the table (RSSEG_I64 SUM): each rank of a row-sharded map receives the whole raster's table, and every rank makes the
+ * same hook calls, also when the table is over the cap. */
+int rsseg_confusion_counts(rsseg_ctx *ctx, const void *d_truth, int truth_dtype, const void *d_pred, int pred_dtype, int64_t n_local,
+                           const int64_t *known_range, int64_t range_out[4], int64_t *n_valid, int64_t *counts, int64_t cap);
 
 /* ---- host-only helper (no GPU needed) ------------------------------------------------------- */
 /* The random draws of k-means++ as the library makes them (numpy RandomState(seed): MT19937, random_sample,

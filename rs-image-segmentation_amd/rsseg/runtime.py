@@ -735,6 +735,41 @@ class Context:
         self._chk(self.lib.rsseg_forest_predict(self.h, self._pp(planes), len(planes), n, C.c_void_p(out.data_ptr())))
         return out
 
+    # ---- K14 -----------------------------------------------------------------------------------
+    def confusion_counts(self, truth, pred, known_range: Optional[Sequence[int]] = None):
+        """rsseg_confusion_counts: the joint count table of (truth, pred) over the pixels where truth > 0.  truth, pred: device
+        tensors of equal length (truth uint8 / int16 / uint16 / int32 / int64, pred uint8 / int32 / int64).  known_range:
+        (tmin, tmax, pmin, pmax) that holds every valid pixel, or None for the range pass.  Returns (truth_values, pred_values,
+        table): the sorted values of the non-empty rows and columns in the input dtypes and the int64 table restricted to
+        them (empty when no pixel is valid).  A table beyond EVAL_MAX_CELLS raises RssegUnsupported."""
+        torch = _torch()
+        codes = {torch.uint8: L.U8, torch.int16: L.I16, torch.uint16: L.U16, torch.int32: L.I32, torch.int64: L.I64}
+        if truth.dtype not in codes or pred.dtype not in (torch.uint8, torch.int32, torch.int64):
+            raise ValueError(f"confusion_counts: truth {truth.dtype} / prediction {pred.dtype} not supported")
+        if truth.numel() != pred.numel():
+            raise ValueError(f"confusion_counts: {truth.numel()} truth values, {pred.numel()} predictions")
+        planes = []
+        for t in (truth.reshape(-1), pred.reshape(-1)):
+            if t.data_ptr() % 16 or not t.is_contiguous():   # the kernels read 16-byte vectors from an aligned start
+                t = t.clone(memory_format=torch.contiguous_format)
+            planes.append(t)
+        t, p = planes
+        kr = None if known_range is None else (C.c_int64 * 4)(*[int(v) for v in known_range])
+        rng = (C.c_int64 * 4)()
+        nv = C.c_int64(0)
+        cap = L.EVAL_MAX_CELLS
+        counts = np.zeros(cap, np.int64)
+        self._chk(self.lib.rsseg_confusion_counts(self.h, C.c_void_p(t.data_ptr()), codes[t.dtype], C.c_void_p(p.data_ptr()), codes[p.dtype],
+                                                  t.numel(), kr, rng, C.byref(nv), counts.ctypes.data_as(C.POINTER(C.c_int64)), cap))
+        tnp, pnp = np.dtype(str(t.dtype).split(".")[1]), np.dtype(str(p.dtype).split(".")[1])
+        tmin, tmax, pmin, pmax = rng[:]
+        if nv.value == 0:
+            return np.zeros(0, tnp), np.zeros(0, pnp), np.zeros((0, 0), np.int64)
+        nt, npv = tmax - tmin + 1, pmax - pmin + 1
+        table = counts[:nt * npv].reshape(nt, npv)
+        rows, cols = np.flatnonzero(table.sum(1)), np.flatnonzero(table.sum(0))
+        return ((tmin + rows).astype(tnp), (pmin + cols).astype(pnp), np.ascontiguousarray(table[np.ix_(rows, cols)]))
+
 
 _default_ctx: Optional[Context] = None
 

@@ -283,11 +283,12 @@ def _rt_unsupported():
 # scripts/3_classification.py:545-632):   python -m rsseg.stages <image.tif> <output_dir> [--classify kmeans]
 # --------------------------------------------------------------------------------------------------
 def run_scripts_2_3(image_path: str, output_dir: str, classify: Optional[str] = None, preprocessing: bool = True, n_clusters: int = 7,
-                    ctx: Optional[Context] = None) -> Dict[str, object]:
+                    ctx: Optional[Context] = None, evaluate: Optional[str] = None) -> Dict[str, object]:
     """Reads the GeoTIFF's bands as float32 with nodata -> NaN (scripts/2:154-161), runs the feature stage, writes
     <output_dir>/feature_outputs/{level1,level2,all_hierarchical}_features.npy, all_features_and_metadata.pkl and
     all_hierarchical_features.tif (scripts/2:193-258), then — `classify` in {'kmeans', 'rule_based', 'random_forest'} —
-    the classification stage on that pickle into <output_dir>/segmentation_results (scripts/3:548-551)."""
+    the classification stage on that pickle into <output_dir>/segmentation_results (scripts/3:548-551), and — `evaluate` naming a
+    ROI mask (.npy / .tif) — the accuracy assessment of that class map (scripts/4) into <output_dir>/evaluation_results."""
     from .tiff import read_tiff, read_tiff_georef
     arr = read_tiff(image_path)
     geo = read_tiff_georef(image_path)
@@ -307,6 +308,12 @@ def run_scripts_2_3(image_path: str, output_dir: str, classify: Optional[str] = 
         sdir = os.path.join(output_dir, "segmentation_results")
         res["class_map"] = run_classification_stage(paths["pkl"], classify, sdir, True, n_clusters=n_clusters, ctx=ctx)
         res["segmentation_dir"] = sdir
+        if evaluate and res["class_map"] is not None:
+            from .evaluate import ClassificationEvaluator
+            ev = ClassificationEvaluator(ctx)
+            edir = os.path.join(output_dir, "evaluation_results")
+            res["metrics"], res["cluster_mapping"] = ev.evaluate_maps(res["class_map"], ev.load_roi_mask(evaluate), edir)
+            res["evaluation_dir"] = edir
     return res
 
 
@@ -319,13 +326,19 @@ def main(argv=None) -> int:
     ap.add_argument("--classify", choices=["kmeans", "rule_based", "random_forest"])
     ap.add_argument("--n-clusters", type=int, default=7)
     ap.add_argument("--no-preprocessing", action="store_true")
+    ap.add_argument("--evaluate", metavar="ROI_MASK", help="accuracy assessment (scripts/4) of the class map against this ROI mask (.npy / .tif)")
     a = ap.parse_args(argv)
-    res = run_scripts_2_3(a.image, a.output_dir, a.classify, not a.no_preprocessing, a.n_clusters)
+    if a.evaluate and not a.classify:
+        ap.error("--evaluate needs --classify")
+    res = run_scripts_2_3(a.image, a.output_dir, a.classify, not a.no_preprocessing, a.n_clusters, evaluate=a.evaluate)
     for k, v in res["paths"].items():
         print(f"{k}: {v}")
     if a.classify:
         cm = res.get("class_map")
         print(f"class map: {None if cm is None else (cm.shape, np.unique(cm).tolist())} -> {res['segmentation_dir']}")
+        if "metrics" in res:
+            m = res["metrics"]
+            print(f"evaluation: OA {m['overall_accuracy'] * 100:.2f}%, kappa {m['kappa_coefficient']:.4f} -> {res['evaluation_dir']}")
         return 0 if cm is not None else 1
     return 0
 
