@@ -38,7 +38,7 @@ extern "C" {
 #define RSSEG_F32 0
 #define RSSEG_F64 1
 #define RSSEG_I64 2
-/* integer label planes (rsseg_confusion_counts) */
+/* integer label planes (rsseg_confusion_counts) and DN planes (rsseg_preprocess_u8) */
 #define RSSEG_U8 3
 #define RSSEG_I16 4
 #define RSSEG_U16 5
@@ -115,7 +115,7 @@ int rsseg_ctx_allreduce(rsseg_ctx *ctx, int64_t offset, int64_t count, int dtype
  * kernel family).  Used by bench.py for the roofline object.  name: "glcm", "lloyd", "indices", "normalize", "quantize", "range",
  * "select", "kpp", "moment" (KMeans' column means), "labels" (uint8 -> int32 label plane), "box" (one plane), "ctxmean" (several planes per launch), "morph", "filt_max" / "filt_write" (the two passes
  * of Sobel / Laplacian), "project", "indices_project" (the fused pass of rsseg_indices_pca_*), "gram", "forest", "resize", "eval_range" / "eval_table"
- * (the two passes of rsseg_confusion_counts), and "allreduce" (host wall time of the hook calls). */
+ * (the two passes of rsseg_confusion_counts), "pre_range" / "pre_stretch" (the two passes of rsseg_preprocess_u8), and "allreduce" (host wall time of the hook calls). */
 /* Number of times the library has made the host wait for the context's stream since the last reset (every result
  * read-back, every all-reduce staged through the host): what a step costs in launch-pipeline bubbles. */
 int rsseg_ctx_host_syncs(rsseg_ctx *ctx, int reset, int64_t *count);
@@ -412,6 +412,30 @@ int rsseg_host_gaussian_kernel_fixed(int ksize, int *taps);
  * same hook calls, also when the table is over the cap. */
 int rsseg_confusion_counts(rsseg_ctx *ctx, const void *d_truth, int truth_dtype, const void *d_pred, int pred_dtype, int64_t n_local,
                            const int64_t *known_range, int64_t range_out[4], int64_t *n_valid, int64_t *counts, int64_t cap);
+
+/* ---- K15: preprocessing (stage 1) ----------------------------------------------------------- */
+/* Radiometric calibration, the identity warp and the 8-bit min-max stretch of modules/features/preprocessing.py:54-125, as
+ * scripts/1_preprocessing.py:25-85 chains them: per band b, radiance = gain[b] * DN + bias[b] in float64 (float32 for
+ * float32 DN, the constants rounded to float32 first; two roundings, no fma), mn / mx = np.min / np.max of the radiance
+ * (NaN when the band holds a NaN), then ((radiance - mn) * 255) / (mx - mn) in that dtype and .astype(np.uint8) as x86-64
+ * NumPy casts it (truncation; 0 for NaN and +-inf, so a constant band, a band with a NaN and a band with an infinite
+ * radiance range come out all zero).  Bit-exact.
+ * d_in[n_bands]: n_local DN of in_dtype (RSSEG_U8, RSSEG_I16, RSSEG_U16, RSSEG_I32, RSSEG_F32, RSSEG_F64; anything else is
+ * RSSEG_ERR_INVALID, named); d_out[n_bands]: n_local uint8; all 16-byte aligned; n_bands <= 16.
+ * gain / bias: n_bands finite values, every gain > 0 (else RSSEG_ERR_INVALID); both NULL: the stretch alone, on values
+ * already calibrated (image_enhancement of what it is handed; for int16 / int32 the caller keeps mx - mn within the type).
+ * Two passes, both enqueued without a host wait: per band the min / max of the non-NaN DN and the NaN count (one partial per
+ * workgroup, reduced on the device), then the stretch, whose workgroups derive the radiance range from that record (8-bit
+ * DN through a 256-entry table in LDS).  With a communication path the record goes through the hook (RSSEG_F64 MIN and
+ * MAX, RSSEG_I64 SUM of the NaN counts): every rank of a row-sharded raster is stretched with the whole raster's range.
+ * range_out: NULL, or (host) double[n_bands][3] = {min, max of the non-NaN DN (+inf, -inf when there is none), NaN count}
+ * of the whole raster, read back with the only host wait of the call.  Profiler names "pre_range", "pre_stretch". */
+int rsseg_preprocess_u8(rsseg_ctx *ctx, const void *const *d_in, int in_dtype, int n_bands, int64_t n_local, const double *gain,
+                        const double *bias, uint8_t *const *d_out, double *range_out);
+/* radiometric_calibration of one band (preprocessing.py:54-74): d_out[i] = gain * d_in[i] + bias, float64 (RSSEG_F64
+ * output), or float32 for RSSEG_F32 input (float32 constants and operations, as NumPy 2 promotes).  in_dtype as above;
+ * gain and bias finite. */
+int rsseg_radiometric(rsseg_ctx *ctx, const void *d_in, int in_dtype, int64_t n, double gain, double bias, void *d_out);
 
 /* ---- host-only helper (no GPU needed) ------------------------------------------------------- */
 /* The random draws of k-means++ as the library makes them (numpy RandomState(seed): MT19937, random_sample,

@@ -14,7 +14,7 @@ MAX_FEATURES = 64
 MAX_CLUSTERS = 64
 MAX_RANKS = 16
 F32, F64, I64 = 0, 1, 2
-U8, I16, U16, I32 = 3, 4, 5, 6   # integer label planes (rsseg_confusion_counts)
+U8, I16, U16, I32 = 3, 4, 5, 6   # integer label planes (rsseg_confusion_counts), DN planes (rsseg_preprocess_u8)
 EVAL_MAX_CELLS = 4096            # the largest table rsseg_confusion_counts builds on the device
 SUM, MIN, MAX = 0, 1, 2
 BORDER_REFLECT, BORDER_REFLECT101 = 0, 1
@@ -129,6 +129,9 @@ SIGNATURES = {
     "rsseg_gaussian_blur_u8": (_int, [_vp, _vp, _int, _int, _int, _vp]),
     "rsseg_confusion_counts": (_int, [_vp, _vp, _int, _vp, _int, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64),
                                       C.POINTER(_i64), _i64]),
+    "rsseg_preprocess_u8": (_int, [_vp, _PP, _int, _int, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), _PP,
+                                   C.POINTER(C.c_double)]),
+    "rsseg_radiometric": (_int, [_vp, _vp, _int, _i64, C.c_double, C.c_double, _vp]),
     "rsseg_host_gaussian_kernel_fixed": (_int, [_int, C.POINTER(_int)]),
     "rsseg_host_lzw_encode": (_i64, [_vp, _i64, _vp, _i64]),
     "rsseg_host_lzw_decode": (_i64, [_vp, _i64, _vp, _i64]),

@@ -770,6 +770,65 @@ class Context:
         rows, cols = np.flatnonzero(table.sum(1)), np.flatnonzero(table.sum(0))
         return ((tmin + rows).astype(tnp), (pmin + cols).astype(pnp), np.ascontiguousarray(table[np.ix_(rows, cols)]))
 
+    # ---- K15 -----------------------------------------------------------------------------------
+    def _dn_code(self, t, what: str) -> int:
+        torch = _torch()
+        codes = {torch.uint8: L.U8, torch.int16: L.I16, torch.uint16: L.U16, torch.int32: L.I32, torch.float32: L.F32,
+                 torch.float64: L.F64}
+        if t.dtype not in codes:
+            raise ValueError(f"{what}: input dtype {str(t.dtype).split('.')[-1]} not supported "
+                             "(uint8, int16, uint16, int32, float32 or float64)")
+        return codes[t.dtype]
+
+    @staticmethod
+    def _aligned(t):
+        t = t.reshape(-1)
+        if t.data_ptr() % 16 or not t.is_contiguous():   # the kernels read 16-byte vectors from an aligned start
+            t = t.clone(memory_format=_torch().contiguous_format)
+        return t
+
+    def preprocess_u8(self, planes: Sequence, gain: Optional[Sequence[float]] = None, bias: Optional[Sequence[float]] = None,
+                      want_range: bool = False, out: Optional[Sequence] = None):
+        """rsseg_preprocess_u8: calibration (gain * DN + bias), identity warp and min-max stretch to uint8 of equal-length
+        device planes of one dtype, without a host wait.  gain / bias None: the stretch alone.  Returns the uint8 planes, and
+        with want_range also the whole raster's (n_bands, 3) float64 array {min, max of the non-NaN DN, NaN count} (one host
+        wait)."""
+        torch = _torch()
+        if not planes:
+            raise ValueError("preprocess_u8: no planes")
+        code = self._dn_code(planes[0], "preprocess_u8")
+        if any(p.dtype != planes[0].dtype or p.numel() != planes[0].numel() for p in planes):
+            raise ValueError("preprocess_u8: the planes must share one dtype and length")
+        ins = [self._aligned(p) for p in planes]
+        n, nb = ins[0].numel(), len(ins)
+        outs = list(out) if out is not None else [self.empty(n, torch.uint8) for _ in range(nb)]
+        if len(outs) != nb or any(o.dtype != torch.uint8 or o.numel() != n or o.data_ptr() % 16 or not o.is_contiguous() for o in outs):
+            raise ValueError("preprocess_u8: out must hold one contiguous, 16-byte aligned uint8 plane per band")
+        if self._needs_keep():
+            self._keep.extend(ins)
+        g = b = None
+        if gain is not None or bias is not None:
+            if gain is None or bias is None or len(gain) != nb or len(bias) != nb:
+                raise ValueError("preprocess_u8: gain and bias need one value per band each")
+            g, b = (C.c_double * nb)(*[float(v) for v in gain]), (C.c_double * nb)(*[float(v) for v in bias])
+        rng = np.zeros((nb, 3), np.float64) if want_range else None
+        self._chk(self.lib.rsseg_preprocess_u8(self.h, self._pp(ins), code, nb, n, g, b, self._pp(outs),
+                                               None if rng is None else rng.ctypes.data_as(C.POINTER(C.c_double))))
+        return (outs, rng) if want_range else outs
+
+    def radiometric(self, plane, gain: float, bias: float, out=None):
+        """rsseg_radiometric: gain * plane + bias, float64 (float32 for a float32 plane), as NumPy 2 computes it."""
+        torch = _torch()
+        code = self._dn_code(plane, "radiometric")
+        x = self._aligned(plane)
+        dt = torch.float32 if x.dtype == torch.float32 else torch.float64
+        out = out if out is not None else self.empty(x.numel(), dt)
+        if out.dtype != dt or out.numel() != x.numel() or not out.is_contiguous():
+            raise ValueError(f"radiometric: out must be a contiguous {dt} plane of {x.numel()} values")
+        self._chk(self.lib.rsseg_radiometric(self.h, C.c_void_p(x.data_ptr()), code, x.numel(), float(gain), float(bias),
+                                             C.c_void_p(out.data_ptr())))
+        return out
+
 
 _default_ctx: Optional[Context] = None
 

@@ -33,6 +33,12 @@ def run_feature_extraction_stage(bands_data: Sequence[np.ndarray], preprocessing
     arrs = [np.asarray(b) for b in bands_data if b is not None]
     all_u8 = all(a.dtype == np.uint8 for a in arrs)
     dev = [ctx.upload_band(a) if all_u8 else ctx.upload_f32(a) for a in arrs]
+    return _feature_extraction_on_device(ctx, dev, h, w, preprocessing)
+
+
+def _feature_extraction_on_device(ctx: Context, dev: Sequence, h: int, w: int, preprocessing: bool = True) -> Tuple[Dict, Dict]:
+    """run_feature_extraction_stage from the bands' flat device planes (uint8 or float32): what --raw hands over from stage 1
+    without a host round trip."""
     planes, ex = P.feature_stack19(ctx, dev, h, w, preprocessing=bool(preprocessing))   # False: bands taken as given (scripts/2:43-50)
 
     def host(t):
@@ -283,27 +289,39 @@ def _rt_unsupported():
 # scripts/3_classification.py:545-632):   python -m rsseg.stages <image.tif> <output_dir> [--classify kmeans]
 # --------------------------------------------------------------------------------------------------
 def run_scripts_2_3(image_path: str, output_dir: str, classify: Optional[str] = None, preprocessing: bool = True, n_clusters: int = 7,
-                    ctx: Optional[Context] = None, evaluate: Optional[str] = None) -> Dict[str, object]:
+                    ctx: Optional[Context] = None, evaluate: Optional[str] = None, raw: bool = False) -> Dict[str, object]:
     """Reads the GeoTIFF's bands as float32 with nodata -> NaN (scripts/2:154-161), runs the feature stage, writes
     <output_dir>/feature_outputs/{level1,level2,all_hierarchical}_features.npy, all_features_and_metadata.pkl and
     all_hierarchical_features.tif (scripts/2:193-258), then — `classify` in {'kmeans', 'rule_based', 'random_forest'} —
     the classification stage on that pickle into <output_dir>/segmentation_results (scripts/3:548-551), and — `evaluate` naming a
-    ROI mask (.npy / .tif) — the accuracy assessment of that class map (scripts/4) into <output_dir>/evaluation_results."""
-    from .tiff import read_tiff, read_tiff_georef
-    arr = read_tiff(image_path)
-    geo = read_tiff_georef(image_path)
-    bands = []
-    for i in range(arr.shape[0]):
-        b = arr[i] if arr.dtype == np.uint8 and geo["nodata"] is None else arr[i].astype(np.float32)
-        if geo["nodata"] is not None:
-            b[b == geo["nodata"]] = np.nan
-        bands.append(b)
-    h, w = arr.shape[1:]
-    fd, hier = run_feature_extraction_stage(bands, preprocessing=preprocessing, ctx=ctx)
+    ROI mask (.npy / .tif) — the accuracy assessment of that class map (scripts/4) into <output_dir>/evaluation_results.
+    raw: the image is a raw DN raster: stage 1 (scripts/1) runs first on the device and writes the reference's product,
+    <output_dir>/preprocessed/<stem>_preprocessed.tif, and its uint8 planes go to the feature stage without leaving HBM."""
+    if raw:
+        from .preprocess import run_preprocessing_stage
+        pdir = os.path.join(output_dir, "preprocessed")
+        stem = os.path.splitext(os.path.basename(image_path))[0]
+        ppath, dev, (h, w), geo = run_preprocessing_stage(image_path, os.path.join(pdir, f"{stem}_preprocessed.tif"), pdir, ctx=ctx,
+                                                          return_device=True)
+        fd, hier = _feature_extraction_on_device(ctx or default_context(), dev, h, w, preprocessing)
+    else:
+        from .tiff import read_tiff, read_tiff_georef
+        arr = read_tiff(image_path)
+        geo = read_tiff_georef(image_path)
+        bands = []
+        for i in range(arr.shape[0]):
+            b = arr[i] if arr.dtype == np.uint8 and geo["nodata"] is None else arr[i].astype(np.float32)
+            if geo["nodata"] is not None:
+                b[b == geo["nodata"]] = np.nan
+            bands.append(b)
+        h, w = arr.shape[1:]
+        fd, hier = run_feature_extraction_stage(bands, preprocessing=preprocessing, ctx=ctx)
     crs = None if geo["epsg"] is None else f"EPSG:{geo['epsg']}"
     fdir = os.path.join(output_dir, "feature_outputs")
     paths = save_feature_outputs(fdir, fd, hier, h, w, geo["transform"], crs)
     res: Dict[str, object] = {"paths": paths, "shape": (h, w)}
+    if raw:
+        res["preprocessed"] = ppath
     if classify:
         sdir = os.path.join(output_dir, "segmentation_results")
         res["class_map"] = run_classification_stage(paths["pkl"], classify, sdir, True, n_clusters=n_clusters, ctx=ctx)
@@ -317,7 +335,14 @@ def run_scripts_2_3(image_path: str, output_dir: str, classify: Optional[str] = 
     return res
 
 
-def main(argv=None) -> int:
+def parse_args(ap, argv=None):
+    a = ap.parse_args(argv)
+    if a.evaluate and not a.classify:
+        ap.error("--evaluate needs --classify")
+    return a
+
+
+def build_parser():
     import argparse
     ap = argparse.ArgumentParser(prog="python -m rsseg.stages",
                                  description="feature extraction (scripts/2) and optionally classification (scripts/3) of one GeoTIFF on the GPU")
@@ -327,10 +352,17 @@ def main(argv=None) -> int:
     ap.add_argument("--n-clusters", type=int, default=7)
     ap.add_argument("--no-preprocessing", action="store_true")
     ap.add_argument("--evaluate", metavar="ROI_MASK", help="accuracy assessment (scripts/4) of the class map against this ROI mask (.npy / .tif)")
-    a = ap.parse_args(argv)
-    if a.evaluate and not a.classify:
-        ap.error("--evaluate needs --classify")
-    res = run_scripts_2_3(a.image, a.output_dir, a.classify, not a.no_preprocessing, a.n_clusters, evaluate=a.evaluate)
+    ap.add_argument("--raw", action="store_true",
+                    help="the image is a raw DN raster: run stage 1 (scripts/1) on the GPU first, writing OUTPUT_DIR/preprocessed/<stem>_preprocessed.tif")
+    return ap
+
+
+def main(argv=None) -> int:
+    ap = build_parser()
+    a = parse_args(ap, argv)
+    res = run_scripts_2_3(a.image, a.output_dir, a.classify, not a.no_preprocessing, a.n_clusters, evaluate=a.evaluate, raw=a.raw)
+    if a.raw:
+        print(f"preprocessed: {res['preprocessed']}")
     for k, v in res["paths"].items():
         print(f"{k}: {v}")
     if a.classify:
