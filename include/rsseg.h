@@ -346,6 +346,30 @@ int rsseg_forest_load(rsseg_ctx *ctx, int n_trees, const int64_t *tree_off, cons
  * (modules/features/extract.py:690-719): d_planes[F] float32 feature planes -> int64 class per pixel. */
 int rsseg_forest_predict(rsseg_ctx *ctx, const float *const *d_planes, int F, int64_t n, int64_t *d_out);
 
+/* ---- K16: random-forest training ------------------------------------------------------------ */
+/* RandomForestClassifier(criterion='gini', splitter='best').fit of scikit-learn 1.7.2 on float32 features, tree for tree
+ * and bit for bit: the depth-first builder (tree/_tree.pyx:141-333) with node_split_best (tree/_splitter.pyx:269-545), the
+ * splitter's xorshift feature draws, the float32 FEATURE_THRESHOLD rules and the Gini proxy over integer class counts.
+ * d_planes[F] (host array of device pointers): n float32 values each, the layout K11 reads; d_y: n class indices 0..C-1;
+ * d_counts: int32 bootstrap counts, n per tree (tree t at t * n), or one row shared by every tree when same_counts != 0
+ * (bootstrap=False: all ones); seeds[n_trees]: each splitter's initial xorshift state (RandomState(seed).randint(0, 2^31-1));
+ * max_depth (2^31-1 for None), min_samples_split, min_samples_leaf, max_features: resolved as tree/_classes.py:320-348 does.
+ * node_off[n_trees+1] (host): node offsets with node_off[t+1] - node_off[t] = 2 m_t - 1, m_t = samples of tree t with a
+ * non-zero count (the most nodes a tree can have).  Per node (device arrays of node_off[n_trees] records, tree-local ids in
+ * sklearn's preorder): left / right child (-1 leaf), feature (-2 leaf), threshold (-2.0 leaf), impurity, n_node_samples,
+ * the integer weighted_n_node_samples, missing_go_to_left, and value[node][C] = count_c / weighted_n_node_samples.
+ * node_count[n_trees], max_depth_out[n_trees] (host): nodes built and deepest depth per tree.
+ * Limits: F <= 64 and C <= 64 (else RSSEG_ERR_UNSUPPORTED), 1 <= n < 2^26 (every sum of squared counts stays exact in
+ * double).  One workgroup per tree; each launch builds at most 2048 nodes per tree and the call issues continuation
+ * launches (one host wait each) until every tree is done; a launch without progress, or more launches than the node
+ * bound allows, is an error.  Synchronous.  Profiler name "forest_fit". */
+int rsseg_forest_fit(rsseg_ctx *ctx, const float *const *d_planes, int F, int64_t n, const int32_t *d_y, int n_classes,
+                     const int32_t *d_counts, int same_counts, int n_trees, const uint32_t *seeds, int max_depth,
+                     int min_samples_split, int min_samples_leaf, int max_features, const int64_t *node_off,
+                     int32_t *d_left, int32_t *d_right, int32_t *d_feature, double *d_threshold, double *d_impurity,
+                     int32_t *d_n_node, int32_t *d_w_node, uint8_t *d_missing_left, double *d_value,
+                     int64_t *node_count, int32_t *max_depth_out);
+
 /* ---- K12: rule-based classification --------------------------------------- */
 /* threshold_segmentation (modules/features/extract.py:344-404, otsu=False): NaN counts as 0, then d_out = 1 where
  * lo < x < hi, else 0 (pass -INFINITY / INFINITY for `x > t` / `x < t`). */

@@ -359,8 +359,9 @@ def rule_based_classification(features):
 
 
 # --------------------------------------------------------------------------------------------------
-# forest training helpers (reference extract.py:585-687): host-side scikit-learn, as in the reference — fitting is not
-# on the accelerated path; inference with the fitted model is (supervised_classification_predict above)
+# forest training helpers (reference extract.py:585-687).  The fit runs on the GPU (K16, rsseg.forest_fit): the same
+# trees scikit-learn grows, bit for bit, so the cached model and every printed metric are unchanged.  A training matrix
+# K16 cannot take (NaN, more than 64 features or classes, ...) is fitted by scikit-learn on the host instead.
 # --------------------------------------------------------------------------------------------------
 def prepare_training_samples(feature_array, labeled_roi_path):
     """extract.py:585-633: rows of the (H, W, F) stack under the non-zero pixels of a single-band label raster
@@ -385,6 +386,16 @@ def prepare_training_samples(feature_array, labeled_roi_path):
     return X, flat[keep]
 
 
+def _fit_forest(clf, X, y):
+    """clf.fit(X, y) through K16 (rsseg.forest_fit.fit); scikit-learn on the host when K16 refuses the input."""
+    from rsseg.forest_fit import fit
+    from rsseg.runtime import RssegUnsupported
+    try:
+        return fit(clf, X, y)
+    except RssegUnsupported:
+        return clf.fit(X, y)
+
+
 def train_random_forest_classifier(X_train, y_train, feature_names_for_training, n_estimators=100, test_size=0.3, random_state=42):
     """extract.py:635-687: stratified 70 / 30 split (when every class has two samples), RandomForestClassifier(n_estimators,
     random_state, n_jobs=-1).fit, validation accuracy / kappa / importances printed.  Returns the fitted classifier."""
@@ -400,7 +411,7 @@ def train_random_forest_classifier(X_train, y_train, feature_names_for_training,
     if X_t.shape[0] == 0:
         raise ValueError("没有足够的训练样本进行分割。")
     clf = RandomForestClassifier(n_estimators=n_estimators, random_state=random_state, n_jobs=-1)
-    clf.fit(X_t, y_t)
+    _fit_forest(clf, X_t, y_t)
     if X_val.shape[0] == 0:
         print("警告: 验证样本数为0，跳过验证评估。")
         return clf

@@ -115,6 +115,9 @@ SIGNATURES = {
                                  C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint8),
                                  C.POINTER(C.c_double), _int, C.POINTER(_i64), _int]),
     "rsseg_forest_predict": (_int, [_vp, _PP, _int, _i64, _vp]),
+    "rsseg_forest_fit": (_int, [_vp, _PP, _int, _i64, _vp, _int, _vp, _int, _int, C.POINTER(C.c_uint32), _int, _int, _int, _int,
+                                C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64),
+                                C.POINTER(C.c_int32)]),
     "rsseg_threshold_band_f32": (_int, [_vp, _vp, _i64, C.c_float, C.c_float, _vp]),
     "rsseg_band_interval_f32": (_int, [_vp, _vp, _i64, C.c_float, C.c_float, _int, _vp]),
     "rsseg_band_interval_f64": (_int, [_vp, _vp, _i64, C.c_double, C.c_double, _int, _vp]),

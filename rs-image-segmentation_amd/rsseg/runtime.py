@@ -735,6 +735,49 @@ class Context:
         self._chk(self.lib.rsseg_forest_predict(self.h, self._pp(planes), len(planes), n, C.c_void_p(out.data_ptr())))
         return out
 
+    # ---- K16 -----------------------------------------------------------------------------------
+    def forest_fit(self, planes: Sequence, y, counts, seeds: np.ndarray, node_caps: np.ndarray, max_depth: int,
+                   min_samples_split: int, min_samples_leaf: int, max_features: int, n_classes: int) -> List[dict]:
+        """rsseg_forest_fit: grows one tree per entry of `seeds` on the device.  planes: F float32 device planes of n samples;
+        y: int32 device class indices; counts: int32 device bootstrap counts, (n_trees * n) or one shared row of n;
+        node_caps[t] = 2 m_t - 1 (m_t = samples of tree t with a non-zero count).  Returns per tree a dict of NumPy arrays
+        (left, right, feature, threshold, impurity, n_node_samples, weighted_n_node_samples, missing_go_to_left, value of
+        shape (nodes, C)) and the tree's max_depth."""
+        torch = _torch()
+        T, n = len(seeds), planes[0].numel()
+        off = np.zeros(T + 1, np.int64)
+        off[1:] = np.cumsum(np.asarray(node_caps, np.int64))
+        total = int(off[-1])
+        i32 = lambda k=1: self.empty(total * k, torch.int32)   # noqa: E731
+        left, right, feat, n_node, w_node = i32(), i32(), i32(), i32(), i32()
+        thr, imp = self.empty(total, torch.float64), self.empty(total, torch.float64)
+        miss = self.empty(total, torch.uint8)
+        value = self.empty(total * n_classes, torch.float64)
+        same = counts.numel() == n
+        seeds = np.ascontiguousarray(seeds, np.uint32)
+        nc = np.zeros(T, np.int64)
+        md = np.zeros(T, np.int32)
+        vp = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+        self._chk(self.lib.rsseg_forest_fit(self.h, self._pp(planes), len(planes), n, vp(y), int(n_classes), vp(counts), int(same), T,
+                                            seeds.ctypes.data_as(C.POINTER(C.c_uint32)), int(max_depth), int(min_samples_split),
+                                            int(min_samples_leaf), int(max_features), off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            vp(left), vp(right), vp(feat), vp(thr), vp(imp), vp(n_node), vp(w_node), vp(miss), vp(value),
+                                            nc.ctypes.data_as(C.POINTER(C.c_int64)), md.ctypes.data_as(C.POINTER(C.c_int32))))
+        # copy back only the nodes that were built
+        keep = np.concatenate([np.arange(off[t], off[t] + nc[t]) for t in range(T)]) if T else np.zeros(0, np.int64)
+        idx = torch.from_numpy(keep).to(self.device)
+        host = {k: v.index_select(0, idx).cpu().numpy() for k, v in
+                (("left", left), ("right", right), ("feature", feat), ("threshold", thr), ("impurity", imp),
+                 ("n_node_samples", n_node), ("weighted_n_node_samples", w_node), ("missing_go_to_left", miss))}
+        host["value"] = value.view(total, n_classes).index_select(0, idx).cpu().numpy()
+        trees, pos = [], 0
+        for t in range(T):
+            k = int(nc[t])
+            trees.append({key: a[pos:pos + k] for key, a in host.items()})
+            trees[-1]["max_depth"] = int(md[t])
+            pos += k
+        return trees
+
     # ---- K14 -----------------------------------------------------------------------------------
     def confusion_counts(self, truth, pred, known_range: Optional[Sequence[int]] = None):
         """rsseg_confusion_counts: the joint count table of (truth, pred) over the pixels where truth > 0.  truth, pred: device

@@ -165,9 +165,9 @@ def run_classification_stage(feature_file_path, method='rule_based', output_dir=
       'random_forest'  scripts/3:401-488, inference part: the feature array is 'hierarchical_all' (also under stage 2's key
                        'hierarchical_features_all') when `use_hierarchical_all`, else every 2-D plane of the image's shape
                        stacked (:425-437); the classifier is `classifier` when given, else <output_dir>/random_forest_model.joblib
-                       when it exists and its n_features_in_ matches (:459-475); otherwise the forest is fitted on the host from
-                       `labeled_roi_file` (prepare_training_samples + train_random_forest_classifier, :450-475, scikit-learn as in
-                       the reference) and cached as that joblib file.  Without a model and without the label raster the stage
+                       when it exists and its n_features_in_ matches (:459-475); otherwise the forest is fitted from
+                       `labeled_roi_file` (prepare_training_samples + train_random_forest_classifier, :450-475: K16 on the GPU,
+                       the same trees scikit-learn grows) and cached as that joblib file.  Without a model and without the label raster the stage
                        reports that and returns None (the reference insists on the label raster even when the cache exists, :405-409).
 
     Writes <output_dir>/classification_<method>.npy and, when the feature file carries transform / crs / width / height
