@@ -268,12 +268,18 @@ def variance_feature(band: np.ndarray, scale: int) -> np.ndarray:
     return var
 
 
-def laplacian_feature(band: np.ndarray) -> np.ndarray:
-    """calculate_filter_responses -> 'laplacian' (indices.py:472-474): cv2.Laplacian(u8, CV_32F) (aperture 1: the cross
-    stencil [0 1 0; 1 -4 1; 0 1 0], BORDER_REFLECT_101) / 255.0, min-max normalised, float32 throughout."""
-    u8 = to_u8(robust_normalize(band)).astype(np.int32)
+def laplacian_u8(u8: np.ndarray) -> np.ndarray:
+    """cv2.Laplacian(u8, CV_32F) (aperture 1: the cross stencil [0 1 0; 1 -4 1; 0 1 0], BORDER_REFLECT_101) / 255.0 of a
+    uint8 plane: float32, not normalised."""
+    u8 = u8.astype(np.int32)
     p = np.pad(u8, 1, mode="reflect")
-    lap = (p[:-2, 1:-1] + p[2:, 1:-1] + p[1:-1, :-2] + p[1:-1, 2:] - 4 * u8).astype(np.float32) / np.float32(255.0)
+    return (p[:-2, 1:-1] + p[2:, 1:-1] + p[1:-1, :-2] + p[1:-1, 2:] - 4 * u8).astype(np.float32) / np.float32(255.0)
+
+
+def laplacian_feature(band: np.ndarray) -> np.ndarray:
+    """calculate_filter_responses -> 'laplacian' (indices.py:472-474): laplacian_u8 of the 8-bit band, min-max normalised,
+    float32 throughout."""
+    lap = laplacian_u8(to_u8(robust_normalize(band)))
     mn, mx = lap.min(), lap.max()
     den = np.float32(np.float32(mx - mn) + np.float32(1e-10))
     return ((lap - mn) / den).astype(np.float32)
@@ -295,11 +301,10 @@ def std_dev_feature(band: np.ndarray, scale: int = 5) -> np.ndarray:
     return np.sqrt(var)
 
 
-def sobel_mag_feature(band: np.ndarray) -> np.ndarray:
-    """calculate_filter_responses -> 'sobel_mag' (indices.py:455-458, 477-480).  cv2.Sobel(u8, CV_32F,
-    1, 0) / (0, 1): 3x3 kernels [-1 0 1]x[1 2 1]^T, BORDER_REFLECT_101; integer-valued, exact."""
-    b = robust_normalize(band)
-    u = to_u8(b).astype(np.float32)
+def sobel_mag_u8(u8: np.ndarray) -> np.ndarray:
+    """sqrt(sx^2 + sy^2) of cv2.Sobel(u8, CV_32F, 1, 0) / 255 and (0, 1) / 255: 3x3 kernels [-1 0 1]x[1 2 1]^T,
+    BORDER_REFLECT_101; integer-valued gradients, exact.  float32, not normalised."""
+    u = u8.astype(np.float32)
     p = np.pad(u, 1, mode="reflect")
     H, W = u.shape
     def at(dy, dx):
@@ -308,7 +313,13 @@ def sobel_mag_feature(band: np.ndarray) -> np.ndarray:
     gy = (at(1, -1) - at(-1, -1)) + 2 * (at(1, 0) - at(-1, 0)) + (at(1, 1) - at(-1, 1))
     sx = gx / 255.0
     sy = gy / 255.0
-    mag = np.sqrt(sx ** 2 + sy ** 2)
+    return np.sqrt(sx ** 2 + sy ** 2)
+
+
+def sobel_mag_feature(band: np.ndarray) -> np.ndarray:
+    """calculate_filter_responses -> 'sobel_mag' (indices.py:455-458, 477-480): sobel_mag_u8 of the 8-bit band over its
+    maximum."""
+    mag = sobel_mag_u8(to_u8(robust_normalize(band)))
     return mag / (mag.max() + 1e-10)
 
 
