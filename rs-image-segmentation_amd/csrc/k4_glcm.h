@@ -19,6 +19,21 @@ __device__ __forceinline__ double glcm_corr(long long np, long long M1, long lon
     return den == 0 ? 1.0 : (double)num / (double)den;
 }
 
+// The register kernels (one window of WIN <= 7 per finish, grey levels < LV <= 64) take the same integers in 32 bits: with
+// np <= WIN (WIN - 1) pairs per angle, M1 <= 2 np (LV - 1), and M2 * 2 np, Mx * 2 np <= 2 np (LV - 1)^2 * 2 np = the bound
+// on M1^2; the contrast / dissimilarity numerators S * nb + S' * na <= 4 na nb (LV - 1)^2 are below it too.  WIN = 7,
+// LV = 64: 28 005 264 < 2^25, so every product and difference below is exact in int and converts with one v_cvt_f64_i32.
+template <int WIN, int LV> constexpr bool glcm_fits_int32()
+{
+    const long long m1 = 2ll * WIN * (WIN - 1) * (LV - 1);
+    return m1 * m1 < (1ll << 31);
+}
+__device__ __forceinline__ double glcm_corr32(int np, int M1, int M2, int Mx)
+{
+    const int den = M2 * (2 * np) - M1 * M1, num = Mx * (2 * np) - M1 * M1;
+    return den == 0 ? 1.0 : (double)num / (double)den;
+}
+
 // group sums: g0 = angles 0 and 90 degrees (na pairs each), g1 = 45 and 135 degrees (nb pairs each)
 struct glcm_group {
     long long S1, S2, Hq;
@@ -84,32 +99,48 @@ static inline bool glcm_make_consts(int win, glcm_consts &gc)
     return true;
 }
 
-// the finish with the two groups' homogeneity sums (2^-52 fixed point) already converted to double
-__device__ __forceinline__ void glcm_finish_hq(const glcm_group &g0, const glcm_group &g1, double hq0, double hq1, long long na,
-                                               long long nb, double r0, double r1, double r2, double r3, size_t o,
-                                               const glcm_out &out, const glcm_consts &gc)
+// the float64 part of the finish: num_c / num_d are the exact contrast and dissimilarity numerators S * nb + S' * na,
+// hq0 / hq1 the two groups' homogeneity sums (2^-52 fixed point), sq0 / sq1 their sqrt(A_a) + sqrt(A_b)
+__device__ __forceinline__ void glcm_finish_f64(double num_c, double num_d, double hq0, double hq1, double sq0, double sq1, double dna,
+                                                double dnb, double r0, double r1, double r2, double r3, size_t o, const glcm_out &out,
+                                                const glcm_consts &gc)
 {
-    const double dna = (double)na, dnb = (double)nb;
-    if (out.p[0]) out.p[0][o] = (float)div_const((double)(g0.S2 * nb + g1.S2 * na), gc.den4, gc.rden4);
-    if (out.p[1]) out.p[1][o] = (float)div_const((double)(g0.S1 * nb + g1.S1 * na), gc.den4, gc.rden4);
+    if (out.p[0]) out.p[0][o] = (float)div_const(num_c, gc.den4, gc.rden4);
+    if (out.p[1]) out.p[1][o] = (float)div_const(num_d, gc.den4, gc.rden4);
     if (out.p[2]) {
         const double t1 = hq1 * dna;
         const double num = fma(hq0, dnb, t1);
         out.p[2][o] = (float)(div_const(num, gc.den4, gc.rden4) * (1.0 / 4503599627370496.0));
     }
     if (out.p[3]) {
-        const double t1 = g1.sq * dna;
-        const double num = fma(g0.sq, dnb, t1);
+        const double t1 = sq1 * dna;
+        const double num = fma(sq0, dnb, t1);
         out.p[3][o] = (float)div_const(num, gc.den8, gc.rden8);
     }
     if (out.p[4]) out.p[4][o] = (float)((((r0 + r1) + r2) + r3) * 0.25);
 }
 
-// the register kernels' windows (WIN <= 7) keep their homogeneity sums in int64: at most 84 terms of 2^52
-__device__ __forceinline__ void glcm_finish(const glcm_group &g0, const glcm_group &g1, long long na, long long nb, double r0,
-                                            double r1, double r2, double r3, size_t o, const glcm_out &out, const glcm_consts &gc)
+// the finish with the two groups' homogeneity sums (2^-52 fixed point) already converted to double
+__device__ __forceinline__ void glcm_finish_hq(const glcm_group &g0, const glcm_group &g1, double hq0, double hq1, long long na,
+                                               long long nb, double r0, double r1, double r2, double r3, size_t o,
+                                               const glcm_out &out, const glcm_consts &gc)
 {
-    glcm_finish_hq(g0, g1, (double)g0.Hq, (double)g1.Hq, na, nb, r0, r1, r2, r3, o, out, gc);
+    glcm_finish_f64((double)(g0.S2 * nb + g1.S2 * na), (double)(g0.S1 * nb + g1.S1 * na), hq0, hq1, g0.sq, g1.sq, (double)na, (double)nb,
+                    r0, r1, r2, r3, o, out, gc);
+}
+
+// the register kernels' windows (glcm_fits_int32): S1 / S2 and the numerators in int; the homogeneity sums stay in int64
+// (at most 84 terms of 2^52)
+struct glcm_group32 {
+    int S1, S2;
+    long long Hq;
+    double sq;
+};
+__device__ __forceinline__ void glcm_finish32(const glcm_group32 &g0, const glcm_group32 &g1, int na, int nb, double r0, double r1,
+                                              double r2, double r3, size_t o, const glcm_out &out, const glcm_consts &gc)
+{
+    glcm_finish_f64((double)(g0.S2 * nb + g1.S2 * na), (double)(g0.S1 * nb + g1.S1 * na), (double)g0.Hq, (double)g1.Hq, g0.sq, g1.sq,
+                    (double)na, (double)nb, r0, r1, r2, r3, o, out, gc);
 }
 
 // the launcher of k4_glcm_offsets.hip: `offsets` holds n (dr, dc) entries; def = the four default angles at distance 1,

@@ -31,6 +31,13 @@
 
 __constant__ long long c_glcm_hq[256];
 __device__ long long g_glcm_hq2[1024];  // pair sums hq[dA] + hq[dB] at [dB * 32 + dA] (levels <= 32)
+// sqrt((double)(2 i)) for every energy sum A = 2 (np + D) + 4 E2 a 7 x 7 window can have: A / 2 = np + D + 2 E2 with np <= 42,
+// D <= np and E2 <= 2 * np (np - 1) / 2 (one run of 42 equal keys on the diagonal, weight 2: the constant window, A = 84^2), so
+// i <= 42 + 42 + 2 * 1722 = 3528.  Filled on the device by k4_glcm_sqrt_fill with the sqrt the kernels call; padded to a whole
+// number of 16-byte pieces per thread of a workgroup, so that the copy into LDS needs no bounds test.
+#define GLCM_SQRT_N 3584
+static_assert(42 + 42 + 2 * (2 * (42 * 41 / 2)) < GLCM_SQRT_N && GLCM_SQRT_N % 512 == 0, "sqrt table too short for window 7");
+__device__ __attribute__((aligned(16))) double g_glcm_sqrt[GLCM_SQRT_N];
 
 static const int H_DR[4] = {0, 1, 1, 1};
 static const int H_DC[4] = {1, 1, 0, -1};
@@ -382,21 +389,22 @@ __global__ __launch_bounds__(256) void k4_glcm_thread(const uint8_t *__restrict_
     opaque_window<WIN>(w);
     unsigned m1[4], m2[4];
     window_m1m2<WIN>(w, m1, m2);
-    constexpr long long NA = (long long)WIN * (WIN - 1), NB = (long long)(WIN - 1) * (WIN - 1);
-    const long long xy0 = q0.XYa >> (2 * SH), xy90 = q0.XYb >> (2 * SH), xy45 = q1.XYa >> (2 * SH), xy135 = q1.XYb >> (2 * SH);
-    const long long M20 = m2[0] >> (2 * SH), M245 = m2[1] >> (2 * SH), M290 = m2[2] >> (2 * SH), M2135 = m2[3] >> (2 * SH);
-    glcm_group g0, g1;
+    static_assert(WIN <= 7 && SH >= 2 && glcm_fits_int32<WIN, (256 >> SH)>(), "the 32-bit finish needs (2 np (levels - 1))^2 < 2^31");
+    constexpr int NA = WIN * (WIN - 1), NB = (WIN - 1) * (WIN - 1);
+    const int xy0 = q0.XYa >> (2 * SH), xy90 = q0.XYb >> (2 * SH), xy45 = q1.XYa >> (2 * SH), xy135 = q1.XYb >> (2 * SH);
+    const int M20 = m2[0] >> (2 * SH), M245 = m2[1] >> (2 * SH), M290 = m2[2] >> (2 * SH), M2135 = m2[3] >> (2 * SH);
+    glcm_group32 g0, g1;
     g0.S1 = q0.S1 >> SH;
-    g0.S2 = (M20 - 2ll * xy0) + (M290 - 2ll * xy90);
+    g0.S2 = (M20 - 2 * xy0) + (M290 - 2 * xy90);
     g0.Hq = q0.Hq;
     g0.sq = q0.sq;
     g1.S1 = q1.S1 >> SH;
-    g1.S2 = (M245 - 2ll * xy45) + (M2135 - 2ll * xy135);
+    g1.S2 = (M245 - 2 * xy45) + (M2135 - 2 * xy135);
     g1.Hq = q1.Hq;
     g1.sq = q1.sq;
-    const double r0 = glcm_corr(NA, m1[0] >> SH, M20, 2ll * xy0), r1 = glcm_corr(NB, m1[1] >> SH, M245, 2ll * xy45);
-    const double r2 = glcm_corr(NA, m1[2] >> SH, M290, 2ll * xy90), r3 = glcm_corr(NB, m1[3] >> SH, M2135, 2ll * xy135);
-    glcm_finish(g0, g1, NA, NB, r0, r1, r2, r3, (size_t)oy * ow + ox, out, gc);
+    const double r0 = glcm_corr32(NA, m1[0] >> SH, M20, 2 * xy0), r1 = glcm_corr32(NB, m1[1] >> SH, M245, 2 * xy45);
+    const double r2 = glcm_corr32(NA, m1[2] >> SH, M290, 2 * xy90), r3 = glcm_corr32(NB, m1[3] >> SH, M2135, 2 * xy135);
+    glcm_finish32(g0, g1, NA, NB, r0, r1, r2, r3, (size_t)oy * ow + ox, out, gc);
 }
 
 
@@ -623,33 +631,44 @@ __device__ __forceinline__ void gp_group(const unsigned (&P)[8][2], const long l
     window(std::integral_constant<int, 2>{}, KB, HqB, sqB);
 }
 
+// the float64 finish of one 7 x 7 window of the dense kernels from its pair moments (still pre-scaled: S1 / m1 by 2^SH, XY / m2
+// by 2^2SH; XY in the order 0, 90, 45, 135 degrees, m1 / m2 in the order 0, 45, 90, 135)
+__device__ __forceinline__ void gp_finish_stats(unsigned S1g0, unsigned S1g1, const unsigned (&XY)[4], const unsigned (&m1)[4],
+                                                const unsigned (&m2)[4], long long Hq0, double sq0, long long Hq1, double sq1, size_t o,
+                                                const glcm_out &out, const glcm_consts &gc)
+{
+    constexpr int WIN = 7, SH = 3;
+    static_assert(glcm_fits_int32<WIN, (256 >> SH)>(), "the 32-bit finish needs (2 np (levels - 1))^2 < 2^31");
+    constexpr int NA = WIN * (WIN - 1), NB = (WIN - 1) * (WIN - 1);
+    const int xy0 = XY[0] >> (2 * SH), xy90 = XY[1] >> (2 * SH), xy45 = XY[2] >> (2 * SH), xy135 = XY[3] >> (2 * SH);
+    const int M20 = m2[0] >> (2 * SH), M245 = m2[1] >> (2 * SH), M290 = m2[2] >> (2 * SH), M2135 = m2[3] >> (2 * SH);
+    glcm_group32 g0, g1;
+    g0.S1 = S1g0 >> SH;
+    g0.S2 = (M20 - 2 * xy0) + (M290 - 2 * xy90);
+    g0.Hq = Hq0;
+    g0.sq = sq0;
+    g1.S1 = S1g1 >> SH;
+    g1.S2 = (M245 - 2 * xy45) + (M2135 - 2 * xy135);
+    g1.Hq = Hq1;
+    g1.sq = sq1;
+    const double r0 = glcm_corr32(NA, m1[0] >> SH, M20, 2 * xy0), r1 = glcm_corr32(NB, m1[1] >> SH, M245, 2 * xy45);
+    const double r2 = glcm_corr32(NA, m1[2] >> SH, M290, 2 * xy90), r3 = glcm_corr32(NB, m1[3] >> SH, M2135, 2 * xy135);
+    glcm_finish32(g0, g1, NA, NB, r0, r1, r2, r3, o, out, gc);
+}
+
 // everything of one window that does not involve the key sort: pair moments, M1 / M2, the float64 finish
 __device__ __forceinline__ void gp_finish(unsigned (&w)[8][2], long long Hq0, double sq0, long long Hq1, double sq1, size_t o,
                                           const glcm_out &out, const glcm_consts &gc)
 {
-    constexpr int WIN = 7, SH = 3;
-    unsigned S1a, XYa, S1b, XYb, S1c, XYc, S1d, XYd;
-    row_moments<WIN, 0, 1>(w, S1a, XYa);
-    row_moments<WIN, 1, 0>(w, S1b, XYb);
-    row_moments<WIN, 1, 1>(w, S1c, XYc);
-    row_moments<WIN, 1, -1>(w, S1d, XYd);
+    constexpr int WIN = 7;
+    unsigned S1a, S1b, S1c, S1d, XY[4];
+    row_moments<WIN, 0, 1>(w, S1a, XY[0]);
+    row_moments<WIN, 1, 0>(w, S1b, XY[1]);
+    row_moments<WIN, 1, 1>(w, S1c, XY[2]);
+    row_moments<WIN, 1, -1>(w, S1d, XY[3]);
     unsigned m1[4], m2[4];
     window_m1m2<WIN>(w, m1, m2);
-    constexpr long long NA = (long long)WIN * (WIN - 1), NB = (long long)(WIN - 1) * (WIN - 1);
-    const long long xy0 = XYa >> (2 * SH), xy90 = XYb >> (2 * SH), xy45 = XYc >> (2 * SH), xy135 = XYd >> (2 * SH);
-    const long long M20 = m2[0] >> (2 * SH), M245 = m2[1] >> (2 * SH), M290 = m2[2] >> (2 * SH), M2135 = m2[3] >> (2 * SH);
-    glcm_group g0, g1;
-    g0.S1 = (S1a + S1b) >> SH;
-    g0.S2 = (M20 - 2ll * xy0) + (M290 - 2ll * xy90);
-    g0.Hq = Hq0;
-    g0.sq = sq0;
-    g1.S1 = (S1c + S1d) >> SH;
-    g1.S2 = (M245 - 2ll * xy45) + (M2135 - 2ll * xy135);
-    g1.Hq = Hq1;
-    g1.sq = sq1;
-    const double r0 = glcm_corr(NA, m1[0] >> SH, M20, 2ll * xy0), r1 = glcm_corr(NB, m1[1] >> SH, M245, 2ll * xy45);
-    const double r2 = glcm_corr(NA, m1[2] >> SH, M290, 2ll * xy90), r3 = glcm_corr(NB, m1[3] >> SH, M2135, 2ll * xy135);
-    glcm_finish(g0, g1, NA, NB, r0, r1, r2, r3, o, out, gc);
+    gp_finish_stats(S1a + S1b, S1c + S1d, XY, m1, m2, Hq0, sq0, Hq1, sq1, o, out, gc);
 }
 
 __global__ __launch_bounds__(256) void k4_glcm_pair(const uint8_t *__restrict__ q, int H, int W, int oh, int ow, glcm_out out,
@@ -713,7 +732,10 @@ __global__ __launch_bounds__(256) void k4_glcm_pair(const uint8_t *__restrict__ 
 // pairs of the 0 / 90 degree angles, 25 of the 36 of 45 / 135), two of them a STRIP of 5 more, and each adds its OWN 7
 // (6): the core is built and sorted once per thread, core + strip merged once per two windows, and a window only sorts
 // its own keys and merges them in — per window 375 compare-exchanges instead of the pair kernel's 446 and 32 packed keys
-// built instead of 46.  The same integer statistics, the same float64 finish (gp_finish): bit-identical.
+// built instead of 46.  The same integer statistics, the same float64 finish (gp_finish_stats): bit-identical.
+//   Finish (r05).  The pair moments of the windows (dx, 0) and (dx, 1) come from per-row sums computed once per column
+//   alignment (gq_column_moments), the integer part of the finish runs in 32 bits (k4_glcm.h: glcm_fits_int32) and the four
+//   square roots of a window are read from a table of sqrt(2 i) in LDS (g_glcm_sqrt) instead of computed.
 //   Packing.  A register carries two angles (low / high half).  For 45 / 135 degrees both halves have the same geometry.
 //   For 0 / 90 degrees the geometry of one is the transpose of the other (0: row strips of 5, column strips of 7;
 //   90: column strips of 5, row strips of 7), so a register "slot" carries the 0-degree keys of one window and the
@@ -946,13 +968,117 @@ __device__ __forceinline__ void gq_group(const unsigned (&P)[8][2], const long l
     slot(std::integral_constant<int, 3>{}, KC);
 }
 
+// The pair moments of the two windows (dy = 0, 1) of one column alignment of the 8 x 8 patch: a[r] holds the 7 pixels of patch
+// row r that both windows see (byte 7 is zero).  The windows share rows 1..6 and row pairs 1..5, so every per-row quantity
+// is computed once over the 8 rows (7 row pairs) and a window adds row 0 or 7 (pair 0 or 6) to the shared part; the two
+// shifted forms of a row (bytes 0..5, bytes 1..6) serve the 0, 45 and 135 degree pairs alike.  All sums are exact unsigned
+// integers: the same values as row_moments / window_m1m2 give window by window.
+struct gq_moments {
+    unsigned S1g0, S1g1, XY[4], m1[4], m2[4];   // as gp_finish_stats takes them
+};
+__device__ __forceinline__ void gq_column_moments(const unsigned (&a)[8][2], gq_moments (&m)[2])
+{
+    auto sad2 = [](unsigned xl, unsigned xh, unsigned yl, unsigned yh, unsigned acc) {
+        return __builtin_amdgcn_sad_u8(xh, yh, __builtin_amdgcn_sad_u8(xl, yl, acc));
+    };
+    auto dot2 = [](unsigned xl, unsigned xh, unsigned yl, unsigned yh, unsigned acc) {
+        return __builtin_amdgcn_udot4(xh, yh, __builtin_amdgcn_udot4(xl, yl, acc, false), false);
+    };
+    unsigned Lh[8], Rl[8], Rh[8];    // L = bytes 0..5 (low word: a[r][0] itself), R = bytes 1..6 moved down one byte
+    static_for<8>([&](auto I) {
+        constexpr int r = I;
+        Lh[r] = a[r][1] & 0x0000ffffu;
+        Rl[r] = __builtin_amdgcn_alignbyte(a[r][1], a[r][0], 1);
+        Rh[r] = a[r][1] >> 8;
+    });
+    unsigned s0 = 0, s1 = 0, x0 = 0, x90 = 0, x45 = 0, x135 = 0;
+    static_for<6>([&](auto I) {      // 0 degrees: rows 1..6
+        constexpr int r = 1 + I;
+        s0 = sad2(a[r][0], Lh[r], Rl[r], Rh[r], s0);
+        x0 = dot2(a[r][0], Lh[r], Rl[r], Rh[r], x0);
+    });
+    static_for<5>([&](auto I) {      // 90, 45, 135 degrees: row pairs 1..5
+        constexpr int r = 1 + I;
+        s0 = sad2(a[r][0], a[r][1], a[r + 1][0], a[r + 1][1], s0);
+        x90 = dot2(a[r][0], a[r][1], a[r + 1][0], a[r + 1][1], x90);
+        s1 = sad2(a[r][0], Lh[r], Rl[r + 1], Rh[r + 1], s1);
+        x45 = dot2(a[r][0], Lh[r], Rl[r + 1], Rh[r + 1], x45);
+        s1 = sad2(Rl[r], Rh[r], a[r + 1][0], Lh[r + 1], s1);
+        x135 = dot2(Rl[r], Rh[r], a[r + 1][0], Lh[r + 1], x135);
+    });
+    // row totals and squares: rows 2..5 in one chain, rows 0, 1, 6, 7 each (first / last row of a window)
+    unsigned in_s = 0, in_q = 0;
+    static_for<4>([&](auto I) {
+        constexpr int r = 2 + I;
+        in_s = sad2(a[r][0], a[r][1], 0u, 0u, in_s);
+        in_q = dot2(a[r][0], a[r][1], a[r][0], a[r][1], in_q);
+    });
+    const unsigned rs0 = sad2(a[0][0], a[0][1], 0u, 0u, 0u), rs1 = sad2(a[1][0], a[1][1], 0u, 0u, 0u);
+    const unsigned rs6 = sad2(a[6][0], a[6][1], 0u, 0u, 0u), rs7 = sad2(a[7][0], a[7][1], 0u, 0u, 0u);
+    const unsigned rq0 = dot2(a[0][0], a[0][1], a[0][0], a[0][1], 0u), rq1 = dot2(a[1][0], a[1][1], a[1][0], a[1][1], 0u);
+    const unsigned rq6 = dot2(a[6][0], a[6][1], a[6][0], a[6][1], 0u), rq7 = dot2(a[7][0], a[7][1], a[7][0], a[7][1], 0u);
+    const unsigned mid_s = in_s + rs1 + rs6, mid_q = in_q + rq1 + rq6;
+    // columns 0 and 6 over the 8 rows (rows 0..3, rows 4..7); a window leaves out row 7 or row 0
+    auto column = [&](auto k_t, unsigned sel, unsigned &lo, unsigned &hi) {
+        constexpr int k = decltype(k_t)::value;
+        const unsigned p01 = __builtin_amdgcn_perm(a[1][k], a[0][k], sel), p23 = __builtin_amdgcn_perm(a[3][k], a[2][k], sel);
+        const unsigned p45 = __builtin_amdgcn_perm(a[5][k], a[4][k], sel), p67 = __builtin_amdgcn_perm(a[7][k], a[6][k], sel);
+        lo = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
+        hi = __builtin_amdgcn_perm(p67, p45, 0x05040100u);
+    };
+    unsigned c0lo, c0hi, c6lo, c6hi;
+    column(std::integral_constant<int, 0>{}, 0x0c0c0400u, c0lo, c0hi);   // byte 0 of the low words
+    column(std::integral_constant<int, 1>{}, 0x0c0c0602u, c6lo, c6hi);   // byte 2 of the high words
+    const unsigned Call = sad2(c0lo, c0hi, 0u, 0u, sad2(c6lo, c6hi, 0u, 0u, 0u));
+    const unsigned Cqall = dot2(c0lo, c0hi, c0lo, c0hi, dot2(c6lo, c6hi, c6lo, c6hi, 0u));
+    static_for<2>([&](auto DY) {
+        constexpr int dy = DY, f = dy, l = 6 + dy, x = dy == 0 ? 7 : 0;   // first and last row of the window, the row it leaves out
+        constexpr int p = 6 * dy, r = 7 * dy;                             // its own row pair, its own row
+        gq_moments &w = m[dy];
+        w.S1g0 = sad2(a[p][0], a[p][1], a[p + 1][0], a[p + 1][1], sad2(a[r][0], Lh[r], Rl[r], Rh[r], s0));
+        w.XY[0] = dot2(a[r][0], Lh[r], Rl[r], Rh[r], x0);
+        w.XY[1] = dot2(a[p][0], a[p][1], a[p + 1][0], a[p + 1][1], x90);
+        w.S1g1 = sad2(Rl[p], Rh[p], a[p + 1][0], Lh[p + 1], sad2(a[p][0], Lh[p], Rl[p + 1], Rh[p + 1], s1));
+        w.XY[2] = dot2(a[p][0], Lh[p], Rl[p + 1], Rh[p + 1], x45);
+        w.XY[3] = dot2(Rl[p], Rh[p], a[p + 1][0], Lh[p + 1], x135);
+        auto at = [&](unsigned lo, unsigned hi, int row) { return ((row < 4 ? lo : hi) >> (8 * (row & 3))) & 0xffu; };
+        const unsigned w00 = at(c0lo, c0hi, f), w0L = at(c6lo, c6hi, f), wL0 = at(c0lo, c0hi, l), wLL = at(c6lo, c6hi, l);
+        const unsigned e0 = at(c0lo, c0hi, x), e6 = at(c6lo, c6hi, x);
+        const unsigned T = mid_s + (dy == 0 ? rs0 : rs7), T2 = mid_q + (dy == 0 ? rq0 : rq7);
+        const unsigned R = dy == 0 ? rs0 + rs6 : rs1 + rs7, Rq = dy == 0 ? rq0 + rq6 : rq1 + rq7;
+        const unsigned C = Call - e0 - e6, Cq = Cqall - e0 * e0 - e6 * e6;
+        w.m1[0] = 2 * T - C;
+        w.m1[2] = 2 * T - R;
+        w.m1[1] = 2 * T - R - C + w00 + wLL;
+        w.m1[3] = 2 * T - R - C + w0L + wL0;
+        w.m2[0] = 2 * T2 - Cq;
+        w.m2[2] = 2 * T2 - Rq;
+        w.m2[1] = 2 * T2 - Rq - Cq + w00 * w00 + wLL * wLL;
+        w.m2[3] = 2 * T2 - Rq - Cq + w0L * w0L + wL0 * wL0;
+    });
+}
+
+__global__ __launch_bounds__(256) void k4_glcm_sqrt_fill()
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < GLCM_SQRT_N) g_glcm_sqrt[i] = sqrt((double)(2ll * i));
+}
+
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k4_glcm_quad(const uint8_t *__restrict__ q, int H, int W, int oh, int ow, glcm_out out,
                                                     glcm_consts gc)
 {
     constexpr int SH = 3;
     __shared__ long long hq2[1024];
     __shared__ long long hq1[32];
-    for (int i = threadIdx.x; i < 1024; i += 256) hq2[i] = g_glcm_hq2[i];
+    // the square roots of the energy sums come from a table (g_glcm_sqrt): four reads per window instead of four float64 sqrt
+    __shared__ __attribute__((aligned(16))) double sqt[GLCM_SQRT_N];
+    // unrolled and without a bounds test: the loads of the three tables are requested back to back, one memory round trip
+    // instead of one per piece
+#pragma unroll
+    for (int k = 0; k < GLCM_SQRT_N / 512; k++)
+        reinterpret_cast<double2 *>(sqt)[k * 256 + threadIdx.x] = reinterpret_cast<const double2 *>(g_glcm_sqrt)[k * 256 + threadIdx.x];
+#pragma unroll
+    for (int k = 0; k < 4; k++) hq2[k * 256 + threadIdx.x] = g_glcm_hq2[k * 256 + threadIdx.x];
     if (threadIdx.x < 32) hq1[threadIdx.x] = c_glcm_hq[threadIdx.x];
     __syncthreads();
     // The window coordinates are needed at the two ends of the kernel only.  Kept in vector registers they (or the thread id
@@ -1005,43 +1131,47 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     coords(ox, oy);
     hasX = ox + 1 < ow;
     hasY = oy + 1 < oh;
-    auto root_sum = [&](int pairs, unsigned ed_lo, unsigned ed_hi) {
-        const long long Aa = 2ll * (pairs + (int)(ed_lo & 0xffffu));
-        const long long Ab = 2ll * (pairs + (int)(ed_hi >> 16));
-        return sqrt((double)Aa) + sqrt((double)Ab);
+    auto root_sum = [&](int pairs, unsigned ed_lo, unsigned ed_hi) {   // sqrt(A_a) + sqrt(A_b), A = 2 (pairs + ED)
+        return sqt[pairs + (int)(ed_lo & 0xffffu)] + sqt[pairs + (int)(ed_hi >> 16)];
     };
+    // The windows (dx, 0) and (dx, 1) share their column alignment: one pass of the loop forms the pair moments of both from
+    // per-row sums computed once (gq_column_moments) and finishes them.  Window (dx, dy) is slot 2 dy + dx; its transpose
+    // partner's slot is 2 dx + dy.
     // RSSEG_GLCM_COUNT_UNROLL (profiles/valu_hist.sh only): the loop unrolled, so that the STATIC instruction histogram of the
-    // code object equals the executed one (the shipped kernel keeps the loop rolled: one copy of the finish)
+    // code object equals the executed one (the shipped kernel keeps the loop rolled: one copy of the finish); the shift is
+    // opaque so that the unrolled copies keep the instructions the rolled loop executes
 #ifdef RSSEG_GLCM_COUNT_UNROLL
 #pragma unroll
 #else
 #pragma nounroll
 #endif
-    for (int wdw = 0; wdw < 4; wdw++) {
-        const int dx = wdw & 1, dy = wdw >> 1;
-        if ((dx && !hasX) || (dy && !hasY)) continue;
-        const int part = wdw == 1 ? 2 : (wdw == 2 ? 1 : wdw);
-        unsigned e0l = 0, e0h = 0, e1 = 0;
-        long long h0 = 0, h1 = 0;
-        static_for<4>([&](auto I) {     // constant indices into the register arrays
-            constexpr int s = I;
-            if (wdw == s) { e0l = ED[0][s]; e1 = ED[1][s]; h0 = Hq[0][s]; h1 = Hq[1][s]; }
-            if (part == s) e0h = ED[0][s];
-        });
-        const double sq0 = root_sum(42, e0l, e0h), sq1 = root_sum(36, e1, e1);
-        unsigned w[8][2];
+    for (int dx = 0; dx < 2; dx++) {
+        if (dx && !hasX) continue;
+        int sh = 8 * dx;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+s"(sh));
+#endif
+        const bool odd = sh != 0;
+        unsigned a[8][2];
         opaque_patch<8>(P);
-        static_for<7>([&](auto I) {
+        static_for<8>([&](auto I) {     // patch columns dx .. dx + 6 of every row
             constexpr int r = I;
-            unsigned a0 = 0, a1 = 0;
-            static_for<2>([&](auto DY) {    // rows r + dy with a constant index
-                if (dy == DY) { a0 = P[r + DY][0]; a1 = P[r + DY][1]; }
-            });
-            w[r][0] = dx ? __builtin_amdgcn_alignbyte(a1, a0, 1) : a0;
-            w[r][1] = dx ? (a1 >> 8) : (a1 & 0x00ffffffu);
+            a[r][0] = __builtin_amdgcn_alignbit(P[r][1], P[r][0], (unsigned)sh);
+            a[r][1] = __builtin_amdgcn_ubfe(P[r][1], (unsigned)sh, 24u);
         });
-        w[7][0] = w[7][1] = 0;
-        gp_finish(w, h0, sq0, h1, sq1, (size_t)(oy + dy) * ow + (ox + dx), out, gc);
+        gq_moments mo[2];
+        gq_column_moments(a, mo);
+        static_for<2>([&](auto DY) {
+            constexpr int dy = DY;
+            if (dy == 0 || hasY) {
+                const unsigned e0l = odd ? ED[0][2 * dy + 1] : ED[0][2 * dy], e0h = odd ? ED[0][2 + dy] : ED[0][dy];
+                const unsigned e1 = odd ? ED[1][2 * dy + 1] : ED[1][2 * dy];
+                const long long h0 = odd ? Hq[0][2 * dy + 1] : Hq[0][2 * dy], h1 = odd ? Hq[1][2 * dy + 1] : Hq[1][2 * dy];
+                const double sq0 = root_sum(42, e0l, e0h), sq1 = root_sum(36, e1, e1);
+                gp_finish_stats(mo[dy].S1g0, mo[dy].S1g1, mo[dy].XY, mo[dy].m1, mo[dy].m2, h0, sq0, h1, sq1,
+                                (size_t)(oy + dy) * ow + (ox + dx), out, gc);
+            }
+        });
     }
 }
 
@@ -1201,6 +1331,10 @@ extern "C" int rsseg_glcm_u8(rsseg_ctx *ctx, const uint8_t *d_q, int H, int W, i
         long long lut2[1024];
         for (int i = 0; i < 1024; i++) lut2[i] = lut[i & 31] + lut[i >> 5];
         HIPCHK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_glcm_hq2), lut2, sizeof(lut2)));
+        // the table of square roots is the device's own sqrt; complete before any other context of this device reads it
+        hipLaunchKernelGGL(k4_glcm_sqrt_fill, dim3((GLCM_SQRT_N + 255) / 256), dim3(256), 0, ctx->stream);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         g_hq_ready[ctx->device & 63] = true;
     }
     hq_lock.unlock();
