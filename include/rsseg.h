@@ -352,7 +352,9 @@ int rsseg_forest_predict(rsseg_ctx *ctx, const float *const *d_planes, int F, in
  * splitter's xorshift feature draws, the float32 FEATURE_THRESHOLD rules and the Gini proxy over integer class counts.
  * d_planes[F] (host array of device pointers): n float32 values each, the layout K11 reads; d_y: n class indices 0..C-1;
  * d_counts: int32 bootstrap counts, n per tree (tree t at t * n), or one row shared by every tree when same_counts != 0
- * (bootstrap=False: all ones); seeds[n_trees]: each splitter's initial xorshift state (RandomState(seed).randint(0, 2^31-1));
+ * (bootstrap=False: all ones).  Every count row is non-negative and sums to n: weighted_n_samples is taken as n (n bootstrap
+ * draws, or n unit weights), and a row that does not is refused with RSSEG_ERR_INVALID ("do not sum to n") instead of growing
+ * subtly different trees; seeds[n_trees]: each splitter's initial xorshift state (RandomState(seed).randint(0, 2^31-1));
  * max_depth (2^31-1 for None), min_samples_split, min_samples_leaf, max_features: resolved as tree/_classes.py:320-348 does.
  * node_off[n_trees+1] (host): node offsets with node_off[t+1] - node_off[t] = 2 m_t - 1, m_t = samples of tree t with a
  * non-zero count (the most nodes a tree can have).  Per node (device arrays of node_off[n_trees] records, tree-local ids in

@@ -13,8 +13,9 @@
 // formed here from the same exact integers: sums of squares stay below 2^53 while the total weight is below 2^26.
 //
 // Bounds: a tree has at most 2m-1 nodes and its stack at most min(max_depth, m)+1 entries (m = samples with a non-zero
-// count); the host sizes both exactly and the kernel still checks them (err, never a truncated tree).  A launch builds at
-// most `budget` nodes per tree; the host issues continuation launches and stops when one makes no progress.
+// count); the host sizes both exactly and the kernel still checks them (err, never a truncated tree).  Every count row sums to
+// n: weighted_n_samples is taken as n, and k16_fit_init refuses a row that does not (err 5).  A launch builds at most
+// `budget` nodes per tree; the host issues continuation launches and stops when one makes no progress.
 #include <cfloat>
 
 #include "common.h"
@@ -324,16 +325,27 @@ __global__ void __launch_bounds__(FF_THREADS) k16_fit_init(const ff_args *__rest
     const ff_args &a = *pa;
     __shared__ int s_w[FF_WAVES];
     __shared__ int s_base;
+    __shared__ int s_neg;
+    __shared__ unsigned long long s_sum;
     const int t = blockIdx.x;
     if (t >= a.T) return;
     const int32_t *cnt = a.counts + (int64_t)t * a.count_stride;
     int32_t *smp = a.samples + a.samp_off[t];
     const int64_t m = a.samp_off[t + 1] - a.samp_off[t];
-    if (threadIdx.x == 0) s_base = 0;
+    if (threadIdx.x == 0) {
+        s_base = 0;
+        s_neg = 0;
+        s_sum = 0ull;
+    }
     __syncthreads();
+    long long wsum = 0;   // this thread's share of the row's total weight
+    int neg = 0;
     for (int64_t c0 = 0; c0 < a.n; c0 += FF_THREADS) {
         const int64_t i = c0 + threadIdx.x;
-        const int flag = (i < a.n && cnt[i] > 0) ? 1 : 0;
+        const int32_t ci = i < a.n ? cnt[i] : 0;
+        const int flag = ci > 0 ? 1 : 0;
+        wsum += ci;
+        neg |= ci < 0;
         int tot;
         const int off = block_excl_count(flag, s_w, &tot);
         const int64_t o = (int64_t)s_base + off;
@@ -342,9 +354,17 @@ __global__ void __launch_bounds__(FF_THREADS) k16_fit_init(const ff_args *__rest
         if (threadIdx.x == 0) s_base += tot;
         __syncthreads();
     }
+    // weighted_n_samples is taken as n (k16_fit_step: w_total), so a count row must be non-negative and sum to n
+    wsum = wave_sum(wsum);
+    neg = wave_sum(neg);
+    if (lane_id() == 0) {
+        atomicAdd(&s_sum, (unsigned long long)wsum);
+        if (neg) atomicOr(&s_neg, 1);
+    }
+    __syncthreads();
     if (threadIdx.x == 0) {
         ff_state *st = a.st + t;
-        st->err = s_base != m ? 1 : 0;
+        st->err = (s_neg || (long long)s_sum != (long long)a.n) ? 5 : s_base != m ? 1 : 0;
         st->node_count = 0;
         st->max_depth_seen = 0;
         st->rng = a.seeds[t];
@@ -700,6 +720,9 @@ extern "C" int rsseg_forest_fit(rsseg_ctx *ctx, const float *const *d_planes, in
         int64_t built = 0;
         bool all = true;
         for (int t = 0; t < n_trees; t++) {
+            if (h[t].err == 5)
+                return rs_fail(ctx, RSSEG_ERR_INVALID, "forest_fit: tree %d: the counts are negative or do not sum to n = %lld "
+                               "(weighted_n_samples is n)", t, (long long)n);
             if (h[t].err)
                 return rs_fail(ctx, RSSEG_ERR_NOMEM, "forest_fit: tree %d stopped with error %d after %d nodes (%s)", t, h[t].err, h[t].node_count,
                                h[t].err == 1 ? "sample count mismatch" : h[t].err == 2 ? "node storage full" : h[t].err == 3 ? "inconsistent partition" : "stack full");

@@ -739,7 +739,8 @@ class Context:
     def forest_fit(self, planes: Sequence, y, counts, seeds: np.ndarray, node_caps: np.ndarray, max_depth: int,
                    min_samples_split: int, min_samples_leaf: int, max_features: int, n_classes: int) -> List[dict]:
         """rsseg_forest_fit: grows one tree per entry of `seeds` on the device.  planes: F float32 device planes of n samples;
-        y: int32 device class indices; counts: int32 device bootstrap counts, (n_trees * n) or one shared row of n;
+        y: int32 device class indices; counts: int32 device bootstrap counts, (n_trees * n) or one shared row of n, every row
+        non-negative and summing to n (ValueError otherwise: weighted_n_samples is taken as n);
         node_caps[t] = 2 m_t - 1 (m_t = samples of tree t with a non-zero count).  Returns per tree a dict of NumPy arrays
         (left, right, feature, threshold, impurity, n_node_samples, weighted_n_node_samples, missing_go_to_left, value of
         shape (nodes, C)) and the tree's max_depth."""
