@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Texture kernel of the dense case (k4_glcm_quad: window 7, step 1, 32 levels) at 16384^2, two builds of the library against
-each other: the same quantised plane and the same HIP-event timers as profiles/r04_glcm_ab.py, each build in a process of
+each other (--dense pair: k4_glcm_pair on the same case; --step 7: k4_glcm_thread<7,3>, the same window at step 7): the same quantised plane and the same HIP-event timers as profiles/r04_glcm_ab.py, each build in a process of
 its own, alternating, several rounds; the five maps of every run are hashed, so the builds are also compared bit for bit.
 
-  driver:  python profiles/glcm_finish_ab.py --parent <parent librsseg_hip.so> [--new <librsseg_hip.so>] [--rounds 3] > out.json
+  driver:  python profiles/glcm_finish_ab.py --parent <parent librsseg_hip.so> [--new <librsseg_hip.so>] [--rounds 3]
+                                             [--dense {quad,pair}] [--step 7] > out.json
   worker:  python profiles/glcm_finish_ab.py --lib <librsseg_hip.so>            (one JSON line: ms per launch, map hashes)
 
 The gain counts if the slowest run of the new build is faster than the fastest run of the parent ("separated").  The
@@ -22,7 +23,14 @@ NEW_LIB = os.path.join(ROOT, "rs-image-segmentation_amd", "librsseg_hip.so")
 LAUNCHES = 5
 
 
-def worker(lib_path, size):
+def kernel_of(args):
+    """(name, mangled prefix) of the kernel the dispatch picks for window 7, 32 levels at this step"""
+    if args.step != 1:
+        return "k4_glcm_thread<7,3>", "_Z14k4_glcm_threadILi7ELi3EE"
+    return ("k4_glcm_pair", "_Z12k4_glcm_pair") if args.dense == "pair" else ("k4_glcm_quad", "_Z12k4_glcm_quad")
+
+
+def worker(lib_path, size, dense, step):
     sys.path[:0] = [os.path.join(ROOT, "rs-image-segmentation_amd"), ROOT]
     import torch
 
@@ -34,14 +42,14 @@ def worker(lib_path, size):
     H = W = size
     nir = bench.synth_rows(torch, ctx.device, W, 0, H, want=[3])[0]
     q = (nir / 255.0 * 31).to(torch.uint8)
-    os.environ["RSSEG_GLCM_DENSE"] = "quad"
-    ctx.glcm(q, H, W, 32, 7, 1)          # warm-up: code object, tables
+    os.environ["RSSEG_GLCM_DENSE"] = dense
+    ctx.glcm(q, H, W, 32, 7, step)       # warm-up: code object, tables
     runs = []
     for _ in range(2):
         ctx.prof_enable(True)
         ctx.prof_reset()
         for _ in range(LAUNCHES):
-            maps, _ = ctx.glcm(q, H, W, 32, 7, 1)
+            maps, _ = ctx.glcm(q, H, W, 32, 7, step)
         ms, cnt = ctx.prof_get("glcm")
         ctx.prof_enable(False)
         runs.append(round(ms / cnt, 3))
@@ -50,9 +58,9 @@ def worker(lib_path, size):
     ctx.close()
 
 
-def remarks(path):
+def remarks(path, mangled):
     text = open(path).read()
-    m = re.search(r"Function Name: _Z12k4_glcm_quad\w*(.*?)(?:Function Name:|\Z)", text, re.S)
+    m = re.search(r"Function Name: " + re.escape(mangled) + r"\w*(.*?)(?:Function Name:|\Z)", text, re.S)
     if not m:
         return None
     out = {}
@@ -65,20 +73,21 @@ def remarks(path):
 
 
 def driver(args):
-    out = {"note": f"ms per launch of k4_glcm_quad on a {args.size}x{args.size} plane (32 levels); per process two timings of {LAUNCHES} "
+    name, mangled = kernel_of(args)
+    out = {"note": f"ms per launch of {name} on a {args.size}x{args.size} plane (32 levels); per process two timings of {LAUNCHES} "
                    "launches after one warm-up launch; parent and new build alternate, one process each",
            "parent": [], "new": [], "rounds": args.rounds}
     sha = {}
     for _ in range(args.rounds):
-        for name, lib in (("parent", args.parent), ("new", args.new)):
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--lib", lib, "--size", str(args.size)], capture_output=True,
-                               text=True, timeout=args.timeout)
+        for build, lib in (("parent", args.parent), ("new", args.new)):
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--lib", lib, "--size", str(args.size), "--dense", args.dense,
+                                "--step", str(args.step)], capture_output=True, text=True, timeout=args.timeout)
             if p.returncode != 0:       # nothing more is started on the GPU after a failure
                 sys.stderr.write(p.stderr[-4000:])
-                raise SystemExit(f"{name} worker exited with {p.returncode}")
+                raise SystemExit(f"{build} worker exited with {p.returncode}")
             r = json.loads(p.stdout.strip().splitlines()[-1])
-            out[name].extend(r["ms_per_launch"])
-            sha.setdefault(name, set()).add(tuple(r["maps_sha256_16"]))
+            out[build].extend(r["ms_per_launch"])
+            sha.setdefault(build, set()).add(tuple(r["maps_sha256_16"]))
     out["bit_identical"] = len(sha["parent"] | sha["new"]) == 1
     out["parent_min_max"] = [min(out["parent"]), max(out["parent"])]
     out["new_min_max"] = [min(out["new"]), max(out["new"])]
@@ -86,7 +95,7 @@ def driver(args):
     med = lambda v: sorted(v)[len(v) // 2]
     out["median_gain_ms"] = round(med(out["parent"]) - med(out["new"]), 3)
     if args.remarks:
-        out["k4_glcm_quad_resources_new_build"] = remarks(args.remarks)
+        out[name + "_resources_new_build"] = remarks(args.remarks, mangled)
     print(json.dumps(out, indent=1))
 
 
@@ -99,9 +108,11 @@ if __name__ == "__main__":
     ap.add_argument("--size", type=int, default=16384)
     ap.add_argument("--timeout", type=int, default=240)
     ap.add_argument("--remarks")
+    ap.add_argument("--dense", choices=("quad", "pair"), default="quad")
+    ap.add_argument("--step", type=int, choices=(1, 7), default=1)
     a = ap.parse_args()
     if a.lib:
-        worker(a.lib, a.size)
+        worker(a.lib, a.size, a.dense, a.step)
     elif a.parent:
         driver(a)
     else:

@@ -14,20 +14,31 @@
 // Angles 0/90 (np = w(w-1)) and 45/135 (np = (w-1)^2) are combined over common denominators, which
 // leaves 8 float64 divisions and 4 square roots per window.
 //
-// Two kernels:
-//   k4_glcm_thread<WIN>  one thread per window (WIN <= 7, levels <= 64; the dense step-1 case of BASELINE
-//        config 3).  The window lives in 2*WIN registers, 4 pixels per register: pair moments come from
-//        v_sad_u8 / v_dot4_u32_u8 on whole rows; the unordered pair keys (13 bits) of TWO angles share a
-//        register and go through one Batcher network of v_pk_min_u16 / v_pk_max_u16, then a packed
-//        run-length pass.  Integer-VALU-bound, not HBM-bound (1 B/px in, 20 B/px out).
-//   k4_glcm_wg           one workgroup per window with an LDS co-occurrence histogram (any window
-//        size, levels <= 64; the reference's 21x21 / step 21 default).
-#include <utility>
-
+// Five kernel families; rsseg_glcm_u8 at the end of the file picks one from the geometry.
+//   Register-resident (WIN <= 7, levels <= 64): the window lives in 2*WIN registers, 4 pixels per register: pair moments
+//   come from v_sad_u8 / v_dot4_u32_u8 on whole rows; the unordered pair keys (13 bits) of TWO angles share a register and go
+//   through networks of v_pk_min_u16 / v_pk_max_u16, then a packed run-length pass.  Integer-VALU-bound, not HBM-bound
+//   (1 B/px in, 20 B/px out).
+//     k4_glcm_thread<WIN,SH>  one thread per window: windows 3 / 5 / 7 at any step, levels <= 32 (SH = 3) or <= 64 (SH = 2).
+//     k4_glcm_pair            window 7, step 1, levels <= 32: two horizontally adjacent windows per thread
+//                             (RSSEG_GLCM_DENSE=pair).
+//     k4_glcm_quad            the same case with a 2 x 2 block of windows per thread: the default dense kernel.
+//   LDS histograms (any window size):
+//     k4_glcm_wave<SPLIT>     one wave per window, levels <= 32 (the reference's 21x21 / step 21 default).
+//     k4_glcm_wg              one workgroup per window, levels <= 64.
+//   (65..256 levels: k4_glcm_offsets.hip.)
+// The register kernels differ in how many windows share a key and in nothing else; each step they share is defined once:
+//   static_net.h   sorting and merging networks built and checked at compile time
+//   pk16.h         packed 16-bit arithmetic, the compare-exchange pass (pk_compare_exchange), the run-length pass (pk_runlength)
+//   this file      the packed keys and their Hq table reads (glcm_build_keys and its hq_* policies), the pair moments
+//                  (row_moments, window_m1m2), the finish from pre-scaled moments (glcm_finish_stats),
+//                  the staging of the tables into LDS (glcm_stage_*)
+//   k4_glcm.h      the float64 finish, shared with k4_glcm_offsets.hip
 #include <mutex>
 
 #include "common.h"
 #include "k4_glcm.h"
+#include "pk16.h"
 
 __constant__ long long c_glcm_hq[256];
 __device__ long long g_glcm_hq2[1024];  // pair sums hq[dA] + hq[dB] at [dB * 32 + dA] (levels <= 32)
@@ -39,112 +50,128 @@ __device__ long long g_glcm_hq2[1024];  // pair sums hq[dA] + hq[dB] at [dB * 32
 static_assert(42 + 42 + 2 * (2 * (42 * 41 / 2)) < GLCM_SQRT_N && GLCM_SQRT_N % 512 == 0, "sqrt table too short for window 7");
 __device__ __attribute__((aligned(16))) double g_glcm_sqrt[GLCM_SQRT_N];
 
-static const int H_DR[4] = {0, 1, 1, 1};
-static const int H_DC[4] = {1, 1, 0, -1};
-
-// ---- compile-time machinery: every register array below is indexed by constants only ----------
-template <typename F, int... I> __device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>)
+// The tables staged into LDS by a workgroup of 256 threads (the caller's __syncthreads() follows).  Unrolled and without a
+// bounds test, the loads of all tables a kernel stages are requested back to back: one memory round trip instead of one
+// per piece.
+__device__ __forceinline__ void glcm_stage_sqrt(double (&sqt)[GLCM_SQRT_N])
 {
-    (f(std::integral_constant<int, I>{}), ...);
+#pragma unroll
+    for (int k = 0; k < GLCM_SQRT_N / 512; k++)
+        reinterpret_cast<double2 *>(sqt)[k * 256 + threadIdx.x] = reinterpret_cast<const double2 *>(g_glcm_sqrt)[k * 256 + threadIdx.x];
 }
-template <int N, typename F> __device__ __forceinline__ void static_for(F &&f)
+// BACK_TO_BACK: the unrolled form, for a kernel that stages other tables beside this one; otherwise a loop (a kernel with
+// this table alone has nothing to request beside it)
+template <bool BACK_TO_BACK> __device__ __forceinline__ void glcm_stage_hq2(long long (&hq2)[1024])
 {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-// Sorting network for P elements: Batcher's merge exchange for an arbitrary count (Knuth, TAOCP 5.2.2, Algorithm M) —
-// 309 comparators at P = 42, 241 at P = 36 (the power-of-two odd-even merge sort with the padded slots pruned: 327, 268)
-template <int P> struct sort_net {
-    int a[P * 12], b[P * 12];
-    int n;
-};
-template <int P> constexpr sort_net<P> make_sort_net()
-{
-    sort_net<P> s{};
-    int t = 0;
-    while ((1 << t) < P) t++;
-    int n = 0;
-    for (int p = t > 0 ? 1 << (t - 1) : 0; p > 0; p /= 2) {
-        int q = 1 << (t - 1), r = 0, d = p;
-        while (d > 0) {
-            for (int i = 0; i + d < P; i++)
-                if ((i & p) == r) {
-                    s.a[n] = i;
-                    s.b[n] = i + d;
-                    n++;
-                }
-            d = q - p;
-            q /= 2;
-            r = p;
-        }
+    if constexpr (BACK_TO_BACK) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) hq2[k * 256 + threadIdx.x] = g_glcm_hq2[k * 256 + threadIdx.x];
+    } else {
+        for (int i = threadIdx.x; i < 1024; i += 256) hq2[i] = g_glcm_hq2[i];
     }
-    s.n = n;
-    return s;
 }
-template <int P> struct net_holder {
-    static constexpr sort_net<P> net = make_sort_net<P>();
+// the first N entries of the per-difference table: 32 for levels <= 32, all 256 otherwise
+template <int N> __device__ __forceinline__ void glcm_stage_hq(long long (&hq)[N])
+{
+    static_assert(N <= 256, "one entry per thread");
+    if (N == 256 || threadIdx.x < N) hq[threadIdx.x] = c_glcm_hq[threadIdx.x];
+}
+
+// ---- the steps the register kernels share --------------------------------------------------------------------------
+// The window (or the patch of several windows) holds the pixels PRE-SCALED by 2^SH (SH = 3 for levels <= 32, 2 for levels
+// <= 64: still one byte), so that the scaled |a-b| gives the byte offset into the Hq table without a shift and all sums are
+// exact multiples that are shifted back at the end.
+
+// compiler fence: the N packed rows are redefined (as far as the compiler can tell) here, e.g. at the top of every group
+// iteration, so that the two group bodies cannot be hoisted out of the loop or merged (their combined live ranges would
+// not fit the register budget)
+template <int N> __device__ __forceinline__ void opaque_rows(unsigned (&w)[8][2])
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    static_for<N>([&](auto I) {
+        unsigned &a = w[I][0];
+        unsigned &b = w[I][1];
+        asm volatile("" : "+v"(a), "+v"(b));
+    });
+#endif
+}
+
+// the pixel positions (row, column 0..7 of the packed rows) of one pair; pad: the entry does not exist for this half
+struct gp_pos {
+    int rx, cx, ry, cy;
+    bool pad;
+};
+#define GP_PAD_LO 0x0000fffeu
+#define GP_PAD_HI 0xfffc0000u
+
+// Hq policies of glcm_build_keys: which table reads a register's packed difference d = dA' | dB' << 16 (primed = pre-scaled)
+// takes, and how many of them are left in flight before the sums are pinned (each read holds two registers).  A caller with
+// one sum passes it for both halves.
+__device__ __forceinline__ void hq_pin(long long &lo, long long &hi)
+{
+    pin64(lo);
+    if (&hi != &lo) pin64(hi);
+}
+// hq_pair_sum (SH = 3): t is the 32 x 32 table of PAIR sums t[dB][dA] = Hq(dA) + Hq(dB), one read per register, added to lo;
+// up to 6 reads in flight
+struct hq_pair_sum {
+    const long long *t;
+    template <int p> __device__ __forceinline__ void add(unsigned d, long long &lo, long long &hi) const
+    {
+        // byte offset 8 * (dA + 32 * dB) = lo16(d) * 1 + hi16(d) * 32 in one v_dot2_u32_u16
+        const unsigned off = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, d), (us2){1, 32}, 0u, false);
+        lo += *reinterpret_cast<const long long *>(reinterpret_cast<const char *>(t) + off);
+        if constexpr (p % 6 == 5) hq_pin(lo, hi);
+    }
+};
+// hq_per_half: t is the table Hq(d) itself, one read per half (the halves end up in different sums, or SH = 2: the table
+// of pair sums would not fit); up to 2 * EVERY reads in flight
+template <int SH, int EVERY> struct hq_per_half {
+    const long long *t;
+    template <int p> __device__ __forceinline__ void add(unsigned d, long long &lo, long long &hi) const
+    {
+        lo += *reinterpret_cast<const long long *>(reinterpret_cast<const char *>(t) + ((d & 0xffffu) << (3 - SH)));
+        hi += *reinterpret_cast<const long long *>(reinterpret_cast<const char *>(t) + ((d >> 16) << (3 - SH)));
+        if constexpr (p % EVERY == EVERY - 1) hq_pin(lo, hi);
+    }
 };
 
-typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pk_min(unsigned a, unsigned b)
+// Builds COUNT packed keys into K[OFF ..) and adds their Hq table reads (pads included: a pad reads Hq(0)) to HqLo / HqHi.
+// Entry p carries the pair WHERE(p, 0) in its low half and WHERE(p, 1) in its high half.
+// Key = lo' << 8 | hi' | diag (primed = scaled: the low SH bits of a scaled value are zero, so bit 0 is free for the flag
+// [a == b]): one v_lshl_or and one v_or on both halves at once.  A pad is an even value above every real key (no diagonal
+// flag, equal to nothing).
+template <gp_pos (*WHERE)(int, int), int COUNT, int OFF, typename HQ, int NK>
+__device__ __forceinline__ void glcm_build_keys(const unsigned (&P)[8][2], unsigned (&K)[NK], HQ hq, long long &HqLo, long long &HqHi)
 {
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(us2, a), __builtin_bit_cast(us2, b)));
-}
-__device__ __forceinline__ unsigned pk_max(unsigned a, unsigned b)
-{
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(us2, a), __builtin_bit_cast(us2, b)));
-}
-// v_pk_min_u16 the optimiser cannot see through: min(x, 1) written in C++ is canonicalised to a compare + select,
-// which has no packed form and costs four instructions per register instead of one.
-__device__ __forceinline__ unsigned pk_min_opaque(unsigned a, unsigned b)
-{
-    unsigned r = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-#endif
-    return r;
-}
-// max(a - b, 0) on both 16-bit halves (v_pk_sub_u16 with the clamp bit): 1 - d saturates to [d == 0]
-__device__ __forceinline__ unsigned pk_sub_sat(unsigned a, unsigned b)
-{
-    unsigned r = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
-#endif
-    return r;
-}
-// a * b on both 16-bit halves (v_pk_mul_lo_u16)
-__device__ __forceinline__ unsigned pk_mul(unsigned a, unsigned b)
-{
-    unsigned r = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-#endif
-    return r;
-}
-__device__ __forceinline__ unsigned pk_add(unsigned a, unsigned b)
-{
-    return __builtin_bit_cast(unsigned, (us2)(__builtin_bit_cast(us2, a) + __builtin_bit_cast(us2, b)));
-}
-__device__ __forceinline__ unsigned pk_sub(unsigned a, unsigned b)
-{
-    return __builtin_bit_cast(unsigned, (us2)(__builtin_bit_cast(us2, a) - __builtin_bit_cast(us2, b)));
+    static_for<COUNT>([&](auto I) {
+        constexpr int p = I;
+        constexpr gp_pos A = WHERE(p, 0), B = WHERE(p, 1);
+        // v_perm_b32: result byte 0 <- low-half pixel, byte 2 <- high-half pixel, bytes 1 and 3 <- 0
+        constexpr unsigned selx = (unsigned)(A.cx & 3) | (0x0cu << 8) | ((unsigned)(4 + (B.cx & 3)) << 16) | (0x0cu << 24);
+        constexpr unsigned sely = (unsigned)(A.cy & 3) | (0x0cu << 8) | ((unsigned)(4 + (B.cy & 3)) << 16) | (0x0cu << 24);
+        const unsigned x = __builtin_amdgcn_perm(P[B.rx][B.cx >> 2], P[A.rx][A.cx >> 2], selx);
+        const unsigned y = __builtin_amdgcn_perm(P[B.ry][B.cy >> 2], P[A.ry][A.cy >> 2], sely);
+        const unsigned lo = pk_min(x, y), hi = pk_max(x, y);
+        const unsigned d = pk_sub(hi, lo);
+        const unsigned one = 0x00010001u;
+        const unsigned diag = pk_sub_sat(one, d);  // [a == b] in both halves
+        unsigned k = ((lo << 8) | hi) | diag;      // each half stays below 2^16: the 32-bit shift does not cross
+        if constexpr (A.pad) k = (k & 0xffff0000u) | GP_PAD_LO;
+        if constexpr (B.pad) k = (k & 0x0000ffffu) | GP_PAD_HI;
+        K[OFF + p] = k;
+        pin32(K[OFF + p]);  // materialise the packed key now (short live ranges)
+        hq.template add<p>(d, HqLo, HqHi);
+    });
 }
 
-
-__device__ __forceinline__ void pin32(unsigned &v)
+// sqrt(A_a) + sqrt(A_b), A = 2 (PAIRS + D) + 4 E2, of the two angles packed in E2 / D
+template <int PAIRS> __device__ __forceinline__ double glcm_root_sum(unsigned E2, unsigned D)
 {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+v"(v));
-#endif
+    const long long Aa = 2ll * (PAIRS + (int)(D & 0xffffu)) + 4ll * (long long)(E2 & 0xffffu);
+    const long long Ab = 2ll * (PAIRS + (int)(D >> 16)) + 4ll * (long long)(E2 >> 16);
+    return sqrt((double)Aa) + sqrt((double)Ab);
 }
-__device__ __forceinline__ void pin64(long long &v)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+v"(v));
-#endif
-}
-
 
 // pair moments of one angle from whole packed rows: S1 = sum|a-b|, XY = sum ab, M2 = sum a^2+b^2, M1 = sum a+b
 template <int WIN, int DR, int DC>
@@ -245,12 +272,46 @@ template <int WIN> __device__ __forceinline__ void window_m1m2(const unsigned (&
     m2[3] = 2 * T2 - Rq - Cq + w0L * w0L + wL0 * wL0;
 }
 
+// the float64 finish of one window from its pair moments (still pre-scaled: S1 / m1 by 2^SH, XY / m2 by 2^2SH, undone here:
+// exact, every term is a multiple; XY in the order 0, 90, 45, 135 degrees, m1 / m2 in the order 0, 45, 90, 135)
+template <int WIN, int SH>
+__device__ __forceinline__ void glcm_finish_stats(unsigned S1g0, unsigned S1g1, const unsigned (&XY)[4], const unsigned (&m1)[4],
+                                                  const unsigned (&m2)[4], long long Hq0, double sq0, long long Hq1, double sq1, size_t o,
+                                                  const glcm_out &out, const glcm_consts &gc)
+{
+    static_assert(WIN <= 7 && SH >= 2 && glcm_fits_int32<WIN, (256 >> SH)>(), "the 32-bit finish needs (2 np (levels - 1))^2 < 2^31");
+    constexpr int NA = WIN * (WIN - 1), NB = (WIN - 1) * (WIN - 1);
+    const int xy0 = XY[0] >> (2 * SH), xy90 = XY[1] >> (2 * SH), xy45 = XY[2] >> (2 * SH), xy135 = XY[3] >> (2 * SH);
+    const int M20 = m2[0] >> (2 * SH), M245 = m2[1] >> (2 * SH), M290 = m2[2] >> (2 * SH), M2135 = m2[3] >> (2 * SH);
+    glcm_group32 g0, g1;
+    g0.S1 = S1g0 >> SH;
+    g0.S2 = (M20 - 2 * xy0) + (M290 - 2 * xy90);
+    g0.Hq = Hq0;
+    g0.sq = sq0;
+    g1.S1 = S1g1 >> SH;
+    g1.S2 = (M245 - 2 * xy45) + (M2135 - 2 * xy135);
+    g1.Hq = Hq1;
+    g1.sq = sq1;
+    const double r0 = glcm_corr32(NA, m1[0] >> SH, M20, 2 * xy0), r1 = glcm_corr32(NB, m1[1] >> SH, M245, 2 * xy45);
+    const double r2 = glcm_corr32(NA, m1[2] >> SH, M290, 2 * xy90), r3 = glcm_corr32(NB, m1[3] >> SH, M2135, 2 * xy135);
+    glcm_finish32(g0, g1, NA, NB, r0, r1, r2, r3, o, out, gc);
+}
+
+// ------------------------------------------------------------------------------------------------
+// k4_glcm_thread — one thread per window.
 // One angle group: G = 0 -> angles 0 (0,1) and 90 (1,0) degrees, G = 1 -> 45 (1,1) and 135 (1,-1).
 // Both angles of a group have the same pair count P, so their keys share registers (low / high half).
-// The window holds the pixels PRE-SCALED by 2^SH (SH = 3 for levels <= 32, 2 for levels <= 64: still one byte), so
-// that the scaled |a-b| gives the byte offset into the Hq table without a shift and all sums are exact multiples
-// that are shifted back at the end.  Key = lo' << 8 | hi' | diag (primed = scaled: the low SH bits of a scaled
-// value are zero, so bit 0 is free for the flag [a == b]): one v_lshl_or and one v_or on both halves at once.
+// ------------------------------------------------------------------------------------------------
+// pair p of the group's first (half 0) and second angle (half 1)
+template <int WIN, int G> __host__ __device__ constexpr gp_pos gt_where(int p, int half)
+{
+    if (G == 0) {
+        if (half == 0) return gp_pos{p / (WIN - 1), p % (WIN - 1), p / (WIN - 1), p % (WIN - 1) + 1, false};
+        return gp_pos{p / WIN, p % WIN, p / WIN + 1, p % WIN, false};
+    }
+    if (half == 0) return gp_pos{p / (WIN - 1), p % (WIN - 1), p / (WIN - 1) + 1, p % (WIN - 1) + 1, false};
+    return gp_pos{p / (WIN - 1), p % (WIN - 1) + 1, p / (WIN - 1) + 1, p % (WIN - 1), false};
+}
 struct glcm_raw {  // what one angle group leaves behind (S1 / XY still carry the 2^SH pre-scaling)
     unsigned S1, XYa, XYb;
     long long Hq;
@@ -261,39 +322,10 @@ __device__ __forceinline__ void glcm_group_stats(const unsigned (&w)[8][2], cons
 {
     constexpr int P = G == 0 ? WIN * (WIN - 1) : (WIN - 1) * (WIN - 1);
     unsigned K[P];
-    long long HqA = 0, HqB = 0;  // SH == 3: hq is the 32 x 32 table of PAIR sums hq[dB][dA] = Hq(dA) + Hq(dB): one read per register
-    static_for<P>([&](auto I) {
-        constexpr int p = I;
-        // pixel positions of pair p in angle A (low half) and angle B (high half)
-        constexpr int rxa = G == 0 ? p / (WIN - 1) : p / (WIN - 1), cxa = G == 0 ? p % (WIN - 1) : p % (WIN - 1);
-        constexpr int rya = G == 0 ? rxa : rxa + 1, cya = cxa + 1;
-        constexpr int rxb = G == 0 ? p / WIN : p / (WIN - 1), cxb = G == 0 ? p % WIN : p % (WIN - 1) + 1;
-        constexpr int ryb = rxb + 1, cyb = G == 0 ? cxb : cxb - 1;
-        // v_perm_b32: result byte 0 <- angle-A pixel, byte 2 <- angle-B pixel, bytes 1 and 3 <- 0
-        constexpr unsigned selx = (unsigned)(cxa & 3) | (0x0cu << 8) | ((unsigned)(4 + (cxb & 3)) << 16) | (0x0cu << 24);
-        constexpr unsigned sely = (unsigned)(cya & 3) | (0x0cu << 8) | ((unsigned)(4 + (cyb & 3)) << 16) | (0x0cu << 24);
-        const unsigned x = __builtin_amdgcn_perm(w[rxb][cxb >> 2], w[rxa][cxa >> 2], selx);
-        const unsigned y = __builtin_amdgcn_perm(w[ryb][cyb >> 2], w[rya][cya >> 2], sely);
-        const unsigned lo = pk_min(x, y), hi = pk_max(x, y);
-        const unsigned d = pk_sub(hi, lo);
-        const unsigned one = 0x00010001u;
-        const unsigned diag = pk_sub_sat(one, d);  // [a == b] in both halves
-        K[p] = ((lo << 8) | hi) | diag;            // each half stays below 2^16: the 32-bit shift does not cross
-        pin32(K[p]);  // materialise the packed key now (short live ranges)
-        if constexpr (SH == 3) {
-            // d = 8*dA | (8*dB) << 16  ->  byte offset 8 * (dA + 32 * dB)
-            // byte offset 8 * (dA + 32 * dB) = lo16(d) * 1 + hi16(d) * 32 in one v_dot2_u32_u16
-            const unsigned off = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, d), (us2){1, 32}, 0u, false);
-            HqA += *reinterpret_cast<const long long *>(reinterpret_cast<const char *>(hq) + off);
-        } else {
-            HqA += *reinterpret_cast<const long long *>(reinterpret_cast<const char *>(hq) + ((d & 0xffffu) << (3 - SH)));
-            HqB += *reinterpret_cast<const long long *>(reinterpret_cast<const char *>(hq) + ((d >> 16) << (3 - SH)));
-        }
-        if constexpr (p % 6 == 5) {  // every 6 pairs: up to 12 LUT reads (24 registers) in flight, not 2P
-            pin64(HqA);
-            pin64(HqB);
-        }
-    });
+    long long HqA = 0, HqB = 0;
+    // every 6 pairs: up to 12 LUT reads (24 registers) in flight, not 2P
+    if constexpr (SH == 3) glcm_build_keys<gt_where<WIN, G>, P, 0>(w, K, hq_pair_sum{hq}, HqA, HqB);
+    else glcm_build_keys<gt_where<WIN, G>, P, 0>(w, K, hq_per_half<SH, 6>{hq}, HqA, HqB);
     __builtin_amdgcn_sched_barrier(0);  // phase boundaries keep the phases' live ranges from overlapping
     unsigned S1a, XYa, S1b, XYb;
     if constexpr (G == 0) {
@@ -304,47 +336,15 @@ __device__ __forceinline__ void glcm_group_stats(const unsigned (&w)[8][2], cons
         row_moments<WIN, 1, -1>(w, S1b, XYb);
     }
     __builtin_amdgcn_sched_barrier(0);
-    // sort both halves at once
-    static_for<net_holder<P>::net.n>([&](auto I) {
-        constexpr int ia = net_holder<P>::net.a[I], ib = net_holder<P>::net.b[I];
-        const unsigned ka = K[ia], kb = K[ib];
-        K[ia] = pk_min(ka, kb);
-        K[ib] = pk_max(ka, kb);
-    });
+    pk_compare_exchange<net_holder<P>>(K);  // sort both halves at once
     __builtin_amdgcn_sched_barrier(0);
-    // packed run-length: t = equal-to-previous ? t + w : 0 (w = 2 on the diagonal, else 1); E2 += t; D += diag.
-    // All fields stay far below 2^16, so plain 32-bit adds (v_add3_u32) serve both halves.
-    const unsigned one = 0x00010001u;
-    unsigned E2 = 0, t = 0, D = K[0] & one;
-    static_for<P - 1>([&](auto I) {
-        constexpr int i = I + 1;
-        const unsigned diag = K[i] & one;
-        const unsigned eq = pk_sub_sat(one, K[i] ^ K[i - 1]);     // 1 where equal, 0 where different
-        t = pk_mul(t + one + diag, eq);
-        E2 += t;
-        D += diag;
-    });
-    const long long Aa = 2ll * (P + (int)(D & 0xffffu)) + 4ll * (long long)(E2 & 0xffffu);
-    const long long Ab = 2ll * (P + (int)(D >> 16)) + 4ll * (long long)(E2 >> 16);
+    unsigned E2, D;
+    pk_runlength<order_identity>(K, E2, D);
     g.S1 = S1a + S1b;
     g.XYa = XYa;
     g.XYb = XYb;
     g.Hq = HqA + HqB;
-    g.sq = sqrt((double)Aa) + sqrt((double)Ab);
-}
-
-// compiler fence: the packed window is redefined (as far as the compiler can tell) at the top of every
-// group iteration, so the two group bodies cannot be hoisted out of the loop or merged (their combined
-// live ranges would not fit the register budget)
-template <int WIN> __device__ __forceinline__ void opaque_window(unsigned (&w)[8][2])
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    static_for<WIN>([&](auto I) {
-        unsigned &a = w[I][0];
-        unsigned &b = w[I][1];
-        asm volatile("" : "+v"(a), "+v"(b));
-    });
-#endif
+    g.sq = glcm_root_sum<P>(E2, D);
 }
 
 template <int WIN, int SH>
@@ -352,11 +352,8 @@ __global__ __launch_bounds__(256) void k4_glcm_thread(const uint8_t *__restrict_
                                                       glcm_out out, glcm_consts gc)
 {
     __shared__ long long hq[SH == 3 ? 1024 : 256];
-    if constexpr (SH == 3) {
-        for (int i = threadIdx.x; i < 1024; i += 256) hq[i] = g_glcm_hq2[i];
-    } else {
-        hq[threadIdx.x] = c_glcm_hq[threadIdx.x];
-    }
+    if constexpr (SH == 3) glcm_stage_hq2<false>(hq);
+    else glcm_stage_hq(hq);
     __syncthreads();
     const int ox = blockIdx.x * 64 + (threadIdx.x & 63);
     const int oy = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -370,7 +367,7 @@ __global__ __launch_bounds__(256) void k4_glcm_thread(const uint8_t *__restrict_
             static_for<WIN>([&](auto J) {
                 constexpr int c = J;
                 const unsigned b = wp[(size_t)r * W + c];
-                if constexpr (c < 4) lo |= b << (8 * c + SH);  // pre-scaled by 2^SH (see glcm_group_stats)
+                if constexpr (c < 4) lo |= b << (8 * c + SH);  // pre-scaled by 2^SH
                 else hi |= b << (8 * (c - 4) + SH);
             });
             w[r][0] = lo;
@@ -380,31 +377,16 @@ __global__ __launch_bounds__(256) void k4_glcm_thread(const uint8_t *__restrict_
     glcm_raw q0, q1;
 #pragma nounroll
     for (int g = 0; g < 2; g++) {
-        opaque_window<WIN>(w);
+        opaque_rows<WIN>(w);
         if (g == 0) glcm_group_stats<WIN, 0, SH>(w, hq, q0);
         else glcm_group_stats<WIN, 1, SH>(w, hq, q1);
     }
-    // M1 / M2 of the four angles (computed after the groups: nothing of it has to stay live across them), then the
-    // 2^SH pre-scaling is undone (exact: every term is a multiple)
-    opaque_window<WIN>(w);
+    // M1 / M2 of the four angles (computed after the groups: nothing of it has to stay live across them)
+    opaque_rows<WIN>(w);
     unsigned m1[4], m2[4];
     window_m1m2<WIN>(w, m1, m2);
-    static_assert(WIN <= 7 && SH >= 2 && glcm_fits_int32<WIN, (256 >> SH)>(), "the 32-bit finish needs (2 np (levels - 1))^2 < 2^31");
-    constexpr int NA = WIN * (WIN - 1), NB = (WIN - 1) * (WIN - 1);
-    const int xy0 = q0.XYa >> (2 * SH), xy90 = q0.XYb >> (2 * SH), xy45 = q1.XYa >> (2 * SH), xy135 = q1.XYb >> (2 * SH);
-    const int M20 = m2[0] >> (2 * SH), M245 = m2[1] >> (2 * SH), M290 = m2[2] >> (2 * SH), M2135 = m2[3] >> (2 * SH);
-    glcm_group32 g0, g1;
-    g0.S1 = q0.S1 >> SH;
-    g0.S2 = (M20 - 2 * xy0) + (M290 - 2 * xy90);
-    g0.Hq = q0.Hq;
-    g0.sq = q0.sq;
-    g1.S1 = q1.S1 >> SH;
-    g1.S2 = (M245 - 2 * xy45) + (M2135 - 2 * xy135);
-    g1.Hq = q1.Hq;
-    g1.sq = q1.sq;
-    const double r0 = glcm_corr32(NA, m1[0] >> SH, M20, 2 * xy0), r1 = glcm_corr32(NB, m1[1] >> SH, M245, 2 * xy45);
-    const double r2 = glcm_corr32(NA, m1[2] >> SH, M290, 2 * xy90), r3 = glcm_corr32(NB, m1[3] >> SH, M2135, 2 * xy135);
-    glcm_finish32(g0, g1, NA, NB, r0, r1, r2, r3, (size_t)oy * ow + ox, out, gc);
+    const unsigned XY[4] = {q0.XYa, q0.XYb, q1.XYa, q1.XYb};
+    glcm_finish_stats<WIN, SH>(q0.S1, q1.S1, XY, m1, m2, q0.Hq, q0.sq, q1.Hq, q1.sq, (size_t)oy * ow + ox, out, gc);
 }
 
 
@@ -420,88 +402,9 @@ __global__ __launch_bounds__(256) void k4_glcm_thread(const uint8_t *__restrict_
 // itself so that its table read adds exactly Hq(0) = 2^52, which is subtracted again.
 // Same integer statistics, same float64 finish: bit-identical to k4_glcm_thread (and to oracle.c mode 1).
 // ------------------------------------------------------------------------------------------------
-template <int M, int N> struct merge_net {
-    int a[(M + N) * 8], b[(M + N) * 8];
-    int n;
-    int order[M + N];  // register indices in ascending order of their values after the network
-};
-struct merge_emit {
-    int *a, *b, *n;
-};
-// merges the sorted runs held in registers x[0..m) and y[0..n): comparators appended to e, ascending order to out
-constexpr void oem_build(const int *x, int m, const int *y, int n, int *out, merge_emit e)
-{
-    if (m == 0) { for (int i = 0; i < n; i++) out[i] = y[i]; return; }
-    if (n == 0) { for (int i = 0; i < m; i++) out[i] = x[i]; return; }
-    if (m == 1 && n == 1) {
-        e.a[*e.n] = x[0]; e.b[*e.n] = y[0]; (*e.n)++;
-        out[0] = x[0]; out[1] = y[0];
-        return;
-    }
-    int xe[64] = {}, xo[64] = {}, ye[64] = {}, yo[64] = {}, v[128] = {}, w[128] = {};
-    int me = 0, mo = 0, ne = 0, no = 0;
-    for (int i = 0; i < m; i++) { if (i & 1) xo[mo++] = x[i]; else xe[me++] = x[i]; }
-    for (int i = 0; i < n; i++) { if (i & 1) yo[no++] = y[i]; else ye[ne++] = y[i]; }
-    oem_build(xe, me, ye, ne, v, e);
-    oem_build(xo, mo, yo, no, w, e);
-    const int lv = me + ne, lw = mo + no;
-    int k = 0;
-    out[k++] = v[0];
-    for (int i = 0; i < lw; i++) {
-        if (i + 1 < lv) {
-            e.a[*e.n] = w[i]; e.b[*e.n] = v[i + 1]; (*e.n)++;
-            out[k++] = w[i];
-            out[k++] = v[i + 1];
-        } else {
-            out[k++] = w[i];
-        }
-    }
-    for (int i = lw + 1; i < lv; i++) out[k++] = v[i];
-}
-template <int M, int N> constexpr merge_net<M, N> make_merge_net()
-{
-    merge_net<M, N> s{};
-    int x[M] = {}, y[N] = {};
-    for (int i = 0; i < M; i++) x[i] = i;
-    for (int i = 0; i < N; i++) y[i] = M + i;
-    int n = 0;
-    oem_build(x, M, y, N, s.order, merge_emit{s.a, s.b, &n});
-    s.n = n;
-    return s;
-}
-// zero-one principle restricted to merging: every pair of sorted 0/1 runs must come out sorted
-template <int M, int N> constexpr bool merge_net_ok(const merge_net<M, N> &s)
-{
-    for (int za = 0; za <= M; za++)
-        for (int zb = 0; zb <= N; zb++) {
-            int r[M + N] = {};
-            for (int i = 0; i < M; i++) r[i] = i >= za;
-            for (int i = 0; i < N; i++) r[M + i] = i >= zb;
-            for (int c = 0; c < s.n; c++) {
-                const int lo = r[s.a[c]] < r[s.b[c]] ? r[s.a[c]] : r[s.b[c]], hi = r[s.a[c]] + r[s.b[c]] - lo;
-                r[s.a[c]] = lo;
-                r[s.b[c]] = hi;
-            }
-            for (int i = 1; i < M + N; i++)
-                if (r[s.order[i - 1]] > r[s.order[i]]) return false;
-        }
-    return true;
-}
-template <int M, int N> struct merge_holder {
-    static constexpr merge_net<M, N> net = make_merge_net<M, N>();
-    static_assert(merge_net_ok(net), "odd-even merging network does not merge");
-};
-
-#define GP_PAD_LO 0x0000fffeu
-#define GP_PAD_HI 0xfffc0000u
-
 // pixel positions (patch row, patch column 0..7) of entry p of a key set: SET 0 = shared by both windows,
 // 1 = only window A (patch columns 0..6), 2 = only window B (columns 1..7).  half 0 = low 16 bits (angle 0 / 45 degrees),
-// half 1 = high 16 bits (90 / 135).  pad: the entry does not exist for this half.
-struct gp_pos {
-    int rx, cx, ry, cy;
-    bool pad;
-};
+// half 1 = high 16 bits (90 / 135).
 template <int G, int SET> __host__ __device__ constexpr int gp_count() { return G == 0 ? (SET == 0 ? 36 : 7) : (SET == 0 ? 30 : 6); }
 template <int G, int SET> __host__ __device__ constexpr gp_pos gp_where(int p, int half)
 {
@@ -530,62 +433,6 @@ template <int G, int SET> __host__ __device__ constexpr int gp_pads()
     return n;
 }
 
-// builds the packed keys of one set into K[OFF ..) and returns the sum of their Hq table reads (pads included)
-template <int G, int SET, int OFF, int NK>
-__device__ __forceinline__ long long gp_build(const unsigned (&P)[8][2], const long long *__restrict__ hq, unsigned (&K)[NK])
-{
-    long long Hq = 0;
-    static_for<gp_count<G, SET>()>([&](auto I) {
-        constexpr int p = I;
-        constexpr gp_pos A = gp_where<G, SET>(p, 0), B = gp_where<G, SET>(p, 1);
-        constexpr unsigned selx = (unsigned)(A.cx & 3) | (0x0cu << 8) | ((unsigned)(4 + (B.cx & 3)) << 16) | (0x0cu << 24);
-        constexpr unsigned sely = (unsigned)(A.cy & 3) | (0x0cu << 8) | ((unsigned)(4 + (B.cy & 3)) << 16) | (0x0cu << 24);
-        const unsigned x = __builtin_amdgcn_perm(P[B.rx][B.cx >> 2], P[A.rx][A.cx >> 2], selx);
-        const unsigned y = __builtin_amdgcn_perm(P[B.ry][B.cy >> 2], P[A.ry][A.cy >> 2], sely);
-        const unsigned lo = pk_min(x, y), hi = pk_max(x, y);
-        const unsigned d = pk_sub(hi, lo);
-        const unsigned one = 0x00010001u;
-        const unsigned diag = pk_sub_sat(one, d);
-        unsigned k = ((lo << 8) | hi) | diag;
-        if constexpr (A.pad) k = (k & 0xffff0000u) | GP_PAD_LO;
-        if constexpr (B.pad) k = (k & 0x0000ffffu) | GP_PAD_HI;
-        K[OFF + p] = k;
-        pin32(K[OFF + p]);
-        const unsigned off = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, d), (us2){1, 32}, 0u, false);
-        Hq += *reinterpret_cast<const long long *>(reinterpret_cast<const char *>(hq) + off);
-        if constexpr (p % 6 == 5) pin64(Hq);
-    });
-    return Hq;
-}
-
-// E2 and D (both halves packed) of the keys in K taken in the order ORD
-template <int NK, typename NET> __device__ __forceinline__ void gp_runlength(const unsigned (&K)[NK], unsigned &E2, unsigned &D)
-{
-    const unsigned one = 0x00010001u;
-    E2 = 0;
-    unsigned t = 0;
-    D = K[NET::net.order[0]] & one;
-    static_for<NK - 1>([&](auto I) {
-        constexpr int i = NET::net.order[I + 1], j = NET::net.order[I];
-        const unsigned diag = K[i] & one;
-        const unsigned eq = pk_sub_sat(one, K[i] ^ K[j]);   // 1 where the keys are equal, 0 where they differ
-        t = pk_mul(t + one + diag, eq);
-        E2 += t;
-        D += diag;
-    });
-}
-
-template <int NS> __device__ __forceinline__ void opaque_patch(unsigned (&P)[8][2])
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    static_for<NS>([&](auto I) {
-        unsigned &a = P[I][0];
-        unsigned &b = P[I][1];
-        asm volatile("" : "+v"(a), "+v"(b));
-    });
-#endif
-}
-
 // one angle group of both windows: E2 / D per window from the shared sorted run, Hq per window
 template <int G>
 __device__ __forceinline__ void gp_group(const unsigned (&P)[8][2], const long long *__restrict__ hq, long long &HqA, long long &HqB,
@@ -595,65 +442,26 @@ __device__ __forceinline__ void gp_group(const unsigned (&P)[8][2], const long l
     constexpr int PAIRS = G == 0 ? 42 : 36;
     using MNET = merge_holder<NS, NO>;
     unsigned KA[NK], KB[NK];
-    const long long HqS = gp_build<G, 0, 0, NK>(P, hq, KA);
+    long long HqS = 0;
+    glcm_build_keys<gp_where<G, 0>, NS, 0>(P, KA, hq_pair_sum{hq}, HqS, HqS);
     __builtin_amdgcn_sched_barrier(0);
-    static_for<net_holder<NS>::net.n>([&](auto I) {
-        constexpr int ia = net_holder<NS>::net.a[I], ib = net_holder<NS>::net.b[I];
-        const unsigned ka = KA[ia], kb = KA[ib];
-        KA[ia] = pk_min(ka, kb);
-        KA[ib] = pk_max(ka, kb);
-    });
+    pk_compare_exchange<net_holder<NS>>(KA);
     static_for<NS>([&](auto I) { KB[I] = KA[I]; });
     __builtin_amdgcn_sched_barrier(0);
     auto window = [&](auto set_t, unsigned (&K)[NK], long long &Hq, double &sq) {
         constexpr int SET = decltype(set_t)::value;
-        Hq = HqS + gp_build<G, SET, NS, NK>(P, hq, K) - (long long)(gp_pads<G, 0>() + gp_pads<G, SET>()) * 4503599627370496ll;
-        static_for<net_holder<NO>::net.n>([&](auto I) {
-            constexpr int ia = NS + net_holder<NO>::net.a[I], ib = NS + net_holder<NO>::net.b[I];
-            const unsigned ka = K[ia], kb = K[ib];
-            K[ia] = pk_min(ka, kb);
-            K[ib] = pk_max(ka, kb);
-        });
-        static_for<MNET::net.n>([&](auto I) {
-            constexpr int ia = MNET::net.a[I], ib = MNET::net.b[I];
-            const unsigned ka = K[ia], kb = K[ib];
-            K[ia] = pk_min(ka, kb);
-            K[ib] = pk_max(ka, kb);
-        });
+        long long HqO = 0;
+        glcm_build_keys<gp_where<G, SET>, NO, NS>(P, K, hq_pair_sum{hq}, HqO, HqO);
+        Hq = HqS + HqO - (long long)(gp_pads<G, 0>() + gp_pads<G, SET>()) * 4503599627370496ll;
+        pk_compare_exchange<net_holder<NO>, NS>(K);
+        pk_compare_exchange<MNET>(K);
         unsigned E2, D;
-        gp_runlength<NK, MNET>(K, E2, D);
-        const long long Aa = 2ll * (PAIRS + (int)(D & 0xffffu)) + 4ll * (long long)(E2 & 0xffffu);
-        const long long Ab = 2ll * (PAIRS + (int)(D >> 16)) + 4ll * (long long)(E2 >> 16);
-        sq = sqrt((double)Aa) + sqrt((double)Ab);
+        pk_runlength<order_of<MNET>>(K, E2, D);
+        sq = glcm_root_sum<PAIRS>(E2, D);
     };
     window(std::integral_constant<int, 1>{}, KA, HqA, sqA);
     __builtin_amdgcn_sched_barrier(0);
     window(std::integral_constant<int, 2>{}, KB, HqB, sqB);
-}
-
-// the float64 finish of one 7 x 7 window of the dense kernels from its pair moments (still pre-scaled: S1 / m1 by 2^SH, XY / m2
-// by 2^2SH; XY in the order 0, 90, 45, 135 degrees, m1 / m2 in the order 0, 45, 90, 135)
-__device__ __forceinline__ void gp_finish_stats(unsigned S1g0, unsigned S1g1, const unsigned (&XY)[4], const unsigned (&m1)[4],
-                                                const unsigned (&m2)[4], long long Hq0, double sq0, long long Hq1, double sq1, size_t o,
-                                                const glcm_out &out, const glcm_consts &gc)
-{
-    constexpr int WIN = 7, SH = 3;
-    static_assert(glcm_fits_int32<WIN, (256 >> SH)>(), "the 32-bit finish needs (2 np (levels - 1))^2 < 2^31");
-    constexpr int NA = WIN * (WIN - 1), NB = (WIN - 1) * (WIN - 1);
-    const int xy0 = XY[0] >> (2 * SH), xy90 = XY[1] >> (2 * SH), xy45 = XY[2] >> (2 * SH), xy135 = XY[3] >> (2 * SH);
-    const int M20 = m2[0] >> (2 * SH), M245 = m2[1] >> (2 * SH), M290 = m2[2] >> (2 * SH), M2135 = m2[3] >> (2 * SH);
-    glcm_group32 g0, g1;
-    g0.S1 = S1g0 >> SH;
-    g0.S2 = (M20 - 2 * xy0) + (M290 - 2 * xy90);
-    g0.Hq = Hq0;
-    g0.sq = sq0;
-    g1.S1 = S1g1 >> SH;
-    g1.S2 = (M245 - 2 * xy45) + (M2135 - 2 * xy135);
-    g1.Hq = Hq1;
-    g1.sq = sq1;
-    const double r0 = glcm_corr32(NA, m1[0] >> SH, M20, 2 * xy0), r1 = glcm_corr32(NB, m1[1] >> SH, M245, 2 * xy45);
-    const double r2 = glcm_corr32(NA, m1[2] >> SH, M290, 2 * xy90), r3 = glcm_corr32(NB, m1[3] >> SH, M2135, 2 * xy135);
-    glcm_finish32(g0, g1, NA, NB, r0, r1, r2, r3, o, out, gc);
 }
 
 // everything of one window that does not involve the key sort: pair moments, M1 / M2, the float64 finish
@@ -668,7 +476,7 @@ __device__ __forceinline__ void gp_finish(unsigned (&w)[8][2], long long Hq0, do
     row_moments<WIN, 1, -1>(w, S1d, XY[3]);
     unsigned m1[4], m2[4];
     window_m1m2<WIN>(w, m1, m2);
-    gp_finish_stats(S1a + S1b, S1c + S1d, XY, m1, m2, Hq0, sq0, Hq1, sq1, o, out, gc);
+    glcm_finish_stats<WIN, 3>(S1a + S1b, S1c + S1d, XY, m1, m2, Hq0, sq0, Hq1, sq1, o, out, gc);
 }
 
 __global__ __launch_bounds__(256) void k4_glcm_pair(const uint8_t *__restrict__ q, int H, int W, int oh, int ow, glcm_out out,
@@ -676,7 +484,7 @@ __global__ __launch_bounds__(256) void k4_glcm_pair(const uint8_t *__restrict__ 
 {
     constexpr int SH = 3;
     __shared__ long long hq[1024];
-    for (int i = threadIdx.x; i < 1024; i += 256) hq[i] = g_glcm_hq2[i];
+    glcm_stage_hq2<false>(hq);
     __syncthreads();
     const int ox = 2 * (blockIdx.x * 64 + (threadIdx.x & 63));
     const int oy = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -703,13 +511,13 @@ __global__ __launch_bounds__(256) void k4_glcm_pair(const uint8_t *__restrict__ 
     double sq[2][2];
 #pragma nounroll
     for (int g = 0; g < 2; g++) {
-        opaque_patch<7>(P);
+        opaque_rows<7>(P);
         if (g == 0) gp_group<0>(P, hq, Hq[0][0], Hq[1][0], sq[0][0], sq[1][0]);
         else gp_group<1>(P, hq, Hq[0][1], Hq[1][1], sq[0][1], sq[1][1]);
     }
     const size_t o = (size_t)oy * ow + ox;
     unsigned w[8][2];
-    opaque_patch<7>(P);
+    opaque_rows<7>(P);
     static_for<7>([&](auto I) {
         w[I][0] = P[I][0];
         w[I][1] = P[I][1] & 0x00ffffffu;
@@ -717,7 +525,7 @@ __global__ __launch_bounds__(256) void k4_glcm_pair(const uint8_t *__restrict__ 
     w[7][0] = w[7][1] = 0;
     gp_finish(w, Hq[0][0], sq[0][0], Hq[0][1], sq[0][1], o, out, gc);
     if (hasB) {
-        opaque_patch<7>(P);
+        opaque_rows<7>(P);
         static_for<7>([&](auto I) {
             w[I][0] = __builtin_amdgcn_alignbyte(P[I][1], P[I][0], 1);
             w[I][1] = P[I][1] >> 8;
@@ -732,7 +540,7 @@ __global__ __launch_bounds__(256) void k4_glcm_pair(const uint8_t *__restrict__ 
 // pairs of the 0 / 90 degree angles, 25 of the 36 of 45 / 135), two of them a STRIP of 5 more, and each adds its OWN 7
 // (6): the core is built and sorted once per thread, core + strip merged once per two windows, and a window only sorts
 // its own keys and merges them in — per window 375 compare-exchanges instead of the pair kernel's 446 and 32 packed keys
-// built instead of 46.  The same integer statistics, the same float64 finish (gp_finish_stats): bit-identical.
+// built instead of 46.  The same integer statistics, the same float64 finish (glcm_finish_stats): bit-identical.
 //   Finish (r05).  The pair moments of the windows (dx, 0) and (dx, 1) come from per-row sums computed once per column
 //   alignment (gq_column_moments), the integer part of the finish runs in 32 bits (k4_glcm.h: glcm_fits_int32) and the four
 //   square roots of a window are read from a table of sqrt(2 i) in LDS (g_glcm_sqrt) instead of computed.
@@ -743,66 +551,9 @@ __global__ __launch_bounds__(256) void k4_glcm_pair(const uint8_t *__restrict__ 
 //   (0 degrees: A, B) and of the left column strip (90 degrees: A, C) is what slots 0 and 1 both start from, and the
 //   bottom / right one what slots 2 and 3 start from.  The Hq sums of the sets that are split between windows are read
 //   per half from the 32-entry table instead of the table of pair sums.
+//   Merging.  Two stages on registers [0, NC + NT + NO): the first merges the sorted runs [0, NC) and [NC, NC + NT), the
+//   second merges that run, in the first's output order, with the sorted run [NC + NT, NC + NT + NO).
 // ------------------------------------------------------------------------------------------------
-// two-stage merging network on registers [0, NC + NT + NO): stage 1 merges the sorted runs [0, NC) and [NC, NC + NT)
-// (the logical order afterwards is order1), stage 2 merges that run with the sorted run [NC + NT, NC + NT + NO)
-template <int NC, int NT, int NO> struct quad_net {
-    int a1[(NC + NT) * 8], b1[(NC + NT) * 8], n1;
-    int order1[NC + NT];
-    int a2[(NC + NT + NO) * 8], b2[(NC + NT + NO) * 8], n2;
-    int order2[NC + NT + NO];
-};
-template <int NC, int NT, int NO> constexpr quad_net<NC, NT, NO> make_quad_net()
-{
-    quad_net<NC, NT, NO> s{};
-    int x[NC] = {}, y[NT] = {}, z[NO] = {};
-    for (int i = 0; i < NC; i++) x[i] = i;
-    for (int i = 0; i < NT; i++) y[i] = NC + i;
-    for (int i = 0; i < NO; i++) z[i] = NC + NT + i;
-    int n = 0;
-    oem_build(x, NC, y, NT, s.order1, merge_emit{s.a1, s.b1, &n});
-    s.n1 = n;
-    n = 0;
-    oem_build(s.order1, NC + NT, z, NO, s.order2, merge_emit{s.a2, s.b2, &n});
-    s.n2 = n;
-    return s;
-}
-// zero-one principle, stage by stage (stage 2 starts from any sorted 0 / 1 run laid out in stage 1's order)
-template <int NC, int NT, int NO> constexpr bool quad_net_ok(const quad_net<NC, NT, NO> &s)
-{
-    for (int za = 0; za <= NC; za++)
-        for (int zb = 0; zb <= NT; zb++) {
-            int r[NC + NT] = {};
-            for (int i = 0; i < NC; i++) r[i] = i >= za;
-            for (int i = 0; i < NT; i++) r[NC + i] = i >= zb;
-            for (int c = 0; c < s.n1; c++) {
-                const int lo = r[s.a1[c]] < r[s.b1[c]] ? r[s.a1[c]] : r[s.b1[c]], hi = r[s.a1[c]] + r[s.b1[c]] - lo;
-                r[s.a1[c]] = lo;
-                r[s.b1[c]] = hi;
-            }
-            for (int i = 1; i < NC + NT; i++)
-                if (r[s.order1[i - 1]] > r[s.order1[i]]) return false;
-        }
-    for (int za = 0; za <= NC + NT; za++)
-        for (int zc = 0; zc <= NO; zc++) {
-            int r[NC + NT + NO] = {};
-            for (int i = 0; i < NC + NT; i++) r[s.order1[i]] = i >= za;
-            for (int i = 0; i < NO; i++) r[NC + NT + i] = i >= zc;
-            for (int c = 0; c < s.n2; c++) {
-                const int lo = r[s.a2[c]] < r[s.b2[c]] ? r[s.a2[c]] : r[s.b2[c]], hi = r[s.a2[c]] + r[s.b2[c]] - lo;
-                r[s.a2[c]] = lo;
-                r[s.b2[c]] = hi;
-            }
-            for (int i = 1; i < NC + NT + NO; i++)
-                if (r[s.order2[i - 1]] > r[s.order2[i]]) return false;
-        }
-    return true;
-}
-template <int NC, int NT, int NO> struct quad_holder {
-    static constexpr quad_net<NC, NT, NO> net = make_quad_net<NC, NT, NO>();
-    static_assert(quad_net_ok(net), "two-stage merging network does not merge");
-};
-
 // sets of a group: 0 = core, 1 = strip of slots 0 / 1 (0 degrees: top row; 90: left column; 45 / 135: top row),
 // 2 = strip of slots 2 / 3 (bottom row; right column), 3 + s = own keys of slot s
 template <int G, int SET> __host__ __device__ constexpr int gq_count()
@@ -842,38 +593,6 @@ template <int G, int SET> __host__ __device__ constexpr gp_pos gq_where(int p, i
     return gp_pos{r, c + sh, r + 1, c + 1 - sh, false};
 }
 
-// builds the packed keys of one set into K[OFF ..).  SPLIT: the Hq table reads are made per half (HqLo / HqHi: the two
-// halves end up in different windows); otherwise one read of the pair-sum table (added to HqLo)
-template <int G, int SET, int OFF, int NK, bool SPLIT>
-__device__ __forceinline__ void gq_build(const unsigned (&P)[8][2], const long long *__restrict__ hq2, const long long *__restrict__ hq1,
-                                         unsigned (&K)[NK], long long &HqLo, long long &HqHi)
-{
-    static_for<gq_count<G, SET>()>([&](auto I) {
-        constexpr int p = I;
-        constexpr gp_pos A = gq_where<G, SET>(p, 0), B = gq_where<G, SET>(p, 1);
-        constexpr unsigned selx = (unsigned)(A.cx & 3) | (0x0cu << 8) | ((unsigned)(4 + (B.cx & 3)) << 16) | (0x0cu << 24);
-        constexpr unsigned sely = (unsigned)(A.cy & 3) | (0x0cu << 8) | ((unsigned)(4 + (B.cy & 3)) << 16) | (0x0cu << 24);
-        const unsigned x = __builtin_amdgcn_perm(P[B.rx][B.cx >> 2], P[A.rx][A.cx >> 2], selx);
-        const unsigned y = __builtin_amdgcn_perm(P[B.ry][B.cy >> 2], P[A.ry][A.cy >> 2], sely);
-        const unsigned lo = pk_min(x, y), hi = pk_max(x, y);
-        const unsigned d = pk_sub(hi, lo);
-        const unsigned one = 0x00010001u;
-        const unsigned diag = pk_sub_sat(one, d);
-        K[OFF + p] = ((lo << 8) | hi) | diag;
-        pin32(K[OFF + p]);
-        if constexpr (SPLIT) {   // d = 8 * dA | (8 * dB) << 16: byte offsets into the 32-entry table
-            HqLo += *reinterpret_cast<const long long *>(reinterpret_cast<const char *>(hq1) + (d & 0xffffu));
-            HqHi += *reinterpret_cast<const long long *>(reinterpret_cast<const char *>(hq1) + (d >> 16));
-        } else {
-            const unsigned off = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, d), (us2){1, 32}, 0u, false);
-            HqLo += *reinterpret_cast<const long long *>(reinterpret_cast<const char *>(hq2) + off);
-        }
-        // table reads in flight: 6 pair-sum reads (core, built while few keys are live) or 2 x 2 per-half reads (8 registers:
-        // the own-key sets are built at the kernel's register peak)
-        if constexpr (SPLIT ? p % 2 == 1 : p % 6 == 5) { pin64(HqLo); pin64(HqHi); }
-    });
-}
-
 // one angle group of the four windows.  ED[s] = D + 2 E2 of slot s (both halves packed: at most 42 + 2 * 1722 per half, so
 // A = 2 (np + D) + 4 E2 = 2 (np + ED)); Hq[w] of window w (A, B, C, D)
 template <int G>
@@ -881,17 +600,17 @@ __device__ __forceinline__ void gq_group(const unsigned (&P)[8][2], const long l
                                          unsigned (&ED)[4], long long (&Hq)[4])
 {
     constexpr int NC = gq_count<G, 0>(), NT = gq_count<G, 1>(), NO = gq_count<G, 3>(), NS = NC + NT, NK = NS + NO;
-    using QN = quad_holder<NC, NT, NO>;
+    using STAGE1 = merge_holder<NC, NT>;
+    using STAGE2 = merge_holder<NS, NO, STAGE1>;
+    // table reads in flight: 6 pair-sum reads (core, built while few keys are live) or 2 x 2 per-half reads (8 registers:
+    // the own-key sets are built at the kernel's register peak)
+    const hq_pair_sum whole{hq2};
+    const hq_per_half<3, 2> split{hq1};
     unsigned KC[NK], KS[NK], K[NK];    // KC: the sorted core (later core + strip 2, then slot 3 in place); KS: core + strip 1, then slot 1 in place
     long long hqCore = 0, dummy = 0;
-    gq_build<G, 0, 0, NK, false>(P, hq2, hq1, KC, hqCore, dummy);
+    glcm_build_keys<gq_where<G, 0>, NC, 0>(P, KC, whole, hqCore, dummy);
     __builtin_amdgcn_sched_barrier(0);
-    static_for<net_holder<NC>::net.n>([&](auto I) {
-        constexpr int ia = net_holder<NC>::net.a[I], ib = net_holder<NC>::net.b[I];
-        const unsigned ka = KC[ia], kb = KC[ib];
-        KC[ia] = pk_min(ka, kb);
-        KC[ib] = pk_max(ka, kb);
-    });
+    pk_compare_exchange<net_holder<NC>>(KC);
     __builtin_amdgcn_sched_barrier(0);
     // Hq of a window = core + its strip halves + its own halves.  Group 0 packs the 0-degree keys of window w with the
     // 90-degree keys of its transpose partner: the low half of slot s belongs to window s, the high half to window
@@ -902,57 +621,29 @@ __device__ __forceinline__ void gq_group(const unsigned (&P)[8][2], const long l
     auto add_strip = [&](auto hb_t, unsigned (&S)[NK]) {
         constexpr int HB = decltype(hb_t)::value;
         long long lo = 0, hi = 0;
-        gq_build<G, 1 + HB, NC, NK, true>(P, hq2, hq1, S, lo, hi);
+        glcm_build_keys<gq_where<G, 1 + HB>, NT, NC>(P, S, split, lo, hi);
         Hq[2 * HB] += lo;
         Hq[2 * HB + 1] += lo;
         if constexpr (G == 0) { Hq[HB] += hi; Hq[HB + 2] += hi; }
         else { Hq[2 * HB] += hi; Hq[2 * HB + 1] += hi; }
-        static_for<net_holder<NT>::net.n>([&](auto I) {
-            constexpr int ia = NC + net_holder<NT>::net.a[I], ib = NC + net_holder<NT>::net.b[I];
-            const unsigned ka = S[ia], kb = S[ib];
-            S[ia] = pk_min(ka, kb);
-            S[ib] = pk_max(ka, kb);
-        });
-        static_for<QN::net.n1>([&](auto I) {
-            constexpr int ia = QN::net.a1[I], ib = QN::net.b1[I];
-            const unsigned ka = S[ia], kb = S[ib];
-            S[ia] = pk_min(ka, kb);
-            S[ib] = pk_max(ka, kb);
-        });
+        pk_compare_exchange<net_holder<NT>, NC>(S);
+        pk_compare_exchange<STAGE1>(S);
         __builtin_amdgcn_sched_barrier(0);
     };
-    // slot S on the array X whose first NS registers hold core + strip (logical order: order1)
+    // slot S on the array X whose first NS registers hold core + strip (logical order: STAGE1's)
     auto slot = [&](auto s_t, unsigned (&X)[NK]) {
         constexpr int S = decltype(s_t)::value;
         {
             long long lo = 0, hi = 0;
-            gq_build<G, 3 + S, NS, NK, true>(P, hq2, hq1, X, lo, hi);
+            glcm_build_keys<gq_where<G, 3 + S>, NO, NS>(P, X, split, lo, hi);
             constexpr int PART = G == 0 ? (S == 1 ? 2 : (S == 2 ? 1 : S)) : S;
             Hq[S] += lo;
             Hq[PART] += hi;
         }
-        static_for<net_holder<NO>::net.n>([&](auto I) {
-            constexpr int ia = NS + net_holder<NO>::net.a[I], ib = NS + net_holder<NO>::net.b[I];
-            const unsigned ka = X[ia], kb = X[ib];
-            X[ia] = pk_min(ka, kb);
-            X[ib] = pk_max(ka, kb);
-        });
-        static_for<QN::net.n2>([&](auto I) {
-            constexpr int ia = QN::net.a2[I], ib = QN::net.b2[I];
-            const unsigned ka = X[ia], kb = X[ib];
-            X[ia] = pk_min(ka, kb);
-            X[ib] = pk_max(ka, kb);
-        });
-        const unsigned one = 0x00010001u;
-        unsigned E2 = 0, t = 0, D = X[QN::net.order2[0]] & one;
-        static_for<NK - 1>([&](auto I) {
-            constexpr int i = QN::net.order2[I + 1], j = QN::net.order2[I];
-            const unsigned diag = X[i] & one;
-            const unsigned eq = pk_sub_sat(one, X[i] ^ X[j]);
-            t = pk_mul(t + one + diag, eq);
-            E2 += t;
-            D += diag;
-        });
+        pk_compare_exchange<net_holder<NO>, NS>(X);
+        pk_compare_exchange<STAGE2>(X);
+        unsigned E2, D;
+        pk_runlength<order_of<STAGE2>>(X, E2, D);
         ED[S] = D + (E2 << 1);
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -974,7 +665,7 @@ __device__ __forceinline__ void gq_group(const unsigned (&P)[8][2], const long l
 // shifted forms of a row (bytes 0..5, bytes 1..6) serve the 0, 45 and 135 degree pairs alike.  All sums are exact unsigned
 // integers: the same values as row_moments / window_m1m2 give window by window.
 struct gq_moments {
-    unsigned S1g0, S1g1, XY[4], m1[4], m2[4];   // as gp_finish_stats takes them
+    unsigned S1g0, S1g1, XY[4], m1[4], m2[4];   // as glcm_finish_stats takes them
 };
 __device__ __forceinline__ void gq_column_moments(const unsigned (&a)[8][2], gq_moments (&m)[2])
 {
@@ -1072,14 +763,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     __shared__ long long hq1[32];
     // the square roots of the energy sums come from a table (g_glcm_sqrt): four reads per window instead of four float64 sqrt
     __shared__ __attribute__((aligned(16))) double sqt[GLCM_SQRT_N];
-    // unrolled and without a bounds test: the loads of the three tables are requested back to back, one memory round trip
-    // instead of one per piece
-#pragma unroll
-    for (int k = 0; k < GLCM_SQRT_N / 512; k++)
-        reinterpret_cast<double2 *>(sqt)[k * 256 + threadIdx.x] = reinterpret_cast<const double2 *>(g_glcm_sqrt)[k * 256 + threadIdx.x];
-#pragma unroll
-    for (int k = 0; k < 4; k++) hq2[k * 256 + threadIdx.x] = g_glcm_hq2[k * 256 + threadIdx.x];
-    if (threadIdx.x < 32) hq1[threadIdx.x] = c_glcm_hq[threadIdx.x];
+    glcm_stage_sqrt(sqt);
+    glcm_stage_hq2<true>(hq2);
+    glcm_stage_hq(hq1);
     __syncthreads();
     // The window coordinates are needed at the two ends of the kernel only.  Kept in vector registers they (or the thread id
     // they come from) were spilled to scratch memory at the 168-register budget: 3 dwords per thread, +2 B/px of HBM writes in
@@ -1122,7 +808,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     long long Hq[2][4];
 #pragma nounroll
     for (int g = 0; g < 2; g++) {
-        opaque_patch<8>(P);
+        opaque_rows<8>(P);
         if (g == 0) gq_group<0>(P, hq2, hq1, ED[0], Hq[0]);
         else gq_group<1>(P, hq2, hq1, ED[1], Hq[1]);
     }
@@ -1153,7 +839,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #endif
         const bool odd = sh != 0;
         unsigned a[8][2];
-        opaque_patch<8>(P);
+        opaque_rows<8>(P);
         static_for<8>([&](auto I) {     // patch columns dx .. dx + 6 of every row
             constexpr int r = I;
             a[r][0] = __builtin_amdgcn_alignbit(P[r][1], P[r][0], (unsigned)sh);
@@ -1168,14 +854,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                 const unsigned e1 = odd ? ED[1][2 * dy + 1] : ED[1][2 * dy];
                 const long long h0 = odd ? Hq[0][2 * dy + 1] : Hq[0][2 * dy], h1 = odd ? Hq[1][2 * dy + 1] : Hq[1][2 * dy];
                 const double sq0 = root_sum(42, e0l, e0h), sq1 = root_sum(36, e1, e1);
-                gp_finish_stats(mo[dy].S1g0, mo[dy].S1g1, mo[dy].XY, mo[dy].m1, mo[dy].m2, h0, sq0, h1, sq1,
+                glcm_finish_stats<7, SH>(mo[dy].S1g0, mo[dy].S1g1, mo[dy].XY, mo[dy].m1, mo[dy].m2, h0, sq0, h1, sq1,
                                 (size_t)(oy + dy) * ow + (ox + dx), out, gc);
             }
         });
     }
 }
 
-// one workgroup per window; LDS histogram of ordered cells [levels][levels]
+// ---- LDS histogram kernels --------------------------------------------------------------------------------------
+// the pairs (r, c)-(r + dr, c + dc) of angle a (0, 45, 90, 135 degrees) in a window: np of them, pw per row, c from c0
+struct glcm_angle {
+    int dr, dc, c0, pw, np;
+};
+__device__ __forceinline__ glcm_angle glcm_angle_geometry(int a, int win)
+{
+    const int dr = a == 0 ? 0 : 1, dc = a == 0 ? 1 : (a == 1 ? 1 : (a == 2 ? 0 : -1));
+    const int r1 = dr > 0 ? win - dr : win, c0 = dc < 0 ? -dc : 0, c1 = dc > 0 ? win - dc : win;
+    const int pw = c1 - c0;
+    return glcm_angle{dr, dc, c0, pw, r1 * pw};
+}
+
 // One WAVE per window (levels <= 32, any window size < 256): the four angles' co-occurrence counts live in four private
 // 2 KB LDS tables of packed 16-bit counters (a window has fewer than 65536 pairs); no workgroup barrier anywhere — a wave's
 // LDS operations execute in order, so its own atomics are complete before its reads.  This is the reference's default
@@ -1199,9 +897,8 @@ __global__ __launch_bounds__(256) void k4_glcm_wave(const uint8_t *__restrict__ 
     long long sums[4][6];  // per angle: S1 S2 Hq M1 M2 Mx (this lane's share)
     glcm_hq_sum hqs[4];    // SPLIT: per angle Hq split (k4_glcm.h), reduced exactly however large the window
     for (int a = 0; a < 4; a++) {
-        const int dr = a == 0 ? 0 : 1, dc = a == 0 ? 1 : (a == 1 ? 1 : (a == 2 ? 0 : -1));
-        const int r1 = dr > 0 ? win - dr : win, c0 = dc < 0 ? -dc : 0, c1 = dc > 0 ? win - dc : win;
-        const int pw = c1 - c0, P = r1 * pw;
+        const glcm_angle ga = glcm_angle_geometry(a, win);
+        const int dr = ga.dr, dc = ga.dc, c0 = ga.c0, pw = ga.pw, P = ga.np;
         int s1 = 0, s2 = 0, m1 = 0, m2 = 0, mx = 0;
         long long hq = 0;
         for (int p = lane; p < P; p += 64) {
@@ -1255,6 +952,7 @@ __global__ __launch_bounds__(256) void k4_glcm_wave(const uint8_t *__restrict__ 
     }
 }
 
+// one workgroup per window; LDS histogram of ordered cells [levels][levels]
 __global__ __launch_bounds__(256) void k4_glcm_wg(const uint8_t *__restrict__ q, int H, int W, int levels, int win, int step,
                                                   int oh, int ow, glcm_out out, glcm_consts gc)
 {
@@ -1265,9 +963,8 @@ __global__ __launch_bounds__(256) void k4_glcm_wg(const uint8_t *__restrict__ q,
     const uint8_t *wp = q + (size_t)(oy * step) * W + (size_t)ox * step;
     const int LL = levels * levels;
     for (int a = 0; a < 4; a++) {
-        const int dr = a == 0 ? 0 : 1, dc = a == 0 ? 1 : (a == 1 ? 1 : (a == 2 ? 0 : -1));
-        const int r1 = dr > 0 ? win - dr : win, c0 = dc < 0 ? -dc : 0, c1 = dc > 0 ? win - dc : win;
-        const int pw = c1 - c0, P = r1 * pw;
+        const glcm_angle ga = glcm_angle_geometry(a, win);
+        const int dr = ga.dr, dc = ga.dc, c0 = ga.c0, pw = ga.pw, P = ga.np;
         for (int i = threadIdx.x; i < LL; i += 256) hist[i] = 0;
         __syncthreads();
         long long st[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // np S1 S2 Hq.hi M1 M2 Mx A Hq.lo (Hq split: k4_glcm.h)
