@@ -106,6 +106,18 @@ template <typename T> __device__ __forceinline__ T scaled(T x, T sc, T mn)
     return xs + mn;
 }
 
+// The four-wave sum of this file's kernels, in two halves around the caller's one __syncthreads(): wg_put leaves a wave's sum
+// (wave_sum) in s[wave] — lane 0 writes, both values in one go where a kernel reduces two — and wg_sum adds the four.
+template <typename V> __device__ __forceinline__ void wg_put(V *s, V v)
+{
+    if (lane_id() == 0) s[threadIdx.x >> 6] = v;
+}
+template <typename V> __device__ __forceinline__ void wg_put(V *s0, V v0, V *s1, V v1)
+{
+    if (lane_id() == 0) { s0[threadIdx.x >> 6] = v0; s1[threadIdx.x >> 6] = v1; }
+}
+template <typename V> __device__ __forceinline__ V wg_sum(const V *s) { return s[0] + s[1] + s[2] + s[3]; }
+
 // ------------------------------------------------------------------------------------------------
 // pass A: per-feature min / max (NaN -> 0).  grid (nblk, F); partial[f][blk] = {min, max}
 // ------------------------------------------------------------------------------------------------
@@ -170,11 +182,10 @@ __global__ __launch_bounds__(KM_THREADS) void km_moment(planes_t pl, int64_t n, 
         for (int i = 0; i < PXL; i++)
             if (base + i < n) acc += to_fixed40((double)scaled<T>(v[i], sc, mnv));
     }
-    acc = wave_sum(acc);
     __shared__ long long sacc[4];
-    if (lane_id() == 0) sacc[threadIdx.x >> 6] = acc;
+    wg_put(sacc, wave_sum(acc));
     __syncthreads();
-    if (threadIdx.x == 0) partial[(size_t)f * gridDim.x + blockIdx.x] = sacc[0] + sacc[1] + sacc[2] + sacc[3];
+    if (threadIdx.x == 0) partial[(size_t)f * gridDim.x + blockIdx.x] = wg_sum(sacc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -209,6 +220,19 @@ __global__ void km_gather_row(planes_t pl, int F, int64_t idx, const scaler_t<T>
 // ------------------------------------------------------------------------------------------------
 #define KPP_MAXL 8
 #define KPP_STRIDE (KPP_MAXL + 1)
+
+// Distance closing, written once for the five places that need it (the pending update and the candidate potentials of km_kpp
+// and km_kpp_blk, and km_kpp_chunkq, which re-derives what the next round will store): euclidean_distances' float64
+// "upcast" formula for one pixel rounded to T, np.maximum(-2 x.c + ||c||^2 + ||x||^2, 0) — one operation sequence, so the
+// same bits between the forms and between a round and its sampling step by construction.
+template <typename T> __device__ __forceinline__ T kpp_close(double dot, double cc, double yy)
+{
+    double d = -2.0 * dot;
+    d = d + cc;
+    d = d + yy;
+    const T dt = (T)d;
+    return dt > (T)0 ? dt : (T)0;
+}
 
 template <typename T, int NL, int FR, int MODE>
 __global__ __launch_bounds__(KM_THREADS) void km_kpp(planes_t pl, int F, int64_t n, const scaler_t<T> *__restrict__ sp,
@@ -275,11 +299,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp(planes_t pl, int F, int64_t
             bool moved = MODE != 2;   // MODE 2: did the pending centre come closer to any of the thread's pixels?
 #pragma unroll
             for (int p = 0; p < PXL; p++) {
-                double d = -2.0 * dotp[p];
-                d = d + ccp;
-                d = d + yy[p];
-                T dt = (T)d;
-                dt = dt > (T)0 ? dt : (T)0;
+                T dt = kpp_close<T>(dotp[p], ccp, yy[p]);
                 if constexpr (MODE == 2) {
                     moved = moved || dt < cl[p];
                     dt = cl[p] < dt ? cl[p] : dt;
@@ -306,11 +326,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp(planes_t pl, int F, int64_t
                 const double ccl = cc[l];
 #pragma unroll
                 for (int p = 0; p < PXL; p++) {
-                    double d = -2.0 * dot[l][p];
-                    d = d + ccl;
-                    d = d + yy[p];
-                    T dt = (T)d;
-                    dt = dt > (T)0 ? dt : (T)0;                               // np.maximum(distances, 0)
+                    T dt = kpp_close<T>(dot[l][p], ccl, yy[p]);               // np.maximum(distances, 0)
                     if constexpr (MODE != 0) dt = cl[p] < dt ? cl[p] : dt;    // np.minimum(closest, d)
                     if (FULL || base + p < n) acc[l] += (unsigned long long)to_fixed40((double)dt);
                 }
@@ -351,8 +367,8 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp(planes_t pl, int F, int64_t
 // Sampling step of a k-means++ round on the device (np.searchsorted(stable_cumsum(closest), r), _kmeans.py:243-246, for the
 // chunk the host has already located from the chunk sums).  One workgroup per candidate:
 //   mode 1: km_kpp_chunkq re-derives the current closest-distance values of the chunk [c0, c0 + cn) — what the next km_kpp
-//           round will store for it: with_old ? min(closest, d2(pending, x)) : d2(pending, x), same operation sequence as
-//           km_kpp, so the same bits — as fixed-point integers; km_kpp_sample finds the first pixel whose running sum
+//           round will store for it: with_old ? min(closest, d2(pending, x)) : d2(pending, x), through km_kpp's own
+//           kpp_close, so the same bits — as fixed-point integers; km_kpp_sample finds the first pixel whose running sum
 //           reaches `rem` (the target minus the sum of everything before the chunk) with a two-level search;
 //   mode 2: the pixel is given (np.clip of an index past the end);   mode 0: another rank owns this candidate.
 // Writes out[l] = {global index as double, the F scaled+centred values of that pixel as double}; one device-to-host copy
@@ -386,11 +402,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp_chunkq(planes_t pl, int F, 
         yy = fma(y, y, yy);
         dotp = fma(candT[f * KPP_STRIDE + KPP_MAXL], y, dotp);
     }
-    double d = -2.0 * dotp;
-    d = d + ccp;
-    d = d + yy;
-    T dt = (T)d;
-    dt = dt > (T)0 ? dt : (T)0;
+    T dt = kpp_close<T>(dotp, ccp, yy);
     if (a.with_old) {
         const T c = closest[c0 + i];
         dt = c < dt ? c : dt;
@@ -649,9 +661,8 @@ __global__ __launch_bounds__(KM_THREADS) void km_lloyd(planes_t pl, int F, int k
         else tile_body(std::false_type{}, base);
     }
     if (UPDATE) {
-        int ch = wave_sum(my_changed);
         __shared__ int changed_w[4];
-        if (lane == 0) changed_w[threadIdx.x >> 6] = ch;
+        wg_put(changed_w, wave_sum(my_changed));
         __syncthreads();
         const int M = KMAX * F + KMAX + 1;
         for (int i = threadIdx.x; i < M; i += KM_THREADS) {
@@ -666,7 +677,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_lloyd(planes_t pl, int F, int k
                 }
                 v = (long long)a;
             } else {
-                v = changed_w[0] + changed_w[1] + changed_w[2] + changed_w[3];
+                v = wg_sum(changed_w);
             }
             partial[(size_t)i * nchunks + blockIdx.x] = v;
         }
@@ -680,6 +691,12 @@ __global__ __launch_bounds__(KM_THREADS) void km_lloyd(planes_t pl, int F, int k
 // across the blocks in the same per-feature fma order as the register-resident kernels — same bits — and the Lloyd
 // update re-reads the blocks after the argmin (the second read of a tile comes from the L2: 2 x 4F B/px requested,
 // not an HBM-bound path any more but the same arithmetic).
+// Shared with the register-resident kernels as ONE definition: the distance closing (kpp_close) and the four-wave sum of
+// the Lloyd `changed` row (wg_put / wg_sum).  The other steps (per-feature accumulation, pending update, potentials, argmin,
+// label step, accumulation, zeroing, epilogues, chunk walk) stay written out in both forms: behind a function — even the
+// whole unchanged body behind a forced-inline wrapper — the compiler emits other code objects for the register-resident
+// kernels (a dead ragged-tile store dropped, 9 -> 39 scalar spills in km_kpp<float, 4, 16, 2>, ...), and those are
+// pinned.  Whoever changes a step in one form changes it in the other.
 // ------------------------------------------------------------------------------------------------
 #define KM_FB 16
 
@@ -720,11 +737,10 @@ __global__ __launch_bounds__(KM_THREADS) void km_var(planes_t pl, int64_t n, con
                 acc += to_fixed40((double)dd);
             }
     }
-    acc = wave_sum(acc);
     __shared__ long long sacc[4];
-    if (lane_id() == 0) sacc[threadIdx.x >> 6] = acc;
+    wg_put(sacc, wave_sum(acc));
     __syncthreads();
-    if (threadIdx.x == 0) partial[(size_t)(1 + f) * nchunks + blockIdx.x] = (unsigned long long)(sacc[0] + sacc[1] + sacc[2] + sacc[3]);
+    if (threadIdx.x == 0) partial[(size_t)(1 + f) * nchunks + blockIdx.x] = (unsigned long long)wg_sum(sacc);
 }
 
 // km_kpp for F > 32 (MODE 0 without the variance rows: km_var writes them)
@@ -781,11 +797,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp_blk(planes_t pl, int F, int
             bool moved = MODE != 2;   // MODE 2: did the pending centre come closer to any of the thread's pixels?
 #pragma unroll
             for (int p = 0; p < PXL; p++) {
-                double d = -2.0 * dotp[p];
-                d = d + ccp;
-                d = d + yy[p];
-                T dt = (T)d;
-                dt = dt > (T)0 ? dt : (T)0;
+                T dt = kpp_close<T>(dotp[p], ccp, yy[p]);
                 if constexpr (MODE == 2) {
                     moved = moved || dt < cl[p];
                     dt = cl[p] < dt ? cl[p] : dt;
@@ -812,11 +824,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp_blk(planes_t pl, int F, int
                 const double ccl = cc[l];
 #pragma unroll
                 for (int p = 0; p < PXL; p++) {
-                    double d = -2.0 * dot[l][p];
-                    d = d + ccl;
-                    d = d + yy[p];
-                    T dt = (T)d;
-                    dt = dt > (T)0 ? dt : (T)0;
+                    T dt = kpp_close<T>(dot[l][p], ccl, yy[p]);
                     if constexpr (MODE != 0) dt = cl[p] < dt ? cl[p] : dt;
                     if (FULL || base + p < n) acc[l] += (unsigned long long)to_fixed40((double)dt);
                 }
@@ -957,9 +965,8 @@ __global__ __launch_bounds__(KM_THREADS) void km_lloyd_blk(planes_t pl, int F, i
         else tile_body(std::false_type{}, base);
     }
     if (UPDATE) {
-        int ch = wave_sum(my_changed);
         __shared__ int changed_w[4];
-        if (lane == 0) changed_w[threadIdx.x >> 6] = ch;
+        wg_put(changed_w, wave_sum(my_changed));
         __syncthreads();
         const int M = KMAX * F + KMAX + 1;
         for (int i = threadIdx.x; i < M; i += KM_THREADS) {
@@ -969,7 +976,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_lloyd_blk(planes_t pl, int F, i
                 for (int c = 0; c < ncopies; c++) a += S[(size_t)c * stride + i];
                 v = (long long)a;
             } else {
-                v = changed_w[0] + changed_w[1] + changed_w[2] + changed_w[3];
+                v = wg_sum(changed_w);
             }
             partial[(size_t)i * nchunks + blockIdx.x] = v;
         }
@@ -1082,14 +1089,12 @@ __global__ __launch_bounds__(KM_THREADS) void km_reduce_cols(const long long *__
         hi += v >> 32;
         lo += v & 0xffffffffLL;
     }
-    hi = wave_sum(hi);
-    lo = wave_sum(lo);
     __shared__ long long sh[4], sl[4];
-    if (lane_id() == 0) { sh[threadIdx.x >> 6] = hi; sl[threadIdx.x >> 6] = lo; }
+    wg_put(sh, wave_sum(hi), sl, wave_sum(lo));
     __syncthreads();
     if (threadIdx.x == 0) {
-        out[2 * (m * ostride + ooff)] = sh[0] + sh[1] + sh[2] + sh[3];
-        out[2 * (m * ostride + ooff) + 1] = sl[0] + sl[1] + sl[2] + sl[3];
+        out[2 * (m * ostride + ooff)] = wg_sum(sh);
+        out[2 * (m * ostride + ooff) + 1] = wg_sum(sl);
     }
 }
 
@@ -1161,10 +1166,15 @@ __global__ __launch_bounds__(KM_THREADS) void kl_prepare(const km_state<T> *__re
     kl_fill_cenT<T>(st, k, F, KMAX, cenT);
 }
 
-__device__ __forceinline__ i128 dev_limbs(long long hi, long long lo) { return ((i128)hi << 32) + (i128)lo; }
-template <typename T> __device__ __forceinline__ T dev_fixed_to_T(i128 s) { return (T)((double)s * (1.0 / 1099511627776.0)); }
+// ---- used by the control kernels below and by the host path (host_iteration): one definition each, so the same operations ----
+// combine {hi, lo} limb sums (km_reduce_cols) into one signed 128-bit value; kc_ulimbs: the unsigned sums of k-means++
+__host__ __device__ __forceinline__ i128 limbs(long long hi, long long lo) { return ((i128)hi << 32) + (i128)lo; }
+__device__ __forceinline__ u128 kc_ulimbs(long long hi, long long lo) { return ((u128)(unsigned long long)hi << 32) + (u128)(unsigned long long)lo; }
+template <typename T> __host__ __device__ __forceinline__ T fixed_to_T(i128 s) { return (T)((double)s * (1.0 / 1099511627776.0)); }
 
-template <typename T> __device__ T dev_pairwise_sum(const T *a, int n)   // numpy pairwise sum, n <= 128
+// numpy pairwise sum over a run-time array, n <= 128.  (np_pairwise_sum_dev above is the same order fully unrolled over a
+// register array: km_farthest's FR squared differences must not be indexed at run time, or they would go to scratch.)
+template <typename T> __host__ __device__ T np_pairwise_sum(const T *a, int n)
 {
     if (n < 8) {
         T res = (T)0;
@@ -1195,7 +1205,7 @@ __global__ __launch_bounds__(KM_THREADS) void kl_update(km_state<T> *st, int k, 
     if (threadIdx.x == 0) n_empty = 0;
     __syncthreads();
     if ((int)threadIdx.x < k) {
-        const long long c = (long long)dev_limbs(red[2 * (KMAX * F + threadIdx.x)], red[2 * (KMAX * F + threadIdx.x) + 1]);
+        const long long c = (long long)limbs(red[2 * (KMAX * F + threadIdx.x)], red[2 * (KMAX * F + threadIdx.x) + 1]);
         cnt[threadIdx.x] = c;
         if (c == 0) atomicAdd(&n_empty, 1);
     }
@@ -1213,7 +1223,7 @@ __global__ __launch_bounds__(KM_THREADS) void kl_update(km_state<T> *st, int k, 
         const int j = i / F, f = i - j * F;
         const T w = (T)cnt[j];
         const T alpha = (T)(1.0 / (double)w);
-        const T sT = dev_fixed_to_T<T>(dev_limbs(red[2 * (j * F + f)], red[2 * (j * F + f) + 1]));
+        const T sT = fixed_to_T<T>(limbs(red[2 * (j * F + f)], red[2 * (j * F + f) + 1]));
         const T cnew = sT * alpha;
         const T d = cnew - st->C[j][f];
         dsq[i] = d * d;
@@ -1237,13 +1247,13 @@ __global__ __launch_bounds__(KM_THREADS) void kl_update(km_state<T> *st, int k, 
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const long long changed = (long long)dev_limbs(red[2 * (KMAX * F + KMAX)], red[2 * (KMAX * F + KMAX) + 1]);
+        const long long changed = (long long)limbs(red[2 * (KMAX * F + KMAX)], red[2 * (KMAX * F + KMAX) + 1]);
         const int it = st->it + 1;
         st->it = it;
         int done = 0;
         if (changed == 0) done = 1;
         else {
-            const T tot = dev_pairwise_sum<T>(shift2, k);
+            const T tot = np_pairwise_sum<T>(shift2, k);
             if (tot <= st->tol) done = 2;
             else if (it >= st->max_iter) done = 4;
         }
@@ -1277,7 +1287,6 @@ __device__ __forceinline__ u128 kc_ceil_scaled(double r)
     const unsigned long long q = m >> sh, rem = m & ((1ull << sh) - 1ull);
     return (u128)q + (rem ? 1 : 0);
 }
-__device__ __forceinline__ u128 kc_ulimbs(long long hi, long long lo) { return ((u128)(unsigned long long)hi << 32) + (u128)(unsigned long long)lo; }
 
 // the (not yet centred) row of the first centre as bit patterns behind the F limb pairs of the column sums (which
 // km_reduce_cols leaves in x[0 .. 2F) from km_moment's block partials)
@@ -1304,7 +1313,7 @@ __global__ __launch_bounds__(KM_THREADS) void kc_mean_apply(km_state<T> *__restr
     const T Nt = (T)st->N;
     if ((int)threadIdx.x < F) {
         const int f = threadIdx.x;
-        const T sT = dev_fixed_to_T<T>(dev_limbs(x[2 * f], x[2 * f + 1]));
+        const T sT = fixed_to_T<T>(limbs(x[2 * f], x[2 * f + 1]));
         const T m = sT / Nt;
         sp->mean[f] = m;
         st->mean[f] = m;
@@ -1329,12 +1338,12 @@ __global__ __launch_bounds__(KM_THREADS) void kc_tol(km_state<T> *__restrict__ s
     const int F = st->F;
     const T Nt = (T)st->N;
     if ((int)threadIdx.x < F) {
-        const T sT = dev_fixed_to_T<T>(dev_limbs(x[2 * threadIdx.x], x[2 * threadIdx.x + 1]));
+        const T sT = fixed_to_T<T>(limbs(x[2 * threadIdx.x], x[2 * threadIdx.x + 1]));
         var[threadIdx.x] = sT / Nt;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const T m = dev_pairwise_sum<T>(var, F);
+        const T m = np_pairwise_sum<T>(var, F);
         const T m2 = m / (T)F;
         st->tol = m2 * (T)st->tol_in;
         u128 total = 0;
@@ -1616,25 +1625,6 @@ int64_t uniform_choice(int64_t n, int dtype, double u)
     return lo;
 }
 
-template <typename T> T np_pairwise_sum(const T *a, int n)
-{
-    if (n < 8) {
-        T res = (T)0;
-        for (int i = 0; i < n; i++) res = res + a[i];
-        return res;
-    }
-    T r[8];
-    for (int j = 0; j < 8; j++) r[j] = a[j];
-    int i;
-    for (i = 8; i < n - (n % 8); i += 8)
-        for (int j = 0; j < 8; j++) r[j] = r[j] + a[i + j];
-    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; i++) res = res + a[i];
-    return res;
-}
-
-template <typename T> T fixed_to_T(i128 s) { return (T)((double)s * (1.0 / 1099511627776.0)); }
-
 template <typename T> struct teps;
 template <> struct teps<float> { static constexpr float v = 1.1920928955078125e-07f; };
 template <> struct teps<double> { static constexpr double v = 2.220446049250313e-16; };
@@ -1643,9 +1633,6 @@ double now_ms()
 {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
-
-// combine {hi, lo} limb sums (km_reduce_cols) into one signed 128-bit value
-i128 limbs(long long hi, long long lo) { return ((i128)hi << 32) + (i128)lo; }
 
 // ---- the launch table: which instantiation serves (T, KMAX, F) ----
 // A kernel holds FR = 8, 16 or 32 planes of its pixels in registers, or KM_BLOCKED for 33 ... RSSEG_MAX_FEATURES planes:

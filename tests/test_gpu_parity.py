@@ -592,6 +592,30 @@ def test_kmeans_float64_planes_with_more_than_32_clusters(ctx, oracle, n, F, k):
     assert meta32["n_iter"] == info32["n_iter"] and np.array_equal(host(labels32), want32)
 
 
+def test_kmeans_both_lloyd_forms_give_the_same_fit(ctx, oracle):
+    """The same data through both Lloyd forms: float64, k = 40 (KMAX = 64), where 8 planes take the register-resident kernel
+    and 9 planes the feature-blocked one.  The 9th plane is constant: it scales to a constant and centres to exactly 0, adds
+    exactly 0 to every dot product, norm, distance and centre shift, so the two fits must agree bit for bit — seeds, iteration
+    count, labels — with each other and with the oracle.  (The tolerance differs, np.var being averaged over 9 planes instead
+    of 8: this fit ends on unchanged labels, which the oracle's equal iteration counts confirm.)  n = 1100: two full float64
+    tiles of 512 pixels and a ragged third, one chunk."""
+    n, k = 1100, 40
+    rng = np.random.default_rng(1100 + 40)
+    planes8 = [rng.random(n) for _ in range(8)]
+    planes9 = planes8 + [np.full(n, 0.25)]
+    want8, info8 = oracle.kmeans_fit_planes(planes8, k)
+    want9, info9 = oracle.kmeans_fit_planes(planes9, k)
+    assert info8["n_iter"] == info9["n_iter"] and np.array_equal(info8["init_indices"], info9["init_indices"])
+    assert np.array_equal(want8, want9)
+    labels8, meta8 = ctx.kmeans_fit_predict([dev(ctx, p) for p in planes8], k)
+    labels9, meta9 = ctx.kmeans_fit_predict([dev(ctx, p) for p in planes9], k)
+    assert planes9[8].dtype == np.float64 and meta8["n_iter"] == meta9["n_iter"] == info8["n_iter"]
+    assert np.array_equal(meta8["init_indices"], meta9["init_indices"])
+    assert np.array_equal(meta8["init_indices"], info8["init_indices"])
+    assert np.array_equal(host(labels8), host(labels9))
+    assert np.array_equal(host(labels8), want8)
+
+
 def test_kmeans_errors(ctx):
     x = dev(ctx, np.zeros(3, np.float32))
     with pytest.raises(ValueError):
