@@ -345,6 +345,24 @@ int rsseg_forest_load(rsseg_ctx *ctx, int n_trees, const int64_t *tree_off, cons
 /* predict_image (modules/supervised_classifiers.py:99-115) / supervised_classification_predict
  * (modules/features/extract.py:690-719): d_planes[F] float32 feature planes -> int64 class per pixel. */
 int rsseg_forest_predict(rsseg_ctx *ctx, const float *const *d_planes, int F, int64_t n, int64_t *d_out);
+/* RandomForestClassifier.predict_proba of the loaded forest (sklearn/ensemble/_forest.py:908-946), bit for bit: the leaf
+ * rows of the trees added in tree order in float64, divided by the tree count.  One launch fills what is asked for:
+ *   d_proba   [n_classes][n] float64, class-planar (class c of pixel i at c * n + i; the forest's own classes, no padding)
+ *   d_conf    [n] float64, the largest class probability of the pixel
+ *   d_labels  [n] int64, exactly what rsseg_forest_predict writes (first maximum on ties)
+ * Any of the three may be null, not all three.  Errors are status codes (RSSEG_ERR_INVALID: no forest loaded, F is not the
+ * forest's feature count, a null plane, every output null); n == 0 returns RSSEG_OK and touches nothing.
+ * Profiler name "forest_proba". */
+int rsseg_forest_predict_proba(rsseg_ctx *ctx, const float *const *d_planes, int F, int64_t n, double *d_proba, double *d_conf,
+                               int64_t *d_labels);
+/* The out-of-bag sums of the loaded forest over its own training samples (ForestClassifier._compute_oob_predictions,
+ * _forest.py:558-622).  d_counts: [n_trees][n] int32 bootstrap counts, the layout rsseg_forest_fit takes; tree t votes for
+ * sample i only where d_counts[t * n + i] == 0.  d_oob: [n_classes][n] float64, the sum of those trees' leaf rows in tree
+ * order divided by max(number of such trees, 1); d_n_oob: [n] int32, that number (0: no tree left the sample out, the
+ * row of d_oob is all zero).  RSSEG_ERR_INVALID as above, and for null counts or a null output; n == 0 returns RSSEG_OK.
+ * Profiler name "forest_oob". */
+int rsseg_forest_oob(rsseg_ctx *ctx, const float *const *d_planes, int F, int64_t n, const int32_t *d_counts, double *d_oob,
+                     int32_t *d_n_oob);
 
 /* ---- K16: random-forest training ------------------------------------------------------------ */
 /* RandomForestClassifier(criterion='gini', splitter='best').fit of scikit-learn 1.7.2 on float32 features, tree for tree

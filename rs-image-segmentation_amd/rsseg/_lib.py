@@ -115,6 +115,8 @@ SIGNATURES = {
                                  C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint8),
                                  C.POINTER(C.c_double), _int, C.POINTER(_i64), _int]),
     "rsseg_forest_predict": (_int, [_vp, _PP, _int, _i64, _vp]),
+    "rsseg_forest_predict_proba": (_int, [_vp, _PP, _int, _i64, _vp, _vp, _vp]),
+    "rsseg_forest_oob": (_int, [_vp, _PP, _int, _i64, _vp, _vp, _vp]),
     "rsseg_forest_fit": (_int, [_vp, _PP, _int, _i64, _vp, _int, _vp, _int, _int, C.POINTER(C.c_uint32), _int, _int, _int, _int,
                                 C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64),
                                 C.POINTER(C.c_int32)]),

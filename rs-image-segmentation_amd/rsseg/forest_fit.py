@@ -8,6 +8,8 @@ the parameter resolution of tree/_classes.py, the tree seeds (ensemble/_base.py:
 (ensemble/_forest.py:124-133, 176-179) and each splitter's xorshift seed (tree/_splitter.pyx:160); the device grows the
 trees; the host assembles DecisionTreeClassifier objects from the node arrays.  Settings K16 does not implement raise
 RssegUnsupported naming the parameter (callers that want the reference's behaviour anyway fall back to `clf.fit`).
+`fit_oob(estimator, X, y)` is `fit` for oob_score=True (or a callable): the grown forest walks its own training planes
+(K11, rsseg_forest_oob) and the estimator gets scikit-learn's oob_decision_function_ and oob_score_, bit for bit.
 """
 from __future__ import annotations
 
@@ -174,10 +176,13 @@ def assemble_forest(estimator, trees_nodes, seeds, n_samples: int, n_features: i
     estimator.n_classes_ = C
 
 
-def fit(estimator, X, y, ctx=None):
-    """Fits the unfitted RandomForestClassifier `estimator` on the GPU and returns it (bit-identical to estimator.fit(X, y))."""
+def _fit_on_device(estimator, X, y, ctx, before_growing=None):
+    """The steps of `fit`.  Returns what an out-of-bag pass over the training set needs besides the fitted estimator: the
+    context, the device planes and bootstrap counts (uploaded once) and the encoded labels."""
     from .runtime import default_context
     X, y_enc, classes, rp = prepare(estimator, X, y)
+    if before_growing is not None:
+        before_growing()
     n, F = X.shape
     C = len(classes)
     T = int(estimator.n_estimators)
@@ -190,6 +195,7 @@ def fit(estimator, X, y, ctx=None):
     caps = 2 * (m if estimator.bootstrap else np.repeat(m, T)) - 1
     xs = np.array([splitter_seed(int(s)) for s in seeds], np.uint32)
     trees = []
+    planes = d_counts = None
     if T:
         ctx = ctx if ctx is not None else default_context()
         planes = [ctx.upload_f32(np.ascontiguousarray(X[:, f])) for f in range(F)]
@@ -198,4 +204,34 @@ def fit(estimator, X, y, ctx=None):
         trees = ctx.forest_fit(planes, d_y, d_counts, xs, caps, rp["max_depth"], rp["min_samples_split"], rp["min_samples_leaf"],
                                rp["max_features"], C)
     assemble_forest(estimator, trees, seeds, n, F, classes, rp["max_features"])
+    return estimator, ctx, planes, d_counts, y_enc
+
+
+def fit(estimator, X, y, ctx=None):
+    """Fits the unfitted RandomForestClassifier `estimator` on the GPU and returns it (bit-identical to estimator.fit(X, y))."""
+    return _fit_on_device(estimator, X, y, ctx)[0]
+
+
+def fit_oob(estimator, X, y, ctx=None):
+    """`fit` for an estimator whose oob_score is True or a callable: the forest is grown as `fit` grows it (the setting held
+    aside meanwhile, so `prepare` and `check_supported` keep refusing it), then loaded and walked over the training
+    planes by rsseg_forest_oob with the bootstrap counts already on the device, and the host finishes as
+    _forest.py:558-622, 805-827 do.  Returns the estimator with oob_decision_function_ and oob_score_ set and the
+    parameter restored: its whole state equals RandomForestClassifier(oob_score=...).fit(X, y)."""
+    from .forest import _flat_for_proba, oob_device, oob_finish
+    scoring = estimator.oob_score
+    if not (scoring is True or callable(scoring)):
+        raise ValueError(f"fit_oob: oob_score={scoring!r}: True or a callable (use fit otherwise)")
+
+    def bootstrap_needed():   # where RandomForestClassifier.fit raises it: after the validation of X and y (_forest.py:446)
+        if not estimator.bootstrap:
+            raise ValueError("Out of bag estimation only available if bootstrap=True")
+
+    estimator.oob_score = False
+    try:
+        _, ctx, planes, d_counts, y_enc = _fit_on_device(estimator, X, y, ctx, before_growing=bootstrap_needed)
+    finally:
+        estimator.oob_score = scoring
+    oob, n_oob = oob_device(ctx, _flat_for_proba(estimator), planes, d_counts)
+    estimator.oob_decision_function_, estimator.oob_score_ = oob_finish(oob, n_oob, y_enc, None if scoring is True else scoring)
     return estimator

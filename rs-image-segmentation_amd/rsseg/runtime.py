@@ -727,6 +727,7 @@ class Context:
                                              keep[2].ctypes.data_as(ip), keep[3].ctypes.data_as(ip), keep[4].ctypes.data_as(dp),
                                              keep[5].ctypes.data_as(C.POINTER(C.c_uint8)), keep[6].ctypes.data_as(dp),
                                              keep[6].shape[1], keep[7].ctypes.data_as(lp), int(f["n_features"])))
+        self._forest_shape = (len(keep[0]) - 1, int(keep[6].shape[1]), int(f["n_features"]))   # trees, classes, features
 
     def forest_predict(self, planes: Sequence):
         torch = _torch()
@@ -734,6 +735,37 @@ class Context:
         out = self.empty(n, torch.int64)
         self._chk(self.lib.rsseg_forest_predict(self.h, self._pp(planes), len(planes), n, C.c_void_p(out.data_ptr())))
         return out
+
+    def forest_predict_proba(self, planes: Sequence, proba: bool = True, confidence: bool = False, labels: bool = False):
+        """rsseg_forest_predict_proba on the loaded forest, one launch for what is asked for.  Returns the device tensors
+        (proba, confidence, labels), None for an output not asked for: proba float64 of shape (n_classes, n), class-planar
+        (`.t()` is predict_proba's layout); confidence float64 (n,), the largest class probability; labels int64 (n,), what
+        forest_predict returns."""
+        torch = _torch()
+        n = planes[0].numel()
+        nc = getattr(self, "_forest_shape", (0, 1, 0))[1]   # without a forest the library refuses the call
+        p = self.empty(nc * n, torch.float64) if proba else None
+        c = self.empty(n, torch.float64) if confidence else None
+        lab = self.empty(n, torch.int64) if labels else None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+        self._chk(self.lib.rsseg_forest_predict_proba(self.h, self._pp(planes), len(planes), n, ptr(p), ptr(c), ptr(lab)))
+        return (None if p is None else p.view(nc, n)), c, lab
+
+    def forest_oob(self, planes: Sequence, counts):
+        """rsseg_forest_oob on the loaded forest over its training samples.  counts: int32 device tensor of n_trees * n
+        bootstrap counts, tree after tree (what forest_fit takes).  Returns the device tensors (oob, n_oob): oob float64 of
+        shape (n_classes, n), the leaf rows of the trees that never drew the sample summed in tree order and divided by
+        max(n_oob, 1); n_oob int32 (n,), the number of those trees."""
+        torch = _torch()
+        n = planes[0].numel()
+        nt, nc, _ = getattr(self, "_forest_shape", (0, 1, 0))
+        if counts is not None and (counts.dtype != torch.int32 or counts.numel() != nt * n or not counts.is_contiguous()):
+            raise ValueError(f"forest_oob: counts must be {nt} x {n} contiguous int32 values (one row per tree of the loaded forest)")
+        oob = self.empty(nc * n, torch.float64)
+        n_oob = self.empty(n, torch.int32)
+        self._chk(self.lib.rsseg_forest_oob(self.h, self._pp(planes), len(planes), n, None if counts is None else C.c_void_p(counts.data_ptr()),
+                                            C.c_void_p(oob.data_ptr()), C.c_void_p(n_oob.data_ptr())))
+        return oob.view(nc, n), n_oob
 
     # ---- K16 -----------------------------------------------------------------------------------
     def forest_fit(self, planes: Sequence, y, counts, seeds: np.ndarray, node_caps: np.ndarray, max_depth: int,

@@ -173,7 +173,25 @@ def run_classification_stage(feature_file_path, method='rule_based', output_dir=
     Writes <output_dir>/classification_<method>.npy and, when the feature file carries transform / crs / width / height
     (scripts/3:495-498), <output_dir>/<method>_classification_map.tif (uint8 labels, nodata 0, LZW tiles); the PNG of
     scripts/3:491 is plotting (out of scope).  The reference returns None; this returns the label map as well (None on the
-    reference's error paths, which print and return)."""
+    reference's error paths, which print and return).  run_forest_confidence_stage is the 'random_forest' branch with the
+    class probabilities and the confidence map written beside the class map."""
+    return _run_classification(feature_file_path, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys,
+                               labeled_roi_file, strict_reference, ctx, False)
+
+
+def run_forest_confidence_stage(feature_file_path, output_dir="segmentation_outputs", use_hierarchical_all=True, *, classifier=None,
+                                labeled_roi_file: str = "labeled_roi.tif", ctx: Optional[Context] = None) -> Optional[np.ndarray]:
+    """run_classification_stage(feature_file_path, 'random_forest', ...) with confidence: every file of that call, unchanged,
+    and beside them <output_dir>/rf_class_probabilities.npy, (H, W, C) float64 = the forest's predict_proba of every pixel in
+    the order of classes_, <output_dir>/rf_confidence.npy, (H, W) float64 = the largest of them, and, with complete
+    metadata, <output_dir>/random_forest_confidence_map.tif (float64, LZW tiles).  Returns the label map.  (A function of
+    its own: the signature of run_classification_stage is the reference's plus a fixed set of keyword-only additions.)"""
+    return _run_classification(feature_file_path, "random_forest", output_dir, use_hierarchical_all, 7, classifier, None,
+                               labeled_roi_file, False, ctx, True)
+
+
+def _run_classification(feature_file_path, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys,
+                        labeled_roi_file, strict_reference, ctx, confidence) -> Optional[np.ndarray]:
     from modules.features.extract import load_features, normalize_features_structure, unsupervised_kmeans_classification
     os.makedirs(output_dir, exist_ok=True)
     try:
@@ -199,8 +217,9 @@ def run_classification_stage(feature_file_path, method='rule_based', output_dir=
     if ctx is not None:   # the mirrors run on the process-wide context: lend them this one for the duration of the call
         _rt._default_ctx = ctx
     try:
+        extras = {} if confidence and method in ("random_forest", "rf", "supervised") else None
         out = _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys, labeled_roi_file,
-                        strict_reference)
+                        strict_reference, extras)
     finally:
         _rt._default_ctx = prev_ctx
     if out is None:
@@ -211,11 +230,20 @@ def run_classification_stage(feature_file_path, method='rule_based', output_dir=
         save_classification_as_geotiff(out, feats, os.path.join(output_dir, f"{method}_classification_map.tif"))
     else:
         print("警告: 元数据不完整，无法将分类结果保存为带地理参考的GeoTIFF。")
+    if extras:
+        np.save(os.path.join(output_dir, "rf_class_probabilities.npy"), extras["proba"])
+        np.save(os.path.join(output_dir, "rf_confidence.npy"), extras["confidence"])
+        if all(feats.get(k) is not None for k in ("transform", "crs", "width", "height")):
+            from .tiff import write_tiff
+            write_tiff(os.path.join(output_dir, f"{method}_confidence_map.tif"), extras["confidence"], transform=feats["transform"],
+                       epsg=_epsg_of(feats["crs"]), geographic=_is_geographic(feats["crs"]), compress="lzw", tiled=True)
     return out
 
 
-def _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys, labeled_roi_file, strict_reference):
-    """The dispatch of scripts/3_classification.py:335-488 on a normalised feature dictionary -> label map or None."""
+def _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys, labeled_roi_file, strict_reference,
+              extras=None):
+    """The dispatch of scripts/3_classification.py:335-488 on a normalised feature dictionary -> label map or None.
+    extras: a dict the forest branch fills with 'proba' (H, W, C) and 'confidence' (H, W), or None."""
     from modules.features.extract import (prepare_training_samples, rule_based_classification, supervised_classification_predict,
                                           train_random_forest_classifier, unsupervised_kmeans_classification)
     shape = (feats["height"], feats["width"])
@@ -269,7 +297,11 @@ def _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, class
                 classifier = train_random_forest_classifier(X, y, feature_names_for_training=names)
                 joblib.dump(classifier, model_path)
                 print(f"随机森林模型训练并保存至: {model_path}")
-            return supervised_classification_predict(arr, classifier)
+            out = supervised_classification_predict(arr, classifier)
+            if extras is not None:   # the same pixels as the label map saw: NaN -> 0 (extract.py:690-719)
+                from .forest import image_proba_and_confidence
+                extras["proba"], extras["confidence"] = image_proba_and_confidence(classifier, np.nan_to_num(arr, nan=0.0))
+            return out
         except _rt_unsupported():
             raise
         except Exception as e:  # noqa: BLE001 — scripts/3:482-486 prints and returns
@@ -289,14 +321,17 @@ def _rt_unsupported():
 # scripts/3_classification.py:545-632):   python -m rsseg.stages <image.tif> <output_dir> [--classify kmeans]
 # --------------------------------------------------------------------------------------------------
 def run_scripts_2_3(image_path: str, output_dir: str, classify: Optional[str] = None, preprocessing: bool = True, n_clusters: int = 7,
-                    ctx: Optional[Context] = None, evaluate: Optional[str] = None, raw: bool = False) -> Dict[str, object]:
+                    ctx: Optional[Context] = None, evaluate: Optional[str] = None, raw: bool = False,
+                    confidence: bool = False) -> Dict[str, object]:
     """Reads the GeoTIFF's bands as float32 with nodata -> NaN (scripts/2:154-161), runs the feature stage, writes
     <output_dir>/feature_outputs/{level1,level2,all_hierarchical}_features.npy, all_features_and_metadata.pkl and
     all_hierarchical_features.tif (scripts/2:193-258), then — `classify` in {'kmeans', 'rule_based', 'random_forest'} —
     the classification stage on that pickle into <output_dir>/segmentation_results (scripts/3:548-551), and — `evaluate` naming a
     ROI mask (.npy / .tif) — the accuracy assessment of that class map (scripts/4) into <output_dir>/evaluation_results.
     raw: the image is a raw DN raster: stage 1 (scripts/1) runs first on the device and writes the reference's product,
-    <output_dir>/preprocessed/<stem>_preprocessed.tif, and its uint8 planes go to the feature stage without leaving HBM."""
+    <output_dir>/preprocessed/<stem>_preprocessed.tif, and its uint8 planes go to the feature stage without leaving HBM.
+    confidence: with classify='random_forest', the class probabilities and the confidence map beside the class map
+    (run_forest_confidence_stage)."""
     if raw:
         from .preprocess import run_preprocessing_stage
         pdir = os.path.join(output_dir, "preprocessed")
@@ -324,7 +359,10 @@ def run_scripts_2_3(image_path: str, output_dir: str, classify: Optional[str] = 
         res["preprocessed"] = ppath
     if classify:
         sdir = os.path.join(output_dir, "segmentation_results")
-        res["class_map"] = run_classification_stage(paths["pkl"], classify, sdir, True, n_clusters=n_clusters, ctx=ctx)
+        if confidence and classify == "random_forest":
+            res["class_map"] = run_forest_confidence_stage(paths["pkl"], sdir, True, ctx=ctx)
+        else:
+            res["class_map"] = run_classification_stage(paths["pkl"], classify, sdir, True, n_clusters=n_clusters, ctx=ctx)
         res["segmentation_dir"] = sdir
         if evaluate and res["class_map"] is not None:
             from .evaluate import ClassificationEvaluator
@@ -339,6 +377,8 @@ def parse_args(ap, argv=None):
     a = ap.parse_args(argv)
     if a.evaluate and not a.classify:
         ap.error("--evaluate needs --classify")
+    if a.confidence and a.classify != "random_forest":
+        ap.error("--confidence needs --classify random_forest")
     return a
 
 
@@ -354,13 +394,16 @@ def build_parser():
     ap.add_argument("--evaluate", metavar="ROI_MASK", help="accuracy assessment (scripts/4) of the class map against this ROI mask (.npy / .tif)")
     ap.add_argument("--raw", action="store_true",
                     help="the image is a raw DN raster: run stage 1 (scripts/1) on the GPU first, writing OUTPUT_DIR/preprocessed/<stem>_preprocessed.tif")
+    ap.add_argument("--confidence", action="store_true",
+                    help="with --classify random_forest: also write rf_class_probabilities.npy (H, W, C), rf_confidence.npy and a confidence GeoTIFF")
     return ap
 
 
 def main(argv=None) -> int:
     ap = build_parser()
     a = parse_args(ap, argv)
-    res = run_scripts_2_3(a.image, a.output_dir, a.classify, not a.no_preprocessing, a.n_clusters, evaluate=a.evaluate, raw=a.raw)
+    res = run_scripts_2_3(a.image, a.output_dir, a.classify, not a.no_preprocessing, a.n_clusters, evaluate=a.evaluate, raw=a.raw,
+                          confidence=a.confidence)
     if a.raw:
         print(f"preprocessed: {res['preprocessed']}")
     for k, v in res["paths"].items():
