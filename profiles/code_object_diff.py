@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Per-kernel comparison of two source trees' gfx950 code, without a GPU: every file is compiled to assembly with the
+Makefile's flags (hipcc --cuda-device-only -S) in both trees; per kernel the registers, LDS and scratch bytes of the
+code-object metadata, the waves per SIMD they allow, and whether the instruction sequences (comments, labels' directives and
+blank lines dropped) are equal.
+
+  python profiles/code_object_diff.py <parent csrc dir> <new csrc dir> out.json k5_window.hip k13_texture.hip ..."""
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+def makefile_flags(csrc):
+    """CXXFLAGS of the tree's own Makefile ($(ARCH) filled in from its ARCH line), so the comparison follows the build."""
+    text = open(os.path.join(csrc, "Makefile")).read()
+    arch = re.search(r"^ARCH \?= *(\S+)", text, re.M).group(1)
+    return re.search(r"^CXXFLAGS \?= *(.*)$", text, re.M).group(1).replace("$(ARCH)", arch).split()
+
+
+def asm(csrc, f, tmp, tag):
+    out = os.path.join(tmp, f"{tag}_{f}.s")
+    subprocess.check_call([HIPCC, *makefile_flags(csrc), "--cuda-device-only", "-S", f, "-o", out], cwd=csrc, stderr=subprocess.DEVNULL)
+    return open(out).read()
+
+
+def demangle(names):
+    p = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True)
+    return dict(zip(names, p.stdout.split("\n")))
+
+
+def kernels(text):
+    res = {}
+    for m in re.finditer(r"^(\w+):\s*; @\1\n(.*?)^\s*\.end_amdhsa_kernel", text, re.S | re.M):
+        ins = [ln.split(";")[0].strip() for ln in m.group(2).split("\n")]
+        res[m.group(1)] = {"ins": [i for i in ins if i and not i.startswith(".")]}
+    for m in re.finditer(r"- \.agpr_count:.*?\.name:\s+(\w+).*?\.wavefront_size", text, re.S):
+        blk, name = m.group(0), m.group(1)
+        if name in res:
+            for key, field in (("vgprs", "vgpr_count"), ("agprs", "agpr_count"), ("sgprs", "sgpr_count"), ("lds", "group_segment_fixed_size"),
+                               ("scratch", "private_segment_fixed_size"), ("wg", "max_flat_workgroup_size")):
+                res[name][key] = int(re.search(r"\." + field + r":\s+(\d+)", blk).group(1))
+    return res
+
+
+def waves_per_simd(k):
+    """gfx950: 512 registers per SIMD lane shared by VGPRs and AGPRs in granules of 8, at most 8 waves per SIMD; 160 KB of LDS
+    per CU shared by the workgroups of its 4 SIMDs.  (The SGPR limit and the LDS allocation granule are ignored: neither binds
+    below 100 SGPRs and with tiles of 9-42 KB.)"""
+    regs = -(-k["vgprs"] // 8) * 8 + -(-k["agprs"] // 8) * 8
+    w = min(8, 512 // max(regs, 8))
+    if k["lds"]:
+        w = min(w, (160 * 1024 // k["lds"]) * -(-k["wg"] // 64) // 4)
+    return w
+
+
+def main():
+    parent, new, outp, files = sys.argv[1], sys.argv[2], sys.argv[3], sys.argv[4:]
+    table = []
+    with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(8) as ex:
+        jobs = {(t, f): ex.submit(asm, c, f, tmp, t) for f in files for t, c in (("parent", parent), ("new", new))}
+        for f in files:
+            kp, kn = kernels(jobs[("parent", f)].result()), kernels(jobs[("new", f)].result())
+            assert set(kp) == set(kn), (f, set(kp) ^ set(kn))
+            names = demangle(sorted(kp))
+            for name in sorted(kp):
+                a, b = kp[name], kn[name]
+                row = {"file": f, "kernel": names[name].split("(")[0].replace("void ", "")}
+                for k in ("vgprs", "sgprs", "lds", "scratch"):
+                    row[k] = [a[k], b[k]]
+                row["waves_per_simd"] = [waves_per_simd(a), waves_per_simd(b)]
+                row["instructions"] = [len(a["ins"]), len(b["ins"])]
+                row["identical"] = a["ins"] == b["ins"]
+                row["within_the_rules"] = b["scratch"] == 0 and a["lds"] == b["lds"] and row["waves_per_simd"][1] >= row["waves_per_simd"][0]
+                table.append(row)
+                print(("same " if row["identical"] else "DIFF ") + ("" if row["within_the_rules"] else "RULE ") + json.dumps(row))
+    json.dump(table, open(outp, "w"), indent=1)
+
+
+main()

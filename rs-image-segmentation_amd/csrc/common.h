@@ -123,6 +123,16 @@ static inline float norm_den(float lo, float hi)
     return e;
 }
 
+// inverse of the ordered keys of the extrema slots and of the radix select (mm_key below, f32_key of k1_select.hip):
+// the float whose key this is (keys 0xffffffff / 0, an untouched min / max slot, decode to NaN)
+static inline float mm_unkey(uint32_t key)
+{
+    const uint32_t u = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
 #ifdef __HIPCC__
 // ---- device helpers ---------------------------------------------------------------------------
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }

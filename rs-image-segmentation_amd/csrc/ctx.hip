@@ -423,15 +423,9 @@ int mm_end(rsseg_ctx *ctx, int nplanes)
             k[2 * i + 1] = std::max(k[2 * i + 1], kr[(r * RSSEG_MM_PLANES + i) * 2 + 1]);
         }
     }
-    auto unkey = [](uint32_t key) {
-        uint32_t u = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
-        float f;
-        memcpy(&f, &u, 4);
-        return (double)f;
-    };
     for (int i = 0; i < nplanes && i < RSSEG_MM_PLANES; i++) {
-        ctx->mm_min[i] = unkey(k[2 * i]);      // an untouched slot decodes to NaN (keys 0xffffffff / 0): empty plane
-        ctx->mm_max[i] = unkey(k[2 * i + 1]);
+        ctx->mm_min[i] = mm_unkey(k[2 * i]);      // an untouched slot decodes to NaN (keys 0xffffffff / 0): empty plane
+        ctx->mm_max[i] = mm_unkey(k[2 * i + 1]);
     }
     ctx->mm_count = nplanes < RSSEG_MM_PLANES ? nplanes : RSSEG_MM_PLANES;
     return RSSEG_OK;

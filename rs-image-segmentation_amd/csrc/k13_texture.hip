@@ -17,16 +17,10 @@
 //        (acc + 32768) >> 16; BORDER_REFLECT_101.
 #include <cmath>
 
+#include "border.h"
 #include "common.h"
 
 #define K13_THREADS 256
-
-__device__ __forceinline__ int reflect101(int i, int n)
-{
-    if (n == 1) return 0;
-    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
-    return i;
-}
 
 // ---- uniform LBP ----
 struct lbp_args {
@@ -122,7 +116,7 @@ __global__ __launch_bounds__(K13_THREADS) void k13_gauss_h(const uint8_t *__rest
     for (int64_t i = (int64_t)blockIdx.x * K13_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * K13_THREADS) {
         const int r = (int)(i / W), c = (int)(i - (int64_t)r * W);
         unsigned acc = 0;
-        for (int t = 0; t < g.n; t++) acc += (unsigned)q[(size_t)r * W + reflect101(c + t - R, W)] * g.k[t];
+        for (int t = 0; t < g.n; t++) acc += (unsigned)q[(size_t)r * W + border_idx(c + t - R, W, BORDER_REFLECT_101)] * g.k[t];
         tmp[i] = (unsigned short)acc;   // 8.8 fixed point: at most 255 * 256
     }
 }
@@ -133,7 +127,7 @@ __global__ __launch_bounds__(K13_THREADS) void k13_gauss_v(const unsigned short 
     for (int64_t i = (int64_t)blockIdx.x * K13_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * K13_THREADS) {
         const int r = (int)(i / W), c = (int)(i - (int64_t)r * W);
         unsigned acc = 0;
-        for (int t = 0; t < g.n; t++) acc += (unsigned)tmp[(size_t)reflect101(r + t - R, H) * W + c] * g.k[t];
+        for (int t = 0; t < g.n; t++) acc += (unsigned)tmp[(size_t)border_idx(r + t - R, H, BORDER_REFLECT_101) * W + c] * g.k[t];
         const unsigned v = (acc + 32768u) >> 16;
         out[i] = (uint8_t)(v > 255u ? 255u : v);
     }

@@ -207,14 +207,6 @@ __global__ __launch_bounds__(THREADS) void k1_hist_u8(const uint8_t *__restrict_
     }
 }
 
-static float key_to_f32(uint32_t k)
-{
-    uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
 // All planes advance pass by pass together: ONE device-to-host copy, ONE stream synchronisation and ONE all-reduce
 // per pass for the whole group (3 per group instead of 3 per plane).
 #define SEL_MAX_PLANES 8
@@ -400,7 +392,7 @@ static int order_stats_core(rsseg_ctx *ctx, const float *const *d_planes, int P,
     }
     for (int p = 0; p < P; p++) {
         for (int r = 0; r < nranks; r++)
-            out_values[(size_t)p * nranks + r] = st[p].is_nan_rank[r] ? __builtin_nanf("") : key_to_f32(st[p].prefix[r]);
+            out_values[(size_t)p * nranks + r] = st[p].is_nan_rank[r] ? __builtin_nanf("") : mm_unkey(st[p].prefix[r]);
         if (n_nan_out) n_nan_out[p] = st[p].n_nan;
     }
     return RSSEG_OK;

@@ -13,29 +13,20 @@
 //      min / max; Sobel row terms) and keeps the last K rows of them in a register ring; every row from the K-th on
 //      completes one output row (the K ring entries top to bottom) — the summation order fixed in oracle/ref_np.py, so the
 //      float64 box sums stay bit-exact.
+// Step 1 (stage_tile), the store (row_store) and the float64 order (sum_in_order) are written once for all four kernels.
+// The walk of step 2 is written once (stencil_walk) for k6_box and k7_morph, whose operators (box_op, morph_op) supply the
+// row term and the closing of a column of the ring; k6_std and k8_filter keep it written out: on stencil_walk they gave the
+// same bits, but at 16384^2 their median time lay above the slowest run of the written-out form in two sessions
+// (profiles/window_shared_steps_ab.json: k8_filter<.,0> 0.2857 / 0.5202 ms against 0.2830 / 0.5198, k6_std<5,false>
+// 0.7408 against 0.7402, k6_std<7,true> 0.9517 against 0.9422).
 // HBM traffic is the plane once in, once out (halo re-reads are L2 hits); LDS traffic is 1.3 b128 reads per pixel.
 // Rows form: every operator takes a plane of Hin rows and produces rows [y0, y1) of it, so a rank of a row-sharded
 // raster passes its stripe plus R halo rows and gets exactly the rows of the un-sharded result.
 #include <cmath>
+#include <type_traits>
 
+#include "border.h"
 #include "common.h"
-
-#define BORDER_REPLICATE 2  // internal: erode / dilate (out-of-image taps never win == replicate the edge)
-
-__device__ __forceinline__ int border_idx(int i, int n, int mode)
-{
-    // mode 0: BORDER_REFLECT (edge duplicated), mode 1: BORDER_REFLECT_101, mode 2: replicate
-    if (n == 1) return 0;
-    if (mode == BORDER_REPLICATE) return i < 0 ? 0 : (i >= n ? n - 1 : i);
-    while (i < 0 || i >= n) {
-        if (i < 0) i = mode == 0 ? -i - 1 : -i;
-        else i = mode == 0 ? 2 * n - 1 - i : 2 * n - 2 - i;
-    }
-    return i;
-}
-
-#define WG_X 64
-#define WG_Y 4
 
 // ---- tile geometry of the LDS stencils ---------------------------------------------------------------------------
 #define TW 256                      // output columns per workgroup
@@ -58,14 +49,18 @@ struct win_planes {
 struct tile_map {
     int ntx, nt, chunk;
 };
-static inline tile_map make_tile_map(int nrows, int W)
-{
-    tile_map m;
-    m.ntx = (W + TW - 1) / TW;
-    m.nt = m.ntx * ((nrows + TH - 1) / TH);
-    m.chunk = (m.nt + 7) / 8;
-    return m;
-}
+// tile map and grid of a stencil launch over nrows x W output pixels of nplanes planes
+struct stencil_launch {
+    tile_map tm;
+    dim3 grid;
+    stencil_launch(int nrows, int W, int nplanes = 1)
+    {
+        tm.ntx = (W + TW - 1) / TW;
+        tm.nt = tm.ntx * ((nrows + TH - 1) / TH);
+        tm.chunk = (tm.nt + 7) / 8;
+        grid = dim3(8 * tm.chunk, 1, nplanes);
+    }
+};
 __device__ __forceinline__ bool tile_of_block(const tile_map &m, int &x0, int &ty0)
 {
     const int t = (int)(blockIdx.x & 7u) * m.chunk + (int)(blockIdx.x >> 3);
@@ -76,16 +71,17 @@ __device__ __forceinline__ bool tile_of_block(const tile_map &m, int &x0, int &t
     return true;
 }
 
-template <typename E> struct vec4;
-template <> struct vec4<float> { typedef float4 type; };
-template <> struct vec4<uint8_t> { typedef uint32_t type; };
+// a plane's element type: its 4-element vector in memory and LDS, and the register type the stencils compute in
+template <typename E> struct elem;
+template <> struct elem<float> { typedef float4 vec; typedef float reg; };
+template <> struct elem<uint8_t> { typedef uint32_t vec; typedef int reg; };
 
 // tile[(TH + 2R)][TSTRIDE]: tile row r holds input row border(yb - R + r), tile column c input column x0 - TPAD + c
 // (columns further than R outside the image are never read by the stencil and are left zero)
 template <typename E, int R>
 __device__ __forceinline__ void load_tile(E *__restrict__ tile, const E *__restrict__ x, int Hin, int W, int mode, int x0, int yb)
 {
-    typedef typename vec4<E>::type V;
+    typedef typename elem<E>::vec V;
     constexpr int NR = TH + 2 * R, SLOTS = TSTRIDE / 4;
     const bool vec = (W & 3) == 0 && ((uintptr_t)x & (sizeof(V) - 1)) == 0;
     for (int s = threadIdx.x; s < NR * SLOTS; s += 256) {
@@ -106,6 +102,21 @@ __device__ __forceinline__ void load_tile(E *__restrict__ tile, const E *__restr
         }
         *reinterpret_cast<V *>(tile + r * TSTRIDE + 4 * g) = v;
     }
+}
+
+// Tile staging, once for every stencil: the workgroup's tile (false, for the whole workgroup, when the chunked map gives it
+// none), the tile with its halo in LDS, and the thread's 4 columns (cx) x RPT rows (ry) of it.
+struct tile_pos { int x0, ty0, cx, ry; };
+template <typename E, int R>
+__device__ __forceinline__ bool stage_tile(E *__restrict__ tile, const E *__restrict__ x, int Hin, int W, int y0, int mode, const tile_map &tm,
+                                           tile_pos &t)
+{
+    if (!tile_of_block(tm, t.x0, t.ty0)) return false;
+    load_tile<E, R>(tile, x, Hin, W, mode, t.x0, y0 + t.ty0);
+    __syncthreads();
+    t.cx = (threadIdx.x & 63) * CPT;
+    t.ry = (threadIdx.x >> 6) * RPT;
+    return true;
 }
 
 __device__ __forceinline__ void read12(const float *p, float (&v)[12])
@@ -143,52 +154,93 @@ __device__ __forceinline__ void store4(uint8_t *out, int W, int orow, int col, c
         for (int q = 0; q < 4; q++)
             if (col + q < W) p[q] = (uint8_t)o[q];
 }
+// the usual ending of a walk: the four results of an output row go to the plane, as one vector where W and the pointer allow
+template <typename O> struct row_store {
+    O *out; int W; bool vec;
+    __device__ __forceinline__ row_store(O *out_, int W_) : out(out_), W(W_), vec((W_ & 3) == 0 && ((uintptr_t)out_ & (4 * sizeof(O) - 1)) == 0) {}
+    template <typename V> __device__ __forceinline__ void operator()(int orow, int col, const V (&o)[CPT]) const { store4(out, W, orow, col, o, vec); }
+};
 
-// ---- box mean (optionally of x*x), float64 sums: rows left-to-right, then rows top-to-bottom ----
-template <int K, bool SQ>
-__global__ __launch_bounds__(256) void k6_box(win_planes pl, int Hin, int W, int y0, int nrows, int mode, tile_map tm)
+// The ring walk, once for every stencil.  The thread reads its RPT + 2R tile rows top to bottom; Op::row turns the K values
+// w[0 .. K-1] under a column into that row's horizontal term, kept in a K-deep register ring; from the K-th row on Op::col
+// closes one output row from the ring entries e(0) .. e(K-1), top to bottom, and emit(output row, first column, the four
+// results) ends it.  A thread whose columns or rows lie outside the plane does nothing.
+template <int K, typename Op, typename E, typename Emit>
+__device__ __forceinline__ void stencil_walk(const E *tile, const tile_pos &t, int W, int nrows, Emit emit)
 {
     constexpr int R = K / 2;
-    __shared__ __align__(16) float tile[(TH + 2 * R) * TSTRIDE];
-    const float *x = (const float *)pl.in[blockIdx.z];
-    float *out = (float *)pl.out[blockIdx.z];
-    int x0, ty0;
-    if (!tile_of_block(tm, x0, ty0)) return;
-    load_tile<float, R>(tile, x, Hin, W, mode, x0, y0 + ty0);
-    __syncthreads();
-    const int cx = (threadIdx.x & 63) * CPT, ry = (threadIdx.x >> 6) * RPT;
-    if (x0 + cx >= W || ty0 + ry >= nrows) return;
-    const bool vec = (W & 3) == 0 && ((uintptr_t)out & 15) == 0;
-    double ring[K][CPT];
+    if (t.x0 + t.cx >= W || t.ty0 + t.ry >= nrows) return;
+    typename Op::term ring[K][CPT];
 #pragma unroll
     for (int j = 0; j < RPT + 2 * R; j++) {
-        float v[12];
-        read12(tile + (ry + j) * TSTRIDE + cx, v);
-        if (SQ)
+        typename elem<E>::reg v[12];
+        read12(tile + (t.ry + j) * TSTRIDE + t.cx, v);
 #pragma unroll
-            for (int e = 0; e < 12; e++) v[e] = v[e] * v[e];
-#pragma unroll
-        for (int c = 0; c < CPT; c++) {
-            double rs = (double)v[TPAD - R + c];
-#pragma unroll
-            for (int d = 1; d < K; d++) rs = rs + (double)v[TPAD - R + c + d];
-            ring[j % K][c] = rs;
-        }
+        for (int c = 0; c < CPT; c++) ring[j % K][c] = Op::row(v + (TPAD - R + c));
         if (j >= 2 * R) {
-            const int i = j - 2 * R, orow = ty0 + ry + i;
+            const int i = j - 2 * R, orow = t.ty0 + t.ry + i;
             if (orow < nrows) {
-                float o[CPT];
+                typename Op::result o[CPT];
 #pragma unroll
-                for (int c = 0; c < CPT; c++) {
-                    double acc = ring[i % K][c];
-#pragma unroll
-                    for (int dy = 1; dy < K; dy++) acc = acc + ring[(i + dy) % K][c];
-                    o[c] = (float)(acc * (1.0 / (double)(K * K)));
-                }
-                store4(out, W, orow, x0 + cx, o, vec);
+                for (int c = 0; c < CPT; c++) o[c] = Op::col([&](int dy) -> const typename Op::term & { return ring[(i + dy) % K][c]; });
+                emit(orow, t.x0 + t.cx, o);
             }
         }
     }
+}
+
+// THE float64 order of the box sums, the parity contract with oracle/ref_np.py: the first term, then the others added one by
+// one — along a row left to right (box_op::row), then down the K row sums top to bottom (box_op::col); k6_std sums x and x * x
+// through it as well.
+template <int K, typename F> __device__ __forceinline__ double sum_in_order(F term)
+{
+    double acc = term(0);
+#pragma unroll
+    for (int d = 1; d < K; d++) acc = acc + term(d);
+    return acc;
+}
+// box mean of x (SQ: of x * x, squared in float32)
+template <int K, bool SQ> struct box_op {
+    typedef double term;
+    typedef float result;
+    static __device__ __forceinline__ double row(const float *w)
+    {
+        return sum_in_order<K>([&](int d) { return (double)(SQ ? w[d] * w[d] : w[d]); });
+    }
+    template <typename G> static __device__ __forceinline__ float col(G e) { return (float)(sum_in_order<K>(e) * (1.0 / (double)(K * K))); }
+};
+// erode (MODE 0: min), dilate (MODE 1: max), gradient (MODE 2: max - min) with a K x K rectangle
+template <int K, int MODE> struct morph_op {
+    struct term { int mn, mx; };
+    typedef int result;
+    static __device__ __forceinline__ void take(term &m, int lo, int hi)
+    {
+        if (MODE != 1) m.mn = lo < m.mn ? lo : m.mn;
+        if (MODE != 0) m.mx = hi > m.mx ? hi : m.mx;
+    }
+    static __device__ __forceinline__ term row(const int *w)
+    {
+        term m = {w[0], w[0]};
+#pragma unroll
+        for (int d = 1; d < K; d++) take(m, w[d], w[d]);
+        return m;
+    }
+    template <typename G> static __device__ __forceinline__ int col(G e)
+    {
+        term m = e(0);
+#pragma unroll
+        for (int dy = 1; dy < K; dy++) take(m, e(dy).mn, e(dy).mx);
+        return MODE == 0 ? m.mn : (MODE == 1 ? m.mx : m.mx - m.mn);
+    }
+};
+// ---- box mean (optionally of x*x), float64 sums ----
+template <int K, bool SQ>
+__global__ __launch_bounds__(256) void k6_box(win_planes pl, int Hin, int W, int y0, int nrows, int mode, tile_map tm)
+{
+    __shared__ __align__(16) float tile[(TH + 2 * (K / 2)) * TSTRIDE];
+    tile_pos t;
+    if (!stage_tile<float, K / 2>(tile, (const float *)pl.in[blockIdx.z], Hin, W, y0, mode, tm, t)) return;
+    stencil_walk<K, box_op<K, SQ>>(tile, t, W, nrows, row_store<float>((float *)pl.out[blockIdx.z], W));
 }
 
 // variance_scale_k / std_dev_scale_k: max(blur(x*x) - blur(x)^2, 0) [sqrt], BORDER_REFLECT_101 (indices.py:537-548)
@@ -197,13 +249,11 @@ __global__ __launch_bounds__(256) void k6_std(const float *__restrict__ x, int H
 {
     constexpr int R = K / 2;
     __shared__ __align__(16) float tile[(TH + 2 * R) * TSTRIDE];
-    int x0, ty0;
-    if (!tile_of_block(tm, x0, ty0)) return;
-    load_tile<float, R>(tile, x, Hin, W, 1, x0, y0 + ty0);
-    __syncthreads();
-    const int cx = (threadIdx.x & 63) * CPT, ry = (threadIdx.x >> 6) * RPT;
+    tile_pos t;
+    if (!stage_tile<float, R>(tile, x, Hin, W, y0, BORDER_REFLECT_101, tm, t)) return;
+    const int x0 = t.x0, ty0 = t.ty0, cx = t.cx, ry = t.ry;
     if (x0 + cx >= W || ty0 + ry >= nrows) return;
-    const bool vec = (W & 3) == 0 && ((uintptr_t)out & 15) == 0;
+    const row_store<float> store(out, W);
     double ring1[K][CPT], ring2[K][CPT];
     const double sc = 1.0 / (double)(K * K);
 #pragma unroll
@@ -214,14 +264,8 @@ __global__ __launch_bounds__(256) void k6_std(const float *__restrict__ x, int H
         for (int e = 0; e < 12; e++) vv[e] = v[e] * v[e];
 #pragma unroll
         for (int c = 0; c < CPT; c++) {
-            double r1 = (double)v[TPAD - R + c], r2 = (double)vv[TPAD - R + c];
-#pragma unroll
-            for (int d = 1; d < K; d++) {
-                r1 = r1 + (double)v[TPAD - R + c + d];
-                r2 = r2 + (double)vv[TPAD - R + c + d];
-            }
-            ring1[j % K][c] = r1;
-            ring2[j % K][c] = r2;
+            ring1[j % K][c] = sum_in_order<K>([&](int d) { return (double)v[TPAD - R + c + d]; });
+            ring2[j % K][c] = sum_in_order<K>([&](int d) { return (double)vv[TPAD - R + c + d]; });
         }
         if (j >= 2 * R) {
             const int i = j - 2 * R, orow = ty0 + ry + i;
@@ -229,73 +273,27 @@ __global__ __launch_bounds__(256) void k6_std(const float *__restrict__ x, int H
                 float o[CPT];
 #pragma unroll
                 for (int c = 0; c < CPT; c++) {
-                    double a1 = ring1[i % K][c], a2 = ring2[i % K][c];
-#pragma unroll
-                    for (int dy = 1; dy < K; dy++) {
-                        a1 = a1 + ring1[(i + dy) % K][c];
-                        a2 = a2 + ring2[(i + dy) % K][c];
-                    }
+                    const double a1 = sum_in_order<K>([&](int dy) { return ring1[(i + dy) % K][c]; });
+                    const double a2 = sum_in_order<K>([&](int dy) { return ring2[(i + dy) % K][c]; });
                     const float mean = (float)(a1 * sc), mean_sq = (float)(a2 * sc);
                     const float mm = mean * mean;
                     float var = mean_sq - mm;
                     if (var < 0.f) var = 0.f;
                     o[c] = VAR ? var : sqrtf(var);
                 }
-                store4(out, W, orow, x0 + cx, o, vec);
+                store(orow, x0 + cx, o);
             }
         }
     }
 }
 
-// erode (MODE 0: min), dilate (MODE 1: max), gradient (MODE 2: max - min) with a K x K rectangle
 template <int K, int MODE>
 __global__ __launch_bounds__(256) void k7_morph(const uint8_t *__restrict__ q, int Hin, int W, int y0, int nrows, uint8_t *__restrict__ out, tile_map tm)
 {
-    constexpr int R = K / 2;
-    __shared__ __align__(16) uint8_t tile[(TH + 2 * R) * TSTRIDE];
-    int x0, ty0;
-    if (!tile_of_block(tm, x0, ty0)) return;
-    load_tile<uint8_t, R>(tile, q, Hin, W, BORDER_REPLICATE, x0, y0 + ty0);
-    __syncthreads();
-    const int cx = (threadIdx.x & 63) * CPT, ry = (threadIdx.x >> 6) * RPT;
-    if (x0 + cx >= W || ty0 + ry >= nrows) return;
-    const bool vec = (W & 3) == 0 && ((uintptr_t)out & 3) == 0;
-    int rmin[K][CPT], rmax[K][CPT];
-#pragma unroll
-    for (int j = 0; j < RPT + 2 * R; j++) {
-        int v[12];
-        read12(tile + (ry + j) * TSTRIDE + cx, v);
-#pragma unroll
-        for (int c = 0; c < CPT; c++) {
-            int mn = v[TPAD - R + c], mx = mn;
-#pragma unroll
-            for (int d = 1; d < K; d++) {
-                const int t = v[TPAD - R + c + d];
-                if (MODE != 1) mn = t < mn ? t : mn;
-                if (MODE != 0) mx = t > mx ? t : mx;
-            }
-            rmin[j % K][c] = mn;
-            rmax[j % K][c] = mx;
-        }
-        if (j >= 2 * R) {
-            const int i = j - 2 * R, orow = ty0 + ry + i;
-            if (orow < nrows) {
-                int o[CPT];
-#pragma unroll
-                for (int c = 0; c < CPT; c++) {
-                    int mn = rmin[i % K][c], mx = rmax[i % K][c];
-#pragma unroll
-                    for (int dy = 1; dy < K; dy++) {
-                        const int a = rmin[(i + dy) % K][c], b = rmax[(i + dy) % K][c];
-                        if (MODE != 1) mn = a < mn ? a : mn;
-                        if (MODE != 0) mx = b > mx ? b : mx;
-                    }
-                    o[c] = MODE == 0 ? mn : (MODE == 1 ? mx : mx - mn);
-                }
-                store4(out, W, orow, x0 + cx, o, vec);
-            }
-        }
-    }
+    __shared__ __align__(16) uint8_t tile[(TH + 2 * (K / 2)) * TSTRIDE];
+    tile_pos t;
+    if (!stage_tile<uint8_t, K / 2>(tile, q, Hin, W, y0, BORDER_REPLICATE, tm, t)) return;
+    stencil_walk<K, morph_op<K, MODE>>(tile, t, W, nrows, row_store<uint8_t>(out, W));
 }
 
 // 3x3 Sobel magnitude (KIND 0) and cross Laplacian (KIND 1) of a uint8 plane, BORDER_REFLECT_101, value / 255 in float32.
@@ -308,14 +306,12 @@ __global__ __launch_bounds__(256) void k8_filter(const uint8_t *__restrict__ q, 
 {
     constexpr int R = 1;
     __shared__ __align__(16) uint8_t tile[(TH + 2 * R) * TSTRIDE];
-    int x0, ty0;
-    if (!tile_of_block(tm, x0, ty0)) return;   // whole workgroup: uniform
-    load_tile<uint8_t, R>(tile, q, Hin, W, 1, x0, y0 + ty0);
-    __syncthreads();
-    const int cx = (threadIdx.x & 63) * CPT, ry = (threadIdx.x >> 6) * RPT;
+    tile_pos t;
+    if (!stage_tile<uint8_t, R>(tile, q, Hin, W, y0, BORDER_REFLECT_101, tm, t)) return;   // whole workgroup: uniform
+    const int x0 = t.x0, ty0 = t.ty0, cx = t.cx, ry = t.ry;
     float lmn = INFINITY, lmx = -INFINITY;
     if (x0 + cx < W && ty0 + ry < nrows) {
-        const bool vec = (W & 3) == 0 && ((uintptr_t)out & 15) == 0;
+        const row_store<float> store(out, W);
         int ra[3][CPT], rb[3][CPT];  // Sobel: horizontal difference / smoothing of a row; Laplacian: left + right / centre
 #pragma unroll
         for (int j = 0; j < RPT + 2; j++) {
@@ -351,7 +347,7 @@ __global__ __launch_bounds__(256) void k8_filter(const uint8_t *__restrict__ q, 
                             o[c] = KIND == 0 ? val / den : dlt / den;
                         }
                     }
-                    if (PASS == 1) store4(out, W, orow, x0 + cx, o, vec);
+                    if (PASS == 1) store(orow, x0 + cx, o);
                 }
             }
         }
@@ -374,36 +370,37 @@ __global__ __launch_bounds__(256) void k8_filter(const uint8_t *__restrict__ q, 
     }
 }
 
-// cv2.resize INTER_LINEAR float32: horizontal taps (edge taps get weight 0), vertical taps clamp rows
-// Row-striped form: the local source holds rows [src_row0, src_row0 + sh_local) of a source sh rows tall and the
-// local destination rows [dst_row0, dst_row0 + dh_local) of a destination dh rows tall; taps are computed in
-// GLOBAL coordinates, so a stripe gets exactly the values of the un-sharded call.
-__device__ __forceinline__ float resize_px(const float *__restrict__ src, int sh, int sw, double scale_x, double scale_y, int src_row0,
-                                           int px, int py)
+// cv2.resize INTER_LINEAR float32.  A destination pixel (px, py) of the whole image is
+//   (src[y0][sx] * a0 + src[y0][sx1] * a1) * (1 - fy) + (src[y1][sx] * a0 + src[y1][sx1] * a1) * fy,
+// every product and sum ONE float32 operation in that order, with the positions below: the coordinate in float64, rounded
+// to float32 before the floor; horizontal taps clamped with the weight of the outside tap set to 0; vertical rows
+// y0 = sy, y1 = sy + 1 clamped to the image with the fraction kept.  That order is what gives cv2's bits.
+struct resize_htaps {
+    int sx, sx1;
+    float a0, a1;
+};
+__host__ __device__ __forceinline__ resize_htaps resize_hpos(int px, double scale_x, int sw)
 {
     float fx = (float)(((double)px + 0.5) * scale_x - 0.5);
     int sx = (int)floorf(fx);
     fx = fx - (float)sx;
     if (sx < 0) { sx = 0; fx = 0.f; }
     if (sx >= sw - 1) { sx = sw - 1; fx = 0.f; }
-    const int sx1 = sx + 1 < sw ? sx + 1 : sw - 1;
-    const float a0 = 1.0f - fx, a1 = fx;
-    float fy = (float)(((double)py + 0.5) * scale_y - 0.5);
-    int sy = (int)floorf(fy);
-    fy = fy - (float)sy;
-    const int y0 = sy < 0 ? 0 : (sy > sh - 1 ? sh - 1 : sy);
-    const int y1 = sy + 1 < 0 ? 0 : (sy + 1 > sh - 1 ? sh - 1 : sy + 1);
-    const float b0 = 1.0f - fy, b1 = fy;
-    const float *r0 = src + (size_t)(y0 - src_row0) * sw, *r1 = src + (size_t)(y1 - src_row0) * sw;
-    const float t00 = r0[sx] * a0, t01 = r0[sx1] * a1, t10 = r1[sx] * a0, t11 = r1[sx1] * a1;
-    const float h0 = t00 + t01, h1 = t10 + t11;
-    const float u0 = h0 * b0, u1 = h1 * b1;
-    return u0 + u1;
+    return {sx, sx + 1 < sw ? sx + 1 : sw - 1, 1.0f - fx, fx};
+}
+// floor and fraction of destination row py's source position (the row is NOT clamped here)
+__host__ __device__ __forceinline__ int resize_vpos(int py, double scale_y, float &frac)
+{
+    const float fy = (float)(((double)py + 0.5) * scale_y - 0.5);
+    const int sy = (int)floorf(fy);
+    frac = fy - (float)sy;
+    return sy;
 }
 
-// A fixed number of workgroups walk the 64 x 4 tiles (measured faster than one workgroup per tile: 0.63 against 0.72 ms
-// per 16384^2 plane).  MM (rsseg_ctx_collect_minmax): the plane's minimum / maximum are committed once per wave at the end
-// (one global atomic per TILE would serialise on one address).
+// Row-striped form: the local source holds rows [src_row0, src_row0 + sh_local) of a source sh rows tall and the
+// local destination rows [dst_row0, dst_row0 + dh_local) of a destination dh rows tall; taps are computed in
+// GLOBAL coordinates, so a stripe gets exactly the values of the un-sharded call.
+// MM (rsseg_ctx_collect_minmax): the plane's minimum / maximum are committed once per workgroup at the end.
 // (Sharing the right-hand tap with the next lane by shuffle, and four pixels per lane with one 16-byte store, were both
 // measured slower than the plain per-pixel form.)
 struct resize_planes {
@@ -425,7 +422,7 @@ struct resize_planes {
 // 4), and the taps of the next RS_AHEAD source rows are requested back to back before any of them is used — the r03 form
 // had ONE destination row in flight per wave (four loads, wait, store: a memory round trip per row).  Every destination
 // row py with floor(fy(py)) == y is then written as h(y) * (1 - fy) + h(y + 1) * fy with rows clamped to the image: the
-// operations and operands of resize_px, so the same bits.
+// operations and operands of the formula above, so the same bits.
 template <bool MM>
 __global__ __launch_bounds__(256) void k5_resize(resize_planes pl, int sh, int sw, int dh, int dw, double scale_x, double scale_y, int src_row0,
                                                  int sh_local, int dst_row0, int dh_local, int gx, int R, int plane, uint32_t *__restrict__ mm)
@@ -436,23 +433,11 @@ __global__ __launch_bounds__(256) void k5_resize(resize_planes pl, int sh, int s
     const int tx = (int)(blockIdx.x % (unsigned)gx), by = (int)(blockIdx.x / (unsigned)gx);
     const int px = tx * RS_W + (int)threadIdx.x;
     if (px < dw) {
-        // horizontal taps (the arithmetic of resize_px, hoisted)
-        float fx = (float)(((double)px + 0.5) * scale_x - 0.5);
-        int sx = (int)floorf(fx);
-        fx = fx - (float)sx;
-        if (sx < 0) { sx = 0; fx = 0.f; }
-        if (sx >= sw - 1) { sx = sw - 1; fx = 0.f; }
-        const int sx1 = sx + 1 < sw ? sx + 1 : sw - 1;
-        const float a0 = 1.0f - fx, a1 = fx;
+        const resize_htaps ht = resize_hpos(px, scale_x, sw);   // hoisted: one column per thread
+        const int sx = ht.sx, sx1 = ht.sx1;
+        const float a0 = ht.a0, a1 = ht.a1;
         const int row_end = min((by + 1) * R, dh_local);
         int pyl = by * R;
-        // vertical position of a destination row: floor and fraction, as resize_px computes them
-        auto vpos = [&](int row_local, float &frac) -> int {
-            float fy = (float)(((double)(row_local + dst_row0) + 0.5) * scale_y - 0.5);
-            const int sy = (int)floorf(fy);
-            frac = fy - (float)sy;
-            return sy;
-        };
         // a source row's address: clamped to the image (the border rule) and to the rows this stripe holds (only rows
         // requested ahead of need can fall outside; they are never used)
         const int lo = src_row0, hi = src_row0 + sh_local - 1;
@@ -462,7 +447,7 @@ __global__ __launch_bounds__(256) void k5_resize(resize_planes pl, int sh, int s
             return src + (size_t)(y - src_row0) * sw;
         };
         float fcur;
-        int sy_cur = pyl < row_end ? vpos(pyl, fcur) : 0;
+        int sy_cur = pyl < row_end ? resize_vpos(pyl + dst_row0, scale_y, fcur) : 0;
         int ys = sy_cur;                                   // the source row h_cur belongs to
         float h_cur;
         {
@@ -490,7 +475,7 @@ __global__ __launch_bounds__(256) void k5_resize(resize_planes pl, int sh, int s
                         mx = fmaxf(mx, z);
                     }
                     pyl++;
-                    if (pyl < row_end) sy_cur = vpos(pyl, fcur);
+                    if (pyl < row_end) sy_cur = resize_vpos(pyl + dst_row0, scale_y, fcur);
                 }
                 h_cur = h_next;
             }
@@ -505,7 +490,17 @@ __global__ __launch_bounds__(256) void k5_resize(resize_planes pl, int sh, int s
     if (MM) mm_commit_wg(mm + 2 * plane, mn, mx);
 }
 
-static dim3 grid2d(int H, int W) { return dim3((W + WG_X - 1) / WG_X, (H + WG_Y - 1) / WG_Y); }
+// the K dispatch of the stencil launches: go(std::integral_constant<int, k>) for k in {3, 5, 7} and, with KMAX 9, 9 (the
+// callers have refused every other k)
+template <int KMAX, typename F> static void with_window(int k, F go)
+{
+    switch (k) {
+    case 3: go(std::integral_constant<int, 3>()); break;
+    case 5: go(std::integral_constant<int, 5>()); break;
+    case 7: go(std::integral_constant<int, 7>()); break;
+    case 9: if constexpr (KMAX >= 9) go(std::integral_constant<int, 9>()); break;
+    }
+}
 
 // rows form: the plane holds Hin rows; rows [y0, y1) are produced.  edges bit 0 / bit 1: row 0 / row Hin - 1 is the
 // image's first / last row (the border rule applies there); otherwise it is a halo row of a stripe and must be out of
@@ -537,15 +532,11 @@ extern "C" int rsseg_box_mean_rows_f32(rsseg_ctx *ctx, const float *const *d_x, 
     HIPCHK(ctx, hipSetDevice(ctx->device));
     {
         prof_scope ps(ctx, nplanes > 1 ? "ctxmean" : "box");  // "ctxmean": several planes per launch (add_spatial_context)
-        const tile_map tm = make_tile_map(y1 - y0, W);
-        const dim3 g(8 * tm.chunk, 1, nplanes);
-#define BOX_GO(KV)                                                                                                          \
-    case KV:                                                                                                                \
-        if (square) hipLaunchKernelGGL((k6_box<KV, true>), g, dim3(256), 0, ctx->stream, pl, Hin, W, y0, y1 - y0, border, tm); \
-        else hipLaunchKernelGGL((k6_box<KV, false>), g, dim3(256), 0, ctx->stream, pl, Hin, W, y0, y1 - y0, border, tm);      \
-        break;
-        switch (k) { BOX_GO(3) BOX_GO(5) BOX_GO(7) BOX_GO(9) }
-#undef BOX_GO
+        const stencil_launch sl(y1 - y0, W, nplanes);
+        with_window<9>(k, [&](auto K) {
+            if (square) hipLaunchKernelGGL((k6_box<K.value, true>), sl.grid, dim3(256), 0, ctx->stream, pl, Hin, W, y0, y1 - y0, border, sl.tm);
+            else hipLaunchKernelGGL((k6_box<K.value, false>), sl.grid, dim3(256), 0, ctx->stream, pl, Hin, W, y0, y1 - y0, border, sl.tm);
+        });
     }
     HIPCHK(ctx, hipGetLastError());
     return stream_sync(ctx);
@@ -566,15 +557,11 @@ extern "C" int rsseg_local_std_rows_f32(rsseg_ctx *ctx, const float *d_x, int Hi
     HIPCHK(ctx, hipSetDevice(ctx->device));
     {
         prof_scope ps(ctx, "box");
-        const tile_map tm = make_tile_map(y1 - y0, W);
-        const dim3 g(8 * tm.chunk);
-#define STD_GO(KV)                                                                                                    \
-    case KV:                                                                                                          \
-        if (variance) hipLaunchKernelGGL((k6_std<KV, true>), g, dim3(256), 0, ctx->stream, d_x, Hin, W, y0, y1 - y0, d_out, tm); \
-        else hipLaunchKernelGGL((k6_std<KV, false>), g, dim3(256), 0, ctx->stream, d_x, Hin, W, y0, y1 - y0, d_out, tm);         \
-        break;
-        switch (k) { STD_GO(3) STD_GO(5) STD_GO(7) }
-#undef STD_GO
+        const stencil_launch sl(y1 - y0, W);
+        with_window<7>(k, [&](auto K) {
+            if (variance) hipLaunchKernelGGL((k6_std<K.value, true>), sl.grid, dim3(256), 0, ctx->stream, d_x, Hin, W, y0, y1 - y0, d_out, sl.tm);
+            else hipLaunchKernelGGL((k6_std<K.value, false>), sl.grid, dim3(256), 0, ctx->stream, d_x, Hin, W, y0, y1 - y0, d_out, sl.tm);
+        });
     }
     HIPCHK(ctx, hipGetLastError());
     return stream_sync(ctx);
@@ -593,13 +580,8 @@ extern "C" int rsseg_local_var_f32(rsseg_ctx *ctx, const float *d_x, int H, int 
 template <int MODE> static int morph_launch(rsseg_ctx *ctx, const uint8_t *in, int Hin, int W, int y0, int y1, int k, uint8_t *out)
 {
     prof_scope ps(ctx, "morph");
-    const tile_map tm = make_tile_map(y1 - y0, W);
-    const dim3 g(8 * tm.chunk);
-    switch (k) {
-    case 3: hipLaunchKernelGGL((k7_morph<3, MODE>), g, dim3(256), 0, ctx->stream, in, Hin, W, y0, y1 - y0, out, tm); break;
-    case 5: hipLaunchKernelGGL((k7_morph<5, MODE>), g, dim3(256), 0, ctx->stream, in, Hin, W, y0, y1 - y0, out, tm); break;
-    case 7: hipLaunchKernelGGL((k7_morph<7, MODE>), g, dim3(256), 0, ctx->stream, in, Hin, W, y0, y1 - y0, out, tm); break;
-    }
+    const stencil_launch sl(y1 - y0, W);
+    with_window<7>(k, [&](auto K) { hipLaunchKernelGGL((k7_morph<K.value, MODE>), sl.grid, dim3(256), 0, ctx->stream, in, Hin, W, y0, y1 - y0, out, sl.tm); });
     return RSSEG_OK;
 }
 
@@ -653,15 +635,14 @@ static int filter_rows(rsseg_ctx *ctx, const char *what, const uint8_t *d_q, int
     RSCHK(ws_reserve(ctx, 64 * RSSEG_MM_REPL));
     RSCHK(pin_reserve(ctx, 64 * RSSEG_MM_REPL));
     uint32_t *d_keys = (uint32_t *)ctx->d_ws;   // [RSSEG_MM_REPL] lines of {min key, max key, ...}
-    const tile_map tm = make_tile_map(std::max(y1 - y0, 1), W);
-    const dim3 g(8 * tm.chunk);
+    const stencil_launch sl(std::max(y1 - y0, 1), W);
     double mm[2] = {-INFINITY, -INFINITY};  // {-(min), max}: a rank without rows contributes nothing to the MAX-reduce
     if (y1 > y0) {
         HIPCHK(ctx, hipMemsetAsync(d_keys, 0, 64 * RSSEG_MM_REPL, ctx->stream));
         HIPCHK(ctx, hipMemset2DAsync(d_keys, 64, 0xff, 4, RSSEG_MM_REPL, ctx->stream));
         {
             prof_scope ps(ctx, "filt_max");
-            hipLaunchKernelGGL((k8_filter<KIND, 0>), g, dim3(256), 0, ctx->stream, d_q, Hin, W, y0, y1 - y0, (float *)nullptr, 0.f, 1.f, d_keys, tm);
+            hipLaunchKernelGGL((k8_filter<KIND, 0>), sl.grid, dim3(256), 0, ctx->stream, d_q, Hin, W, y0, y1 - y0, (float *)nullptr, 0.f, 1.f, d_keys, sl.tm);
         }
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d_keys, 64 * RSSEG_MM_REPL, hipMemcpyDeviceToHost, ctx->stream));
@@ -671,14 +652,8 @@ static int filter_rows(rsseg_ctx *ctx, const char *what, const uint8_t *d_q, int
             kmn = std::min(kmn, ((const uint32_t *)ctx->h_pin)[16 * r]);
             kmx = std::max(kmx, ((const uint32_t *)ctx->h_pin)[16 * r + 1]);
         }
-        auto unkey = [](uint32_t key) {
-            uint32_t u = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
-            float f;
-            memcpy(&f, &u, 4);
-            return (double)f;
-        };
-        mm[0] = -unkey(kmn);
-        mm[1] = unkey(kmx);
+        mm[0] = -(double)mm_unkey(kmn);
+        mm[1] = (double)mm_unkey(kmx);
     }
     RSCHK(comm_allreduce_host(ctx, mm, 2, RSSEG_F64, RSSEG_MAX));
     if (y1 == y0) return RSSEG_OK;
@@ -696,7 +671,7 @@ static int filter_rows(rsseg_ctx *ctx, const char *what, const uint8_t *d_q, int
     }
     {
         prof_scope ps(ctx, "filt_write");
-        hipLaunchKernelGGL((k8_filter<KIND, 1>), g, dim3(256), 0, ctx->stream, d_q, Hin, W, y0, y1 - y0, d_out, sub, den, (uint32_t *)nullptr, tm);
+        hipLaunchKernelGGL((k8_filter<KIND, 1>), sl.grid, dim3(256), 0, ctx->stream, d_q, Hin, W, y0, y1 - y0, d_out, sub, den, (uint32_t *)nullptr, sl.tm);
     }
     HIPCHK(ctx, hipGetLastError());
     return stream_sync(ctx);
@@ -741,8 +716,8 @@ static int resize_rows(rsseg_ctx *ctx, const float *const *d_src, int nplanes, i
     const double scale_x = 1.0 / ((double)dw / (double)sw), scale_y = 1.0 / ((double)dh / (double)sh);
     // the source stripe must hold every row the destination stripe taps
     auto tap = [&](int py) {
-        float fy = (float)(((double)py + 0.5) * scale_y - 0.5);
-        return (int)floorf(fy);
+        float frac;
+        return resize_vpos(py, scale_y, frac);
     };
     const int need0 = std::min(std::max(tap(dst_row0), 0), sh - 1), need1 = std::min(std::max(tap(dst_row0 + dh_local - 1) + 1, 0), sh - 1);
     if (need0 < src_row0 || need1 >= src_row0 + sh_local)

@@ -37,7 +37,7 @@ TW, TH, CPT, RPT, TPAD, WIN_MAXP = (KC[n] for n in ("TW", "TH", "CPT", "RPT", "T
 
 
 def tile_map(nrows, W):
-    """make_tile_map of k5_window.hip: (tile columns, tiles, tiles per XCD); the launch has 8 * chunk blocks."""
+    """stencil_launch of k5_window.hip: (tile columns, tiles, tiles per XCD); the launch has 8 * chunk blocks."""
     ntx = (W + TW - 1) // TW
     nt = ntx * ((nrows + TH - 1) // TH)
     return ntx, nt, (nt + 7) // 8
@@ -384,6 +384,68 @@ def test_nan_and_inf_next_to_the_seams(ctx, oracle):
                 done += 1
     assert not bad, report(bad)
     assert done == len(shapes) * len(insts) and len(shapes) >= 12
+
+
+# ------------------------------------------------------------------------------------------------ 2b. more workgroups than replica slots
+WRAP_SHAPE = (8 * TH + 1, 7 * TW + 1)
+
+
+def mm_replicas():
+    with open(os.path.join(os.path.dirname(K5_SOURCE), "common.h")) as f:
+        return int(re.search(r"^#define[ \t]+RSSEG_MM_REPL[ \t]+(\d+)\b", f.read(), re.M).group(1))
+
+
+def block_of_pixel(r, c, H, W):
+    """tile_of_block of k5_window.hip inverted: the workgroup that owns pixel (r, c) of an H x W launch."""
+    ntx, _nt, chunk = tile_map(H, W)
+    t = (r // TH) * ntx + c // TW
+    return (t % chunk) * 8 + t // chunk
+
+
+def wrap_planes(H, W):
+    """Flat planes (128) whose extrema come from the two last workgroups of the launch, a weaker copy of each feature in
+    tile 0.  The last tile of this shape is the single corner pixel, where reflect-101 makes the Sobel magnitude 0 whatever
+    the plane holds: it can carry the Laplacian's minimum (a 255 pixel) but not the Sobel maximum, which therefore lies,
+    with the Laplacian's maximum (a 0 pixel), in the last full tile — the tile of the last workgroup but one."""
+    ntx, nt, chunk = tile_map(H, W)
+    r, c = (H - 2) // TH * TH + TH // 2, (ntx - 2) * TW + TW // 2       # centre of tile nt - ntx - 2
+    sob = np.full((H, W), 128, np.uint8)
+    sob[r + 1, c - 1:c + 2] = 255
+    sob[TH // 2 + 1, TW // 2 - 1:TW // 2 + 2] = 200
+    lap = np.full((H, W), 128, np.uint8)
+    lap[H - 1, W - 1] = 255
+    lap[r, c] = 0
+    lap[TH // 2, TW // 2] = 200
+    lap[TH // 2, TW // 2 + 12] = 60
+    return sob, lap
+
+
+@pytest.mark.gpu
+def test_extrema_committed_by_workgroups_beyond_the_replica_slots(ctx, oracle):
+    """PASS 0 of k8_filter commits to replica slot blockIdx.x % RSSEG_MM_REPL: with more workgroups than slots the last ones
+    share a slot with the first.  Here the extrema are produced ONLY by such workgroups (checked on the CPU first), so a lost
+    or misrouted commit normalises the whole plane with the weaker extrema of tile 0."""
+    H, W = WRAP_SHAPE
+    repl = mm_replicas()
+    ntx, nt, chunk = tile_map(H, W)
+    assert nt == 8 * chunk == 72 > repl and block_of_pixel(H - 1, W - 1, H, W) == nt - 1
+    sob, lap = wrap_planes(H, W)
+    mag, l = oracle.sobel_mag_u8(sob), oracle.laplacian_u8(lap)
+    assert mag[H - 1, W - 1] == 0                      # why the Sobel maximum cannot sit in the last tile
+    owners = {}
+    for name, plane, where in (("sobel max", mag, mag == mag.max()), ("laplacian min", l, l == l.min()), ("laplacian max", l, l == l.max())):
+        owners[name] = {block_of_pixel(int(r), int(c), H, W) for r, c in np.argwhere(where)}
+        assert min(owners[name]) >= repl, (name, owners[name])
+    assert owners["laplacian min"] == {nt - 1} and owners["sobel max"] == owners["laplacian max"] == {nt - 2}
+    first = np.zeros((H, W), bool)
+    first[:TH, :TW] = True                             # tile 0: weaker, but not flat
+    assert 0 < mag[first].max() < mag.max() and l.min() < l[first].min() < 0 < l[first].max() < l.max()
+    bad = []
+    for inst, q in ((("sobel",), sob), (("laplacian",), lap)):
+        d = first_difference(host(run(ctx, inst, dev(ctx, q), H, W), (H, W)), expected(oracle, inst, q=q))
+        if d:
+            bad.append("%dx%d %s: %s" % (H, W, label(inst), d))
+    assert not bad, report(bad)
 
 
 # ------------------------------------------------------------------------------------------------ 3. alignment branches
