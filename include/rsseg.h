@@ -389,6 +389,31 @@ int rsseg_forest_fit(rsseg_ctx *ctx, const float *const *d_planes, int F, int64_
                      int32_t *d_left, int32_t *d_right, int32_t *d_feature, double *d_threshold, double *d_impurity,
                      int32_t *d_n_node, int32_t *d_w_node, uint8_t *d_missing_left, double *d_value,
                      int64_t *node_count, int32_t *max_depth_out);
+/* rsseg_forest_fit with one record per tree in place of the scalar parameters and same_counts: trees of different forests
+ * (other depths, other leaf sizes, other training subsets) grow side by side in one call, one workgroup each, and the chain of
+ * continuation launches is as long as the slowest tree needs.  rsseg_forest_fit itself is this call with uniform jobs
+ * (counts_row = t or 0, weight_total = n).
+ * d_counts: n_count_rows rows of n int32 counts; tree t reads row jobs[t].counts_row, and several trees may name one row.  A
+ * row is non-negative and sums to the job's weight_total, the tree's weighted_n_samples (a mismatch is RSSEG_ERR_INVALID
+ * naming the tree and the expected sum; 1 <= weight_total < 2^26 as n above).  A sample with count 0 is not part of the tree,
+ * exactly as scikit-learn's splitter drops samples of weight zero: with the bootstrap counts of a cross-validation fold's
+ * training subset scattered into rows of length n (zeros at the held-out samples, weight_total = the subset's size) the tree
+ * equals the one RandomForestClassifier.fit(X[train], y[train]) grows, provided `train` is sorted.
+ * jobs[n_trees] (host): seed, max_depth, min_samples_split, min_samples_leaf, max_features as rsseg_forest_fit takes them,
+ * per tree; `reserved` is 0.  node_off, the node arrays, node_count and max_depth_out: as rsseg_forest_fit.
+ * Profiler name "forest_fit_jobs". */
+typedef struct rsseg_forest_job {
+    int64_t counts_row;
+    int64_t weight_total;
+    uint32_t seed;
+    int32_t max_depth, min_samples_split, min_samples_leaf, max_features;
+    int32_t reserved;
+} rsseg_forest_job;
+int rsseg_forest_fit_jobs(rsseg_ctx *ctx, const float *const *d_planes, int F, int64_t n, const int32_t *d_y, int n_classes,
+                          const int32_t *d_counts, int64_t n_count_rows, int n_trees, const rsseg_forest_job *jobs,
+                          const int64_t *node_off, int32_t *d_left, int32_t *d_right, int32_t *d_feature, double *d_threshold,
+                          double *d_impurity, int32_t *d_n_node, int32_t *d_w_node, uint8_t *d_missing_left, double *d_value,
+                          int64_t *node_count, int32_t *max_depth_out);
 
 /* ---- K12: rule-based classification --------------------------------------- */
 /* threshold_segmentation (modules/features/extract.py:344-404, otsu=False): NaN counts as 0, then d_out = 1 where

@@ -13,9 +13,15 @@
 // formed here from the same exact integers: sums of squares stay below 2^53 while the total weight is below 2^26.
 //
 // Bounds: a tree has at most 2m-1 nodes and its stack at most min(max_depth, m)+1 entries (m = samples with a non-zero
-// count); the host sizes both exactly and the kernel still checks them (err, never a truncated tree).  Every count row sums to
-// n: weighted_n_samples is taken as n, and k16_fit_init refuses a row that does not (err 5).  A launch builds at most
+// count); the host sizes both exactly and the kernel still checks them (err, never a truncated tree).  A launch builds at most
 // `budget` nodes per tree; the host issues continuation launches and stops when one makes no progress.
+//
+// Each tree is a job (rsseg_forest_job): its own count row, weight_total, seed, max_depth, min_samples_split,
+// min_samples_leaf and max_features, read from device memory once per launch into SGPRs (uniform per workgroup).  A count
+// row has length n and sums to the job's weight_total, which is the tree's weighted_n_samples; k16_fit_init refuses a row
+// that does not (err 5).  Samples with count 0 never enter a tree (sklearn's splitter drops them too), so a row that is zero
+// on the held-out samples of a cross-validation fold grows the tree of the fit on the fold's training subset, and trees of
+// different folds, depths and forests share one launch chain.  rsseg_forest_fit is the uniform case: weight_total = n.
 #include <cfloat>
 
 #include "common.h"
@@ -43,16 +49,14 @@ struct ff_entry {
 struct ff_args {
     const float *const *planes;   // F device pointers (device array)
     const int32_t *y;         // class index per sample
-    const int32_t *counts;    // bootstrap counts, tree t at t * count_stride
-    int64_t count_stride;     // N, or 0 when every tree has the same counts (bootstrap=False)
+    const int32_t *counts;    // count rows of n values; tree t reads row jobs[t].counts_row
+    const rsseg_forest_job *jobs;   // [T] per-tree parameters
     int64_t n;                // samples
     int F, C, T;
-    int max_depth, mss, msl, max_features;
     int budget;
     const int64_t *samp_off;  // [T+1] samples / sort scratch of tree t
     const int64_t *node_off;  // [T+1] node records of tree t (2m-1 each)
     const int64_t *stack_off; // [T+1] stack entries of tree t
-    const uint32_t *seeds;    // xorshift start per tree
     int32_t *samples;
     uint64_t *g0, *g1;
     ff_state *st;
@@ -89,6 +93,8 @@ __device__ __forceinline__ int ff_rand_int(int lo, int hi, uint32_t *s) { return
 // splits two samples one float32 ulp apart at 0.5 (6e-8) or 2/255 +- 1e-7 (tests/test_forest_fit_host.py pins this against
 // scikit-learn itself).  So values are the same only when equal.
 __device__ __forceinline__ bool ff_close(float a, float b) { return b <= a; }
+
+__device__ __forceinline__ int ff_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 __device__ __forceinline__ int wave_incl_scan(int v)
 {
@@ -238,7 +244,7 @@ __device__ const uint64_t *ff_sort(const ff_args &a, ff_shared &S, const int32_t
 }
 
 // the best position of one feature over sorted keys `buf` (n of them): first maximum of the Gini proxy
-__device__ ff_best ff_scan(const ff_args &a, ff_shared &S, const uint64_t *buf, int n, const int32_t *cnt, long long W)
+__device__ ff_best ff_scan(const ff_args &a, ff_shared &S, const uint64_t *buf, int n, const int32_t *cnt, long long W, int msl)
 {
     const int C = a.C, tid = threadIdx.x, w = tid >> 6;
     if (tid < C) S.base[tid] = 0;
@@ -260,7 +266,7 @@ __device__ ff_best ff_scan(const ff_args &a, ff_shared &S, const uint64_t *buf, 
             wt = cnt[s];
             if (i + 1 < n) {
                 const float v = ff_val(e), vn = ff_val(buf[i + 1]);
-                cand = !ff_close(v, vn) && (i + 1) >= a.msl && (n - i - 1) >= a.msl;
+                cand = !ff_close(v, vn) && (i + 1) >= msl && (n - i - 1) >= msl;
             }
         }
         for (int c = 0; c < C; c++) {
@@ -329,7 +335,8 @@ __global__ void __launch_bounds__(FF_THREADS) k16_fit_init(const ff_args *__rest
     __shared__ unsigned long long s_sum;
     const int t = blockIdx.x;
     if (t >= a.T) return;
-    const int32_t *cnt = a.counts + (int64_t)t * a.count_stride;
+    const int32_t *cnt = a.counts + a.jobs[t].counts_row * a.n;
+    const int64_t weight_total = a.jobs[t].weight_total;
     int32_t *smp = a.samples + a.samp_off[t];
     const int64_t m = a.samp_off[t + 1] - a.samp_off[t];
     if (threadIdx.x == 0) {
@@ -354,7 +361,7 @@ __global__ void __launch_bounds__(FF_THREADS) k16_fit_init(const ff_args *__rest
         if (threadIdx.x == 0) s_base += tot;
         __syncthreads();
     }
-    // weighted_n_samples is taken as n (k16_fit_step: w_total), so a count row must be non-negative and sum to n
+    // weighted_n_samples is the job's weight_total (k16_fit_step: w_total), so a count row must be non-negative and sum to it
     wsum = wave_sum(wsum);
     neg = wave_sum(neg);
     if (lane_id() == 0) {
@@ -364,10 +371,10 @@ __global__ void __launch_bounds__(FF_THREADS) k16_fit_init(const ff_args *__rest
     __syncthreads();
     if (threadIdx.x == 0) {
         ff_state *st = a.st + t;
-        st->err = (s_neg || (long long)s_sum != (long long)a.n) ? 5 : s_base != m ? 1 : 0;
+        st->err = (s_neg || (long long)s_sum != (long long)weight_total) ? 5 : s_base != m ? 1 : 0;
         st->node_count = 0;
         st->max_depth_seen = 0;
-        st->rng = a.seeds[t];
+        st->rng = a.jobs[t].seed;
         for (int f = 0; f < FF_MAX_F; f++) st->features[f] = st->constants[f] = f;
         ff_entry root;
         root.start = 0;
@@ -393,7 +400,14 @@ __global__ void __launch_bounds__(FF_THREADS) k16_fit_step(const ff_args *__rest
     if (t >= a.T) return;
     ff_state *st = a.st + t;
     if (st->done) return;
-    const int32_t *cnt = a.counts + (int64_t)t * a.count_stride;
+    // the tree's own parameters, loaded once per launch.  They are uniform over the workgroup, but the loads go through a
+    // pointer that is itself loaded, so the compiler makes them vector loads and every test on them a vector compare under
+    // an exec mask; readfirstlane puts them where the kernel arguments were, in SGPRs (scalar compares and branches)
+    const rsseg_forest_job *jp = a.jobs + t;
+    const int max_depth = ff_uniform(jp->max_depth), mss = ff_uniform(jp->min_samples_split), msl = ff_uniform(jp->min_samples_leaf);
+    const int max_features = ff_uniform(jp->max_features);
+    const int weight_total = ff_uniform((int)jp->weight_total);   // below 2^26
+    const int32_t *cnt = a.counts + (int64_t)ff_uniform((int)jp->counts_row) * a.n;   // the host keeps the row count below 2^31
     int32_t *smp = a.samples + a.samp_off[t];
     const int64_t so = a.samp_off[t];
     uint64_t *g0 = a.g0 + so, *g1 = a.g1 + so;
@@ -401,7 +415,7 @@ __global__ void __launch_bounds__(FF_THREADS) k16_fit_step(const ff_args *__rest
     ff_entry *stk = a.stack + a.stack_off[t];
     const int64_t scap = a.stack_off[t + 1] - a.stack_off[t];
     const int F = a.F, C = a.C;
-    const double w_total = (double)a.n;   // weighted_n_samples: n bootstrap draws, or n unit weights
+    const double w_total = (double)weight_total;   // weighted_n_samples: the bootstrap draws, or the unit weights, of the tree's training set
     if (tid < FF_MAX_F) {
         S.features[tid] = st->features[tid];
         S.constants[tid] = st->constants[tid];
@@ -449,7 +463,7 @@ __global__ void __launch_bounds__(FF_THREADS) k16_fit_step(const ff_args *__rest
         __syncthreads();
         const double impurity = S.cur.impurity;
         const long long W = S.wsum;
-        bool leaf = cur.depth >= a.max_depth || n < a.mss || n < 2 * a.msl || impurity <= DBL_EPSILON;
+        bool leaf = cur.depth >= max_depth || n < mss || n < 2 * msl || impurity <= DBL_EPSILON;
         if (tid == 0) {
             S.best.score = -INFINITY;
             S.best.pos = n;   // "no split": pos >= end
@@ -466,7 +480,7 @@ __global__ void __launch_bounds__(FF_THREADS) k16_fit_step(const ff_args *__rest
             // node_split_best's draw loop; thread 0 owns the draw state, the workgroup evaluates each drawn feature
             for (int guard = 0; guard < 2 * FF_MAX_F + 2; guard++) {
                 if (tid == 0) {
-                    if (S.f_i > S.ntotal && (S.nvis < a.max_features || S.nvis <= S.nfound + S.ndrawn)) {
+                    if (S.f_i > S.ntotal && (S.nvis < max_features || S.nvis <= S.nfound + S.ndrawn)) {
                         S.nvis++;
                         int fj = ff_rand_int(S.ndrawn, S.f_i - S.nfound, &S.rng);
                         if (fj < S.nknown) {
@@ -494,7 +508,7 @@ __global__ void __launch_bounds__(FF_THREADS) k16_fit_step(const ff_args *__rest
                     const float lo = ff_val(buf[0]), hi = ff_val(buf[n - 1]);
                     const bool is_const = ff_close(lo, hi);
                     ff_best b;
-                    if (!is_const) b = ff_scan(a, S, buf, n, cnt, W);
+                    if (!is_const) b = ff_scan(a, S, buf, n, cnt, W, msl);
                     if (tid == 0) {
                         if (is_const) {
                             const int x = S.features[S.fj];
@@ -617,46 +631,59 @@ __global__ void __launch_bounds__(FF_THREADS) k16_fit_step(const ff_args *__rest
 
 }  // namespace
 
-extern "C" int rsseg_forest_fit(rsseg_ctx *ctx, const float *const *d_planes, int F, int64_t n, const int32_t *d_y, int n_classes,
-                                const int32_t *d_counts, int same_counts, int n_trees, const uint32_t *seeds, int max_depth,
-                                int min_samples_split, int min_samples_leaf, int max_features, const int64_t *node_off,
-                                int32_t *d_left, int32_t *d_right, int32_t *d_feature, double *d_threshold, double *d_impurity,
-                                int32_t *d_n_node, int32_t *d_w_node, uint8_t *d_missing_left, double *d_value,
-                                int64_t *node_count, int32_t *max_depth_out)
+static int ff_check_shape(rsseg_ctx *ctx, const char *who, int F, int n_classes)
 {
-    if (!ctx) return RSSEG_ERR_INVALID;
     if (F < 1 || F > FF_MAX_F || n_classes < 1 || n_classes > FF_MAX_C)
-        return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "forest_fit: %d features, %d classes: at most %d of each", F, n_classes, FF_MAX_F);
-    if (n < 1 || n >= (int64_t)1 << 26 || n_trees < 1 || !d_planes || !d_y || !d_counts || !seeds || !node_off || !node_count ||
-        !max_depth_out || max_depth < 0 || min_samples_split < 2 || min_samples_leaf < 1 || max_features < 0)
-        return rs_fail(ctx, RSSEG_ERR_INVALID,
-                       "forest_fit: bad arguments (n=%lld trees=%d max_depth=%d min_samples_split=%d min_samples_leaf=%d max_features=%d; "
-                       "1 <= n < 2^26)", (long long)n, n_trees, max_depth, min_samples_split, min_samples_leaf, max_features);
+        return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "%s: %d features, %d classes: at most %d of each", who, F, n_classes, FF_MAX_F);
+    return RSSEG_OK;
+}
+
+// The body of both entry points: `who` names the caller in messages and in the profiler; `uniform` is rsseg_forest_fit, whose
+// jobs all have weight_total = n (it keeps its own wording for a count row with another sum).
+static int ff_run(rsseg_ctx *ctx, const char *who, bool uniform, const float *const *d_planes, int F, int64_t n, const int32_t *d_y,
+                  int n_classes, const int32_t *d_counts, int64_t n_count_rows, int n_trees, const rsseg_forest_job *jobs,
+                  const int64_t *node_off, int32_t *d_left, int32_t *d_right, int32_t *d_feature, double *d_threshold,
+                  double *d_impurity, int32_t *d_n_node, int32_t *d_w_node, uint8_t *d_missing_left, double *d_value,
+                  int64_t *node_count, int32_t *max_depth_out)
+{
+    RSCHK(ff_check_shape(ctx, who, F, n_classes));
+    if (n < 1 || n >= (int64_t)1 << 26 || n_trees < 1 || n_count_rows < 1 || n_count_rows > INT32_MAX || !d_planes || !d_y || !d_counts || !jobs || !node_off ||
+        !node_count || !max_depth_out)
+        return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: bad arguments (n=%lld trees=%d count rows=%lld; 1 <= n < 2^26)", who, (long long)n,
+                       n_trees, (long long)n_count_rows);
     ff_args a;
     memset(&a, 0, sizeof(a));
     for (int f = 0; f < F; f++)
-        if (!d_planes[f]) return rs_fail(ctx, RSSEG_ERR_INVALID, "forest_fit: plane %d is NULL", f);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+        if (!d_planes[f]) return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: plane %d is NULL", who, f);
     // per-tree sample counts m_t (the host passes node_off = prefix of 2 m_t - 1): the layout follows from it
     std::vector<int64_t> samp(n_trees + 1, 0), stk(n_trees + 1, 0);
     for (int t = 0; t < n_trees; t++) {
+        const rsseg_forest_job &j = jobs[t];
+        if (j.counts_row < 0 || j.counts_row >= n_count_rows || j.weight_total < 1 || j.weight_total >= (int64_t)1 << 26 || j.max_depth < 0 ||
+            j.min_samples_split < 2 || j.min_samples_leaf < 1 || j.max_features < 0)
+            return rs_fail(ctx, RSSEG_ERR_INVALID,
+                           "%s: tree %d: bad job (counts_row=%lld of %lld rows, weight_total=%lld, max_depth=%d min_samples_split=%d "
+                           "min_samples_leaf=%d max_features=%d; 1 <= weight_total < 2^26)", who, t, (long long)j.counts_row,
+                           (long long)n_count_rows, (long long)j.weight_total, j.max_depth, j.min_samples_split, j.min_samples_leaf,
+                           j.max_features);
         const int64_t cap = node_off[t + 1] - node_off[t];
-        if (cap < 1 || !(cap & 1)) return rs_fail(ctx, RSSEG_ERR_INVALID, "forest_fit: tree %d: node capacity %lld is not 2m-1", t, (long long)cap);
+        if (cap < 1 || !(cap & 1)) return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: tree %d: node capacity %lld is not 2m-1", who, t, (long long)cap);
         const int64_t m = (cap + 1) / 2;
-        if (m > n) return rs_fail(ctx, RSSEG_ERR_INVALID, "forest_fit: tree %d: %lld samples > n", t, (long long)m);
+        if (m > n) return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: tree %d: %lld samples > n", who, t, (long long)m);
         samp[t + 1] = samp[t] + m;
-        stk[t + 1] = stk[t] + std::min<int64_t>(max_depth, m) + 2;
+        stk[t + 1] = stk[t] + std::min<int64_t>(j.max_depth, m) + 2;
     }
-    const size_t b_off = 3 * 8 * (size_t)(n_trees + 1), b_seed = 4 * (size_t)n_trees, b_pl = 8 * (size_t)F, b_args = sizeof(ff_args);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t b_off = 3 * 8 * (size_t)(n_trees + 1), b_job = sizeof(rsseg_forest_job) * (size_t)n_trees, b_pl = 8 * (size_t)F, b_args = sizeof(ff_args);
     const size_t b_smp = 4 * (size_t)samp[n_trees], b_g = 8 * (size_t)samp[n_trees];
     const size_t b_st = sizeof(ff_state) * n_trees, b_stk = sizeof(ff_entry) * (size_t)stk[n_trees];
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t total = al(b_args) + al(b_off) + al(b_seed) + al(b_pl) + al(b_smp) + 2 * al(b_g) + al(b_st) + al(b_stk);
+    const size_t total = al(b_args) + al(b_off) + al(b_job) + al(b_pl) + al(b_smp) + 2 * al(b_g) + al(b_st) + al(b_stk);
     RSCHK(ws_reserve(ctx, total));
     char *p = ctx->d_ws;
     ff_args *d_args = (ff_args *)p; p += al(b_args);
     int64_t *d_off = (int64_t *)p; p += al(b_off);
-    uint32_t *d_seed = (uint32_t *)p; p += al(b_seed);
+    rsseg_forest_job *d_job = (rsseg_forest_job *)p; p += al(b_job);
     const float **d_pl = (const float **)p; p += al(b_pl);
     a.samples = (int32_t *)p; p += al(b_smp);
     a.g0 = (uint64_t *)p; p += al(b_g);
@@ -670,24 +697,19 @@ extern "C" int rsseg_forest_fit(rsseg_ctx *ctx, const float *const *d_planes, in
         hoff[2 * (n_trees + 1) + t] = stk[t];
     }
     HIPCHK(ctx, hipMemcpyAsync(d_off, hoff.data(), b_off, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_seed, seeds, b_seed, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_job, jobs, b_job, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d_pl, d_planes, b_pl, hipMemcpyHostToDevice, ctx->stream));
     a.planes = d_pl;
     a.samp_off = d_off;
     a.node_off = d_off + (n_trees + 1);
     a.stack_off = d_off + 2 * (n_trees + 1);
-    a.seeds = d_seed;
+    a.jobs = d_job;
     a.y = d_y;
     a.counts = d_counts;
-    a.count_stride = same_counts ? 0 : n;
     a.n = n;
     a.F = F;
     a.C = n_classes;
     a.T = n_trees;
-    a.max_depth = max_depth;
-    a.mss = min_samples_split;
-    a.msl = min_samples_leaf;
-    a.max_features = max_features;
     a.budget = 2048;
     a.left = d_left;
     a.right = d_right;
@@ -701,7 +723,7 @@ extern "C" int rsseg_forest_fit(rsseg_ctx *ctx, const float *const *d_planes, in
 
     // the arguments live in device memory: the kernels read the fields they need instead of holding ~30 pointers in SGPRs
     HIPCHK(ctx, hipMemcpyAsync(d_args, &a, b_args, hipMemcpyHostToDevice, ctx->stream));
-    prof_scope ps(ctx, "forest_fit");
+    prof_scope ps(ctx, who);
     hipLaunchKernelGGL(k16_fit_init, dim3(n_trees), dim3(FF_THREADS), 0, ctx->stream, (const ff_args *)d_args);
     HIPCHK(ctx, hipGetLastError());
     RSCHK(pin_reserve(ctx, b_st));
@@ -712,7 +734,7 @@ extern "C" int rsseg_forest_fit(rsseg_ctx *ctx, const float *const *d_planes, in
     int64_t prev = -1;
     for (int64_t launch = 0;; launch++) {
         if (launch >= max_launches)
-            return rs_fail(ctx, RSSEG_ERR_HIP, "forest_fit: %lld launches did not finish the trees", (long long)launch);
+            return rs_fail(ctx, RSSEG_ERR_HIP, "%s: %lld launches did not finish the trees", who, (long long)launch);
         hipLaunchKernelGGL(k16_fit_step, dim3(n_trees), dim3(FF_THREADS), 0, ctx->stream, (const ff_args *)d_args);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipMemcpyAsync(h, a.st, b_st, hipMemcpyDeviceToHost, ctx->stream));
@@ -720,17 +742,20 @@ extern "C" int rsseg_forest_fit(rsseg_ctx *ctx, const float *const *d_planes, in
         int64_t built = 0;
         bool all = true;
         for (int t = 0; t < n_trees; t++) {
+            if (h[t].err == 5 && uniform)
+                return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: tree %d: the counts are negative or do not sum to n = %lld "
+                               "(weighted_n_samples is n)", who, t, (long long)n);
             if (h[t].err == 5)
-                return rs_fail(ctx, RSSEG_ERR_INVALID, "forest_fit: tree %d: the counts are negative or do not sum to n = %lld "
-                               "(weighted_n_samples is n)", t, (long long)n);
+                return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: tree %d: the counts of row %lld are negative or do not sum to weight_total = %lld "
+                               "(the tree's weighted_n_samples)", who, t, (long long)jobs[t].counts_row, (long long)jobs[t].weight_total);
             if (h[t].err)
-                return rs_fail(ctx, RSSEG_ERR_NOMEM, "forest_fit: tree %d stopped with error %d after %d nodes (%s)", t, h[t].err, h[t].node_count,
+                return rs_fail(ctx, RSSEG_ERR_NOMEM, "%s: tree %d stopped with error %d after %d nodes (%s)", who, t, h[t].err, h[t].node_count,
                                h[t].err == 1 ? "sample count mismatch" : h[t].err == 2 ? "node storage full" : h[t].err == 3 ? "inconsistent partition" : "stack full");
             built += h[t].node_count;
             all = all && h[t].done;
         }
         if (all) break;
-        if (built <= prev) return rs_fail(ctx, RSSEG_ERR_HIP, "forest_fit: launch %lld made no progress", (long long)launch);
+        if (built <= prev) return rs_fail(ctx, RSSEG_ERR_HIP, "%s: launch %lld made no progress", who, (long long)launch);
         prev = built;
     }
     for (int t = 0; t < n_trees; t++) {
@@ -738,4 +763,46 @@ extern "C" int rsseg_forest_fit(rsseg_ctx *ctx, const float *const *d_planes, in
         max_depth_out[t] = h[t].max_depth_seen;
     }
     return RSSEG_OK;
+}
+
+extern "C" int rsseg_forest_fit_jobs(rsseg_ctx *ctx, const float *const *d_planes, int F, int64_t n, const int32_t *d_y, int n_classes,
+                                     const int32_t *d_counts, int64_t n_count_rows, int n_trees, const rsseg_forest_job *jobs,
+                                     const int64_t *node_off, int32_t *d_left, int32_t *d_right, int32_t *d_feature, double *d_threshold,
+                                     double *d_impurity, int32_t *d_n_node, int32_t *d_w_node, uint8_t *d_missing_left, double *d_value,
+                                     int64_t *node_count, int32_t *max_depth_out)
+{
+    if (!ctx) return RSSEG_ERR_INVALID;
+    return ff_run(ctx, "forest_fit_jobs", false, d_planes, F, n, d_y, n_classes, d_counts, n_count_rows, n_trees, jobs, node_off, d_left, d_right,
+                  d_feature, d_threshold, d_impurity, d_n_node, d_w_node, d_missing_left, d_value, node_count, max_depth_out);
+}
+
+// the uniform case: one set of parameters, tree t on count row t (or all on row 0), weight_total = n
+extern "C" int rsseg_forest_fit(rsseg_ctx *ctx, const float *const *d_planes, int F, int64_t n, const int32_t *d_y, int n_classes,
+                                const int32_t *d_counts, int same_counts, int n_trees, const uint32_t *seeds, int max_depth,
+                                int min_samples_split, int min_samples_leaf, int max_features, const int64_t *node_off,
+                                int32_t *d_left, int32_t *d_right, int32_t *d_feature, double *d_threshold, double *d_impurity,
+                                int32_t *d_n_node, int32_t *d_w_node, uint8_t *d_missing_left, double *d_value,
+                                int64_t *node_count, int32_t *max_depth_out)
+{
+    if (!ctx) return RSSEG_ERR_INVALID;
+    RSCHK(ff_check_shape(ctx, "forest_fit", F, n_classes));
+    if (n < 1 || n >= (int64_t)1 << 26 || n_trees < 1 || !d_planes || !d_y || !d_counts || !seeds || !node_off || !node_count ||
+        !max_depth_out || max_depth < 0 || min_samples_split < 2 || min_samples_leaf < 1 || max_features < 0)
+        return rs_fail(ctx, RSSEG_ERR_INVALID,
+                       "forest_fit: bad arguments (n=%lld trees=%d max_depth=%d min_samples_split=%d min_samples_leaf=%d max_features=%d; "
+                       "1 <= n < 2^26)", (long long)n, n_trees, max_depth, min_samples_split, min_samples_leaf, max_features);
+    std::vector<rsseg_forest_job> jobs(n_trees);
+    for (int t = 0; t < n_trees; t++) {
+        rsseg_forest_job &j = jobs[t];
+        j.counts_row = same_counts ? 0 : t;
+        j.weight_total = n;
+        j.seed = seeds[t];
+        j.max_depth = max_depth;
+        j.min_samples_split = min_samples_split;
+        j.min_samples_leaf = min_samples_leaf;
+        j.max_features = max_features;
+        j.reserved = 0;
+    }
+    return ff_run(ctx, "forest_fit", true, d_planes, F, n, d_y, n_classes, d_counts, same_counts ? 1 : n_trees, n_trees, jobs.data(), node_off, d_left,
+                  d_right, d_feature, d_threshold, d_impurity, d_n_node, d_w_node, d_missing_left, d_value, node_count, max_depth_out);
 }

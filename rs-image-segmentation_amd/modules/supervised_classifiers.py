@@ -9,9 +9,13 @@ and raises rsseg.runtime.RssegUnsupported instead of returning an empty map.
 prepare_training_samples and train_random_forest_from_samples are the reference's interactive-sample helpers
 (supervised_classifiers.py:32-52, 85-97): same names, defaults and print-and-return error behaviour.  The forest is fitted
 by K16 on the GPU (rsseg.forest_fit: the same trees scikit-learn grows), or by scikit-learn on the host for an input K16
-refuses.  train_random_forest (GridSearchCV) is not mirrored.
+refuses.  train_random_forest (supervised_classifiers.py:57-83) is the reference's grid search: every fold fit of every
+candidate grown in one K16 call and scored by K11 (rsseg.forest_grid.grid_search: GridSearchCV's scores, ranks and best
+model), or scikit-learn's GridSearchCV on the host for a search the device path refuses.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 
@@ -19,7 +23,7 @@ from rsseg.forest import flatten_forest
 from rsseg.runtime import RssegUnsupported
 from rsseg.runtime import default_context as _ctx
 
-__all__ = ["prepare_training_samples", "train_random_forest_from_samples", "predict_image", "np"]
+__all__ = ["prepare_training_samples", "train_random_forest", "train_random_forest_from_samples", "predict_image", "np"]
 
 
 def prepare_training_samples(features, roi_array, target_labels):
@@ -36,6 +40,36 @@ def prepare_training_samples(features, roi_array, target_labels):
     except Exception as e:  # noqa: BLE001 — reference behaviour
         print("❌ prepare_training_samples 出错:", e)
         return np.array([]), np.array([])
+
+
+def train_random_forest(X, y, param_grid=None, save_path="output/rf_model.pkl"):
+    """GridSearchCV(RandomForestClassifier(), param_grid, cv=3) over (X, y), the default grid being n_estimators 100, max_depth
+    10 / 20 / None, random_state 42 (on the GPU when the search is one rsseg.forest_grid takes): the refitted best model,
+    saved with joblib.dump to save_path and returned; on an error a message and None."""
+    try:
+        import joblib
+        from sklearn.ensemble import RandomForestClassifier
+        from rsseg.forest_grid import grid_search
+        if param_grid is None:
+            param_grid = {
+                'n_estimators': [100],
+                'max_depth': [10, 20, None],
+                'random_state': [42]
+            }
+        try:
+            best_model = grid_search(RandomForestClassifier(), param_grid, X, y, cv=3).best_estimator_
+        except RssegUnsupported:
+            from sklearn.model_selection import GridSearchCV
+            grid = GridSearchCV(RandomForestClassifier(), param_grid, cv=3, n_jobs=-1)
+            grid.fit(X, y)
+            best_model = grid.best_estimator_
+        os.makedirs(os.path.dirname(save_path), exist_ok=True)
+        joblib.dump(best_model, save_path)
+        print(f"✅ 模型训练完成，保存至 {save_path}")
+        return best_model
+    except Exception as e:  # noqa: BLE001 — reference behaviour
+        print("❌ 随机森林训练失败:", e)
+        return None
 
 
 def train_random_forest_from_samples(samples, labels, save_path="output/rf_model.pkl"):

@@ -776,8 +776,37 @@ class Context:
         node_caps[t] = 2 m_t - 1 (m_t = samples of tree t with a non-zero count).  Returns per tree a dict of NumPy arrays
         (left, right, feature, threshold, impurity, n_node_samples, weighted_n_node_samples, missing_go_to_left, value of
         shape (nodes, C)) and the tree's max_depth."""
+        same = counts.numel() == planes[0].numel()
+        seeds = np.ascontiguousarray(seeds, np.uint32)
+        vp = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+
+        def call(n, off, out, nc, md):
+            return self.lib.rsseg_forest_fit(self.h, self._pp(planes), len(planes), n, vp(y), int(n_classes), vp(counts), int(same), len(seeds),
+                                             seeds.ctypes.data_as(C.POINTER(C.c_uint32)), int(max_depth), int(min_samples_split),
+                                             int(min_samples_leaf), int(max_features), off, *out, nc, md)
+        return self._forest_grow(call, planes[0].numel(), node_caps, n_classes)
+
+    def forest_fit_jobs(self, planes: Sequence, y, counts, jobs: np.ndarray, node_caps: np.ndarray, n_classes: int) -> List[dict]:
+        """rsseg_forest_fit_jobs: grows one tree per record of `jobs` (dtype rsseg._lib.FOREST_JOB: counts_row, weight_total, seed,
+        max_depth, min_samples_split, min_samples_leaf, max_features) in one call.  counts: int32 device tensor of whole rows of
+        n counts; tree t reads row jobs[t].counts_row, which is non-negative and sums to jobs[t].weight_total (ValueError
+        otherwise), and trees may share rows.  planes, y, node_caps and the result: as forest_fit."""
+        n = planes[0].numel()
+        if counts.numel() == 0 or counts.numel() % n:
+            raise ValueError(f"forest_fit_jobs: counts must hold whole rows of {n} values")
+        jobs = np.ascontiguousarray(jobs, np.dtype(L.FOREST_JOB))
+        vp = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+
+        def call(n, off, out, nc, md):
+            return self.lib.rsseg_forest_fit_jobs(self.h, self._pp(planes), len(planes), n, vp(y), int(n_classes), vp(counts), counts.numel() // n,
+                                                  len(jobs), jobs.ctypes.data_as(C.c_void_p), off, *out, nc, md)
+        return self._forest_grow(call, n, node_caps, n_classes)
+
+    def _forest_grow(self, call, n: int, node_caps: np.ndarray, n_classes: int) -> List[dict]:
+        """Node storage for trees of `node_caps` records, the library call `call(n, node_off, node arrays, node_count,
+        max_depth)`, and the nodes that were built, copied back per tree."""
         torch = _torch()
-        T, n = len(seeds), planes[0].numel()
+        T = len(node_caps)
         off = np.zeros(T + 1, np.int64)
         off[1:] = np.cumsum(np.asarray(node_caps, np.int64))
         total = int(off[-1])
@@ -786,16 +815,11 @@ class Context:
         thr, imp = self.empty(total, torch.float64), self.empty(total, torch.float64)
         miss = self.empty(total, torch.uint8)
         value = self.empty(total * n_classes, torch.float64)
-        same = counts.numel() == n
-        seeds = np.ascontiguousarray(seeds, np.uint32)
         nc = np.zeros(T, np.int64)
         md = np.zeros(T, np.int32)
-        vp = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-        self._chk(self.lib.rsseg_forest_fit(self.h, self._pp(planes), len(planes), n, vp(y), int(n_classes), vp(counts), int(same), T,
-                                            seeds.ctypes.data_as(C.POINTER(C.c_uint32)), int(max_depth), int(min_samples_split),
-                                            int(min_samples_leaf), int(max_features), off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                            vp(left), vp(right), vp(feat), vp(thr), vp(imp), vp(n_node), vp(w_node), vp(miss), vp(value),
-                                            nc.ctypes.data_as(C.POINTER(C.c_int64)), md.ctypes.data_as(C.POINTER(C.c_int32))))
+        out = [C.c_void_p(t.data_ptr()) for t in (left, right, feat, thr, imp, n_node, w_node, miss, value)]
+        self._chk(call(n, off.ctypes.data_as(C.POINTER(C.c_int64)), out, nc.ctypes.data_as(C.POINTER(C.c_int64)),
+                       md.ctypes.data_as(C.POINTER(C.c_int32))))
         # copy back only the nodes that were built
         keep = np.concatenate([np.arange(off[t], off[t] + nc[t]) for t in range(T)]) if T else np.zeros(0, np.int64)
         idx = torch.from_numpy(keep).to(self.device)
