@@ -306,6 +306,25 @@ int rsseg_laplacian_norm_rows_u8(rsseg_ctx *ctx, const uint8_t *d_q, int Hin, in
 int rsseg_sobel_mag_u8(rsseg_ctx *ctx, const uint8_t *d_q, int H, int W, float *d_out);
 int rsseg_sobel_mag_rows_u8(rsseg_ctx *ctx, const uint8_t *d_q, int Hin, int W, int y0, int y1, int edges, float *d_out);
 
+/* ---- K17: correlation with a bank of float32 kernels (calculate_gabor_features, indices.py:346-399) ------------ */
+/* cv2.filter2D(u8, CV_32F, kern)'s direct path for nf kernels of one odd size ksize <= 15: out[f][y][x] = sum over i, then
+ * j (row-major), of taps[f][i][j] * u8[y + i - m][x + j - m], m = ksize / 2, BORDER_REFLECT_101 (reflected repeatedly on a
+ * plane smaller than m; an axis of one element reads that element), started from +0, one rounded float32 multiply and one
+ * rounded float32 add per tap, subnormals kept.  h_taps: nf * ksize * ksize floats on the host; d_out: nf planes of H * W
+ * float32, 16-byte aligned, not the input; h_minmax (host, 2 * nf, may be NULL): {min, max} of every plane.  Up to 8
+ * kernels share one launch and one staging of the plane.  Whole plane on one device: there is no rows form.
+ * RSSEG_ERR_INVALID, with a text: ksize even or outside 1..15, nf < 1, H or W < 1, a NaN or infinite tap.
+ * Supported tap range: the sum of |tap| of a kernel times 255 must stay finite in float32 (sum |tap| < 1.3e36; the Gabor taps
+ * are <= 1).  Finite taps beyond that are not refused: a response overflows to +-inf, inf - inf gives NaN, and the extrema
+ * (which count NaN as 0) and the normalised planes are then meaningless, without a report. */
+int rsseg_correlate_u8_f32(rsseg_ctx *ctx, const uint8_t *d_q, int H, int W, const float *h_taps, int ksize, int nf, float *d_out,
+                           float *h_minmax);
+/* the same, then every plane min-max normalised in place: (r - min) / (max - min + 1e-10) in float32 (indices.py:395), the
+ * roundings of rsseg_laplacian_norm_u8 and a true division; a constant plane gives zeros. */
+int rsseg_filter_bank_norm_u8(rsseg_ctx *ctx, const uint8_t *d_q, int H, int W, const float *h_taps, int ksize, int nf, float *d_out);
+/* the output tile (rows, columns) one workgroup of K17 owns: tests place their shapes and seams by it */
+void rsseg_correlate_tile(int *tile_h, int *tile_w);
+
 /* ---- K9/K10: KMeans ------------------------------------------------------------------------ */
 typedef struct rsseg_kmeans_info {
     int32_t n_iter;

@@ -4,8 +4,12 @@ names, positional order, defaults, NumPy-in / NumPy-out contract and dtypes (SUR
 the arithmetic done by the gfx950 kernels of librsseg_hip.so.  Inputs are never modified; outputs are
 fresh host arrays.  There is no CPU fallback: without the HIP library / an MI355X these raise.
 
-Functions of the reference module that are plotting (visualize_*) or never called by the stages (Gabor, HOG, ...)
-are out of scope; every member of the stage-2 feature dictionary is produced.
+Every member of the stage-2 feature dictionary is produced, and so is every other function of the reference module: the
+Gabor bank (calculate_gabor_features, on the correlation kernel K17) and the selection / fusion helpers the stages never
+call (feature_selection_by_variance, feature_fusion_for_segmentation, prepare_features_for_segmentation,
+hierarchical_feature_fusion, semantic_merge_water_classes).  Two kinds stay out: plotting (visualize_*: the names resolve
+and draw nothing) and evaluate_feature_importance_for_classes, which fits an unseeded forest
+and so has no result to be equal to.
 """
 from __future__ import annotations
 
@@ -23,6 +27,8 @@ __all__ = [
     "calculate_ndbi", "calculate_bsi", "perform_pca", "calculate_glcm_features", "calculate_lbp_features", "calculate_morphological_features",
     "calculate_multi_scale_features", "calculate_filter_responses", "add_spatial_context", "prepare_level_1_features",
     "prepare_level_2_features", "visualize_hierarchical_features", "visualize_selected_features", "np", "os",
+    "calculate_gabor_features", "feature_selection_by_variance", "feature_fusion_for_segmentation", "prepare_features_for_segmentation",
+    "hierarchical_feature_fusion", "semantic_merge_water_classes",
 ]
 
 
@@ -172,6 +178,17 @@ def calculate_lbp_features(band, radius=3, n_points=24):
     return lbp / lbp.max()
 
 
+def calculate_gabor_features(band, num_scales=4, num_orientations=6):
+    """reference indices.py:346-399: the re-normalised uint8 band under num_scales x num_orientations Gabor kernels
+    (cv2.getGaborKernel restated in rsseg.gabor, cv2.filter2D as its float32 direct path on K17), each response min-max
+    normalised in float32.  A list of (H, W) float32 planes, scales outer, orientations inner."""
+    from rsseg import gabor as _G
+    d, (h, w) = _dev(band)
+    ctx = _ctx()
+    q = ctx.quantize_u8(_P.renormalize(ctx, d), 255.0)
+    return [_host(p, (h, w)) for p in _G.gabor_bank(ctx, q, h, w, num_scales, num_orientations)]
+
+
 def calculate_morphological_features(band):
     """reference indices.py:401-442 — erosion / dilation / opening / closing / gradient at 3, 5, 7 (float64, u8 / 255.0;
     the stack consumes 'gradient_5')."""
@@ -181,6 +198,32 @@ def calculate_morphological_features(band):
     ops = (("erosion", _L.MORPH_ERODE), ("dilation", _L.MORPH_DILATE), ("opening", _L.MORPH_OPEN), ("closing", _L.MORPH_CLOSE),
            ("gradient", _L.MORPH_GRADIENT))
     return {f"{name}_{k}": _host(ctx.morph(q, h, w, k, op), (h, w)) / 255.0 for k in (3, 5, 7) for name, op in ops}
+
+
+def _is_plane(x):
+    return isinstance(x, np.ndarray) and x.ndim == 2
+
+
+def feature_selection_by_variance(features_dict, threshold=0.01):
+    """reference indices.py:484-517 (NumPy on the host).  A 2-D plane stays where np.var(plane) >= threshold.  A list made of
+    arrays only, and a dict (its array members only), are filtered member by member with the same test and dropped when
+    nothing is left.  Anything else is dropped.  The kept arrays are the caller's own objects, in the caller's order."""
+    def varies(a):
+        return np.var(a) >= threshold
+
+    kept = {}
+    for key, value in features_dict.items():
+        if _is_plane(value):
+            survivors = value if varies(value) else None
+        elif isinstance(value, list) and all(isinstance(m, np.ndarray) for m in value):
+            survivors = list(filter(varies, value))
+        elif isinstance(value, dict):
+            survivors = {k: m for k, m in value.items() if isinstance(m, np.ndarray) and varies(m)}
+        else:
+            continue
+        if survivors is not None and len(survivors):
+            kept[key] = survivors
+    return kept
 
 
 def calculate_multi_scale_features(band, scales=[1, 3, 5, 7]):
@@ -221,6 +264,86 @@ def filter_members(ctx, q, h, w):
     dog = g5 - g15
     return {"gaussian_5": g5, "gaussian_15": g15, "dog": (dog - dog.min()) / (dog.max() - dog.min() + 1e-10),
             "laplacian": _host(ctx.laplacian_norm(q, h, w), (h, w)), "sobel_mag": _host(ctx.sobel_mag(q, h, w), (h, w))}
+
+
+_INDEX_WORDS = ('ndvi', 'evi', 'msavi', 'ndwi', 'mndwi', 'ndbi', 'bsi')
+
+
+def feature_fusion_for_segmentation(features_dict, selected_features=None, fusion_method='weighted_sum'):
+    """reference indices.py:630-677 (NumPy on the host).  The 2-D planes named by selected_features (all 2-D planes of the
+    dictionary when None; names that are missing or are no plane are passed over) are min-max normalised,
+    (f - min) / (max - min + 1e-10) in NumPy's own dtypes, and then
+      'weighted_sum'  added up with the float64 weight 1 / count each, into an accumulator of the first plane's dtype;
+      'concatenate'   stacked on a new last axis.
+    ValueError, with the reference's texts, when no plane is left and for any other method (in that order)."""
+    names = features_dict.keys() if selected_features is None else selected_features
+    planes = [features_dict[n] for n in names if n in features_dict and _is_plane(features_dict[n])]
+    if len(planes) == 0:
+        raise ValueError("没有有效的特征可以融合")
+    scaled = []
+    for f in planes:
+        lo, hi = np.min(f), np.max(f)
+        scaled.append((f - lo) / (hi - lo + 1e-10))
+    if fusion_method == 'concatenate':
+        return np.stack(scaled, axis=-1)
+    if fusion_method != 'weighted_sum':
+        raise ValueError(f"不支持的融合方法: {fusion_method}")
+    share = np.float64(1.0) / len(scaled)      # what np.ones(count) / count holds
+    total = np.zeros_like(scaled[0])
+    for f in scaled:
+        total += share * f
+    return total
+
+
+def prepare_features_for_segmentation(features_dict, important_features=None):
+    """reference indices.py:679-730.  important_features names 2-D planes of the dictionary, or, as 'key_i', member i of the
+    list under 'key'; every plane found goes through robust_normalize — this module's, on the GPU — and the results are
+    stacked on a new last axis.  None stands for every key that contains one of the index names (case-insensitive) and, for
+    every other key that contains 'pca' and holds a list, its first three members.  Names that resolve to nothing are passed
+    over; ValueError with the reference's text when nothing is left.
+    One difference: the reference also swallows a ValueError raised while normalising a list member and skips that member.
+    Here only a non-integer suffix is passed over; what this module's robust_normalize refuses (a float64 plane:
+    RssegUnsupported; a member that is not 2-D: ValueError) is raised, not dropped, since the reference would have used it."""
+    names = important_features
+    if names is None:
+        names = []
+        for key, value in features_dict.items():
+            low = key.lower()
+            if any(word in low for word in _INDEX_WORDS):
+                names.append(key)
+            elif 'pca' in low and isinstance(value, list):
+                names += [f"{key}_{i}" for i in range(min(len(value), 3))]
+    stack = []
+    for name in names:
+        if name in features_dict and _is_plane(features_dict[name]):
+            stack.append(robust_normalize(features_dict[name]))
+            continue
+        key, sep, suffix = name.rpartition('_')
+        members = features_dict.get(key) if sep else None
+        if not isinstance(members, list):
+            continue
+        try:
+            i = int(suffix)
+        except ValueError:
+            continue
+        if 0 <= i < len(members):
+            stack.append(robust_normalize(members[i]))
+    if not stack:
+        raise ValueError("没有找到适合分割的特征")
+    return np.stack(stack, axis=-1)
+
+
+def hierarchical_feature_fusion(features_dict):
+    """reference indices.py:732-758 (pure stacking): ndwi, mndwi, ndvi, evi, ndbi, bsi on a last axis."""
+    return np.stack([features_dict['ndwi'], features_dict['mndwi'], features_dict['ndvi'], features_dict['evi'],
+                     features_dict['ndbi'], features_dict['bsi']], axis=-1)
+
+
+def semantic_merge_water_classes(segmentation_result):
+    """reference indices.py:778-791: classes 1 (river) and 2 (lake) both become 1, in a copy."""
+    merged_result = segmentation_result.copy()
+    merged_result[(segmentation_result == 1) | (segmentation_result == 2)] = 1
+    return merged_result
 
 
 def add_spatial_context(features_array, window_size=7):

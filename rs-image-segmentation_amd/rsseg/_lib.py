@@ -106,6 +106,9 @@ SIGNATURES = {
     "rsseg_local_var_f32": (_int, [_vp, _vp, _int, _int, _int, _vp]),
     "rsseg_laplacian_norm_u8": (_int, [_vp, _vp, _int, _int, _vp]),
     "rsseg_sobel_mag_u8": (_int, [_vp, _vp, _int, _int, _vp]),
+    "rsseg_correlate_u8_f32": (_int, [_vp, _vp, _int, _int, C.POINTER(C.c_float), _int, _int, _vp, C.POINTER(C.c_float)]),
+    "rsseg_filter_bank_norm_u8": (_int, [_vp, _vp, _int, _int, C.POINTER(C.c_float), _int, _int, _vp]),
+    "rsseg_correlate_tile": (None, [C.POINTER(_int), C.POINTER(_int)]),
     "rsseg_kmeans_fit_predict": (_int, [_vp, _PP, _int, _int, _i64, _int, C.c_uint32, _int, C.c_double, _vp,
                                         C.POINTER(C.c_double), C.POINTER(KMeansInfo)]),
     "rsseg_kmeans_fit_predict_mm": (_int, [_vp, _PP, _int, _int, _i64, _int, C.c_uint32, _int, C.c_double, _vp,

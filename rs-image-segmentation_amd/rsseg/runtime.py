@@ -612,6 +612,39 @@ class Context:
         self._chk(self.lib.rsseg_sobel_mag_rows_u8(self.h, C.c_void_p(q.data_ptr()), H, W, y0, y1, edges, C.c_void_p(out.data_ptr())))
         return out
 
+    # ---- K17: correlation with a bank of float32 kernels -------------------------------------------
+    @staticmethod
+    def _taps(taps):
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        if t.ndim == 2:
+            t = t[None]
+        if t.ndim != 3 or t.shape[1] != t.shape[2]:
+            raise ValueError("taps: (nf, ksize, ksize) float32")
+        return t
+
+    def correlate_u8(self, q, H: int, W: int, taps, minmax: bool = False):
+        """cv2.filter2D(u8, CV_32F, k)'s direct path for every k of taps[nf, ksize, ksize]: nf raw float32 planes (views of one
+        buffer), and with minmax=True the (nf, 2) float32 array of their {min, max} beside them."""
+        torch = _torch()
+        t = self._taps(taps)
+        nf, ksize = t.shape[0], t.shape[1]
+        out = self.empty(max(nf, 1) * H * W, torch.float32)
+        mm = np.zeros((max(nf, 1), 2), np.float32)
+        self._chk(self.lib.rsseg_correlate_u8_f32(self.h, C.c_void_p(q.data_ptr()), H, W, t.ctypes.data_as(C.POINTER(C.c_float)), ksize, nf,
+                                                  C.c_void_p(out.data_ptr()), mm.ctypes.data_as(C.POINTER(C.c_float)) if minmax else None))
+        planes = [out[f * H * W:(f + 1) * H * W] for f in range(nf)]
+        return (planes, mm) if minmax else planes
+
+    def filter_bank_norm(self, q, H: int, W: int, taps):
+        """correlate_u8, then every plane (r - min) / (max - min + 1e-10) in float32, in place."""
+        torch = _torch()
+        t = self._taps(taps)
+        nf, ksize = t.shape[0], t.shape[1]
+        out = self.empty(max(nf, 1) * H * W, torch.float32)
+        self._chk(self.lib.rsseg_filter_bank_norm_u8(self.h, C.c_void_p(q.data_ptr()), H, W, t.ctypes.data_as(C.POINTER(C.c_float)), ksize, nf,
+                                                     C.c_void_p(out.data_ptr())))
+        return [out[f * H * W:(f + 1) * H * W] for f in range(nf)]
+
     # ---- K13: LBP, rank entropy, fixed-point Gaussian ---------------------------------------------
     def lbp_uniform(self, q, H: int, W: int, n_points: int = 24, radius: float = 3):
         torch = _torch()
