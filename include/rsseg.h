@@ -382,6 +382,28 @@ int rsseg_forest_predict_proba(rsseg_ctx *ctx, const float *const *d_planes, int
  * Profiler name "forest_oob". */
 int rsseg_forest_oob(rsseg_ctx *ctx, const float *const *d_planes, int F, int64_t n, const int32_t *d_counts, double *d_oob,
                      int32_t *d_n_oob);
+/* The counts behind sklearn.inspection.permutation_importance (inspection/_permutation_importance.py:43-85) of the loaded
+ * forest with accuracy as the score: for every job j = (feature f, source row s)
+ *   counts[j] = #{ i < n : label_index(x_i with x_i[f] := d_planes[f][d_src[s * n + i]]) == d_y[i] }
+ * label_index: the class index rsseg_forest_predict turns into classes[...] (float64 sums in tree order, first maximum on
+ * ties); feature -1 substitutes nothing (the baseline score) and ignores `source`.
+ * d_y: [n] int32 class indices, -1 for a label the forest does not know (never correct); d_src: [n_src][n] int32 rows of
+ * sample indices, each in [0, n) (an index outside is not dereferenced: RSSEG_ERR_INVALID "source index out of range");
+ * jobs[n_jobs], counts[n_jobs]: host arrays.  Every job of the call runs in one launch (jobs on the grid's second axis;
+ * one launch per 65535 jobs), each workgroup adds its integer count with one 64-bit atomic, and the call waits once;
+ * the counters are zeroed on the context's stream inside the call.  The NaN-aware walk is chosen per job from the values
+ * after the substitution.  Synchronous.
+ * RSSEG_ERR_INVALID: no forest loaded, F is not the forest's feature count, a null plane, null d_y / jobs / counts, d_src
+ * null while a job has feature >= 0, a job's feature outside [-1, F), a job's source outside [0, n_src) while feature >= 0,
+ * n >= 2^31; `counts` is then untouched.  n_jobs == 0 returns RSSEG_OK; n == 0 returns RSSEG_OK with zero counts.
+ * Algorithmic HBM traffic per job: 4F + 12 B/sample in (planes, d_y, d_src, the gathered value), 8 B per workgroup out.
+ * Profiler name "forest_perm". */
+typedef struct rsseg_perm_job {
+    int32_t feature;
+    int32_t source;
+} rsseg_perm_job;
+int rsseg_forest_permutation_counts(rsseg_ctx *ctx, const float *const *d_planes, int F, int64_t n, const int32_t *d_y,
+                                    const int32_t *d_src, int n_src, const rsseg_perm_job *jobs, int n_jobs, int64_t *counts);
 
 /* ---- K16: random-forest training ------------------------------------------------------------ */
 /* RandomForestClassifier(criterion='gini', splitter='best').fit of scikit-learn 1.7.2 on float32 features, tree for tree

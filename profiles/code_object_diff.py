@@ -2,7 +2,8 @@
 """Per-kernel comparison of two source trees' gfx950 code, without a GPU: every file is compiled to assembly with the
 Makefile's flags (hipcc --cuda-device-only -S) in both trees; per kernel the registers, LDS and scratch bytes of the
 code-object metadata, the waves per SIMD they allow, and whether the instruction sequences (comments, labels' directives and
-blank lines dropped) are equal.
+blank lines dropped) are equal.  A file that only the new tree has is listed by itself (`new_file`, no parent figures): its
+kernels are within the rules when they use no scratch.
 
   python profiles/code_object_diff.py <parent csrc dir> <new csrc dir> out.json k5_window.hip k13_texture.hip ..."""
 import json
@@ -63,8 +64,24 @@ def main():
     parent, new, outp, files = sys.argv[1], sys.argv[2], sys.argv[3], sys.argv[4:]
     table = []
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(8) as ex:
-        jobs = {(t, f): ex.submit(asm, c, f, tmp, t) for f in files for t, c in (("parent", parent), ("new", new))}
+        jobs = {(t, f): ex.submit(asm, c, f, tmp, t) for f in files for t, c in (("parent", parent), ("new", new))
+                if os.path.exists(os.path.join(c, f))}
         for f in files:
+            if ("parent", f) not in jobs:      # a file the parent does not have: its kernels alone, the rule is no scratch
+                kn = kernels(jobs[("new", f)].result())
+                names = demangle(sorted(kn))
+                for name in sorted(kn):
+                    b = kn[name]
+                    row = {"file": f, "kernel": names[name].split("(")[0].replace("void ", ""), "new_file": True}
+                    for k in ("vgprs", "sgprs", "lds", "scratch"):
+                        row[k] = [None, b[k]]
+                    row["waves_per_simd"] = [None, waves_per_simd(b)]
+                    row["instructions"] = [None, len(b["ins"])]
+                    row["identical"] = None
+                    row["within_the_rules"] = b["scratch"] == 0
+                    table.append(row)
+                    print("new  " + ("" if row["within_the_rules"] else "RULE ") + json.dumps(row))
+                continue
             kp, kn = kernels(jobs[("parent", f)].result()), kernels(jobs[("new", f)].result())
             assert set(kp) == set(kn), (f, set(kp) ^ set(kn))
             names = demangle(sorted(kp))

@@ -41,6 +41,8 @@ class KMeansInfo(C.Structure):
 # rsseg_forest_job of include/rsseg.h as a NumPy record: one per tree of rsseg_forest_fit_jobs
 FOREST_JOB = [("counts_row", "<i8"), ("weight_total", "<i8"), ("seed", "<u4"), ("max_depth", "<i4"), ("min_samples_split", "<i4"),
               ("min_samples_leaf", "<i4"), ("max_features", "<i4"), ("reserved", "<i4")]
+# rsseg_perm_job of include/rsseg.h: one per job of rsseg_forest_permutation_counts (feature -1: no substitution)
+PERM_JOB = [("feature", "<i4"), ("source", "<i4")]
 
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -124,6 +126,7 @@ SIGNATURES = {
     "rsseg_forest_predict": (_int, [_vp, _PP, _int, _i64, _vp]),
     "rsseg_forest_predict_proba": (_int, [_vp, _PP, _int, _i64, _vp, _vp, _vp]),
     "rsseg_forest_oob": (_int, [_vp, _PP, _int, _i64, _vp, _vp, _vp]),
+    "rsseg_forest_permutation_counts": (_int, [_vp, _PP, _int, _i64, _vp, _vp, _int, _vp, _int, C.POINTER(_i64)]),
     "rsseg_forest_fit": (_int, [_vp, _PP, _int, _i64, _vp, _int, _vp, _int, _int, C.POINTER(C.c_uint32), _int, _int, _int, _int,
                                 C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64),
                                 C.POINTER(C.c_int32)]),

@@ -800,6 +800,30 @@ class Context:
                                             C.c_void_p(oob.data_ptr()), C.c_void_p(n_oob.data_ptr())))
         return oob.view(nc, n), n_oob
 
+    def forest_permutation_counts(self, planes: Sequence, y, src, jobs) -> np.ndarray:
+        """rsseg_forest_permutation_counts on the loaded forest: for every record of `jobs` (dtype rsseg._lib.PERM_JOB: feature,
+        source) the number of samples whose label index equals y when feature `feature` of every sample i is taken from row
+        src[source, i] (feature -1: the samples as they are).  planes: F float32 device planes of n samples; y: int32 device
+        class indices, -1 for a label the forest does not know; src: int32 device tensor of whole rows of n sample indices
+        (None when no job substitutes).  One launch and one wait for all jobs; returns int64 counts, one per job.  ValueError
+        with the library's message for what it refuses (a source index outside [0, n) among them)."""
+        torch = _torch()
+        n = planes[0].numel()
+        jobs = np.ascontiguousarray(jobs, np.dtype(L.PERM_JOB)).reshape(-1)
+        if y is not None and (y.dtype != torch.int32 or y.numel() != n or not y.is_contiguous()):
+            raise ValueError(f"forest_permutation_counts: y must be {n} contiguous int32 class indices")
+        n_src = 0
+        if src is not None:
+            if src.dtype != torch.int32 or not src.is_contiguous() or (n and src.numel() % n):
+                raise ValueError(f"forest_permutation_counts: src must hold whole rows of {n} contiguous int32 sample indices")
+            n_src = src.numel() // n if n else 0
+        counts = np.zeros(len(jobs), np.int64)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+        self._chk(self.lib.rsseg_forest_permutation_counts(self.h, self._pp(planes), len(planes), n, ptr(y), ptr(src), n_src,
+                                                           jobs.ctypes.data_as(C.c_void_p), len(jobs),
+                                                           counts.ctypes.data_as(C.POINTER(C.c_int64))))
+        return counts
+
     # ---- K16 -----------------------------------------------------------------------------------
     def forest_fit(self, planes: Sequence, y, counts, seeds: np.ndarray, node_caps: np.ndarray, max_depth: int,
                    min_samples_split: int, min_samples_leaf: int, max_features: int, n_classes: int) -> List[dict]:

@@ -179,6 +179,24 @@ def run_classification_stage(feature_file_path, method='rule_based', output_dir=
                                labeled_roi_file, strict_reference, ctx, False)
 
 
+IMPORTANCE_FILE = "rf_permutation_importance.json"
+IMPORTANCE_REPEATS, IMPORTANCE_SEED = 5, 42
+
+
+def run_forest_importance_stage(feature_file_path, roi_mask, output_dir="segmentation_outputs", use_hierarchical_all=True, *,
+                                classifier=None, labeled_roi_file: str = "labeled_roi.tif", confidence: bool = False,
+                                ctx: Optional[Context] = None) -> Optional[np.ndarray]:
+    """run_classification_stage(feature_file_path, 'random_forest', ...) (run_forest_confidence_stage with `confidence`) with
+    the permutation importance of the forest's features over the labelled pixels of `roi_mask` ((H, W) integers, 0 = no
+    label): every file of that call, unchanged, and beside them <output_dir>/rf_permutation_importance.json with
+    feature_names, importances_mean, importances_std, importances (F x n_repeats), baseline_score, n_samples, n_repeats (5)
+    and random_state (42) — rsseg.forest_importance.permutation_importance_image, equal to scikit-learn's
+    permutation_importance.  The ranking is printed as train_random_forest_classifier prints its importances.  Returns the
+    label map."""
+    return _run_classification(feature_file_path, "random_forest", output_dir, use_hierarchical_all, 7, classifier, None,
+                               labeled_roi_file, False, ctx, confidence, np.asarray(roi_mask))
+
+
 def run_forest_confidence_stage(feature_file_path, output_dir="segmentation_outputs", use_hierarchical_all=True, *, classifier=None,
                                 labeled_roi_file: str = "labeled_roi.tif", ctx: Optional[Context] = None) -> Optional[np.ndarray]:
     """run_classification_stage(feature_file_path, 'random_forest', ...) with confidence: every file of that call, unchanged,
@@ -191,7 +209,7 @@ def run_forest_confidence_stage(feature_file_path, output_dir="segmentation_outp
 
 
 def _run_classification(feature_file_path, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys,
-                        labeled_roi_file, strict_reference, ctx, confidence) -> Optional[np.ndarray]:
+                        labeled_roi_file, strict_reference, ctx, confidence, importance_mask=None) -> Optional[np.ndarray]:
     from modules.features.extract import load_features, normalize_features_structure, unsupervised_kmeans_classification
     os.makedirs(output_dir, exist_ok=True)
     try:
@@ -217,7 +235,9 @@ def _run_classification(feature_file_path, method, output_dir, use_hierarchical_
     if ctx is not None:   # the mirrors run on the process-wide context: lend them this one for the duration of the call
         _rt._default_ctx = ctx
     try:
-        extras = {} if confidence and method in ("random_forest", "rf", "supervised") else None
+        extras = None
+        if (confidence or importance_mask is not None) and method in ("random_forest", "rf", "supervised"):
+            extras = {"want_confidence": bool(confidence), "importance_mask": importance_mask}
         out = _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys, labeled_roi_file,
                         strict_reference, extras)
     finally:
@@ -230,20 +250,36 @@ def _run_classification(feature_file_path, method, output_dir, use_hierarchical_
         save_classification_as_geotiff(out, feats, os.path.join(output_dir, f"{method}_classification_map.tif"))
     else:
         print("警告: 元数据不完整，无法将分类结果保存为带地理参考的GeoTIFF。")
-    if extras:
+    if extras and "proba" in extras:
         np.save(os.path.join(output_dir, "rf_class_probabilities.npy"), extras["proba"])
         np.save(os.path.join(output_dir, "rf_confidence.npy"), extras["confidence"])
         if all(feats.get(k) is not None for k in ("transform", "crs", "width", "height")):
             from .tiff import write_tiff
             write_tiff(os.path.join(output_dir, f"{method}_confidence_map.tif"), extras["confidence"], transform=feats["transform"],
                        epsg=_epsg_of(feats["crs"]), geographic=_is_geographic(feats["crs"]), compress="lzw", tiled=True)
+    if extras and "importance" in extras:
+        _save_importance(os.path.join(output_dir, IMPORTANCE_FILE), extras["importance"], extras["feature_names"])
     return out
+
+
+def _save_importance(path: str, imp, names) -> None:
+    import json
+    with open(path, "w") as f:
+        json.dump({"feature_names": list(names), "importances_mean": imp["importances_mean"].tolist(),
+                   "importances_std": imp["importances_std"].tolist(), "importances": imp["importances"].tolist(),
+                   "baseline_score": imp["baseline_score"], "n_samples": imp["n_samples"], "n_repeats": IMPORTANCE_REPEATS,
+                   "random_state": IMPORTANCE_SEED}, f, indent=1)
+    mean = imp["importances_mean"]
+    print(f"随机森林置换特征重要性 ({imp['n_samples']} 个标注像素, 基准准确率 {imp['baseline_score']:.4f}):")
+    for i in np.argsort(mean)[::-1]:
+        print(f"    特征 '{names[i]}': {mean[i]:.4f}")
 
 
 def _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys, labeled_roi_file, strict_reference,
               extras=None):
     """The dispatch of scripts/3_classification.py:335-488 on a normalised feature dictionary -> label map or None.
-    extras: a dict the forest branch fills with 'proba' (H, W, C) and 'confidence' (H, W), or None."""
+    extras: None, or a dict of requests the forest branch answers in place: 'want_confidence' -> 'proba' (H, W, C) and
+    'confidence' (H, W); 'importance_mask' (an (H, W) label mask) -> 'importance' and 'feature_names'."""
     from modules.features.extract import (prepare_training_samples, rule_based_classification, supervised_classification_predict,
                                           train_random_forest_classifier, unsupervised_kmeans_classification)
     shape = (feats["height"], feats["width"])
@@ -298,9 +334,14 @@ def _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, class
                 joblib.dump(classifier, model_path)
                 print(f"随机森林模型训练并保存至: {model_path}")
             out = supervised_classification_predict(arr, classifier)
-            if extras is not None:   # the same pixels as the label map saw: NaN -> 0 (extract.py:690-719)
+            if extras is not None and extras.get("want_confidence"):   # the same pixels as the label map saw: NaN -> 0 (extract.py:690-719)
                 from .forest import image_proba_and_confidence
                 extras["proba"], extras["confidence"] = image_proba_and_confidence(classifier, np.nan_to_num(arr, nan=0.0))
+            if extras is not None and extras.get("importance_mask") is not None:
+                from .forest_importance import permutation_importance_image
+                extras["importance"] = permutation_importance_image(classifier, arr, extras["importance_mask"],
+                                                                    n_repeats=IMPORTANCE_REPEATS, random_state=IMPORTANCE_SEED)
+                extras["feature_names"] = names
             return out
         except _rt_unsupported():
             raise
@@ -322,7 +363,7 @@ def _rt_unsupported():
 # --------------------------------------------------------------------------------------------------
 def run_scripts_2_3(image_path: str, output_dir: str, classify: Optional[str] = None, preprocessing: bool = True, n_clusters: int = 7,
                     ctx: Optional[Context] = None, evaluate: Optional[str] = None, raw: bool = False,
-                    confidence: bool = False) -> Dict[str, object]:
+                    confidence: bool = False, importance: Optional[str] = None) -> Dict[str, object]:
     """Reads the GeoTIFF's bands as float32 with nodata -> NaN (scripts/2:154-161), runs the feature stage, writes
     <output_dir>/feature_outputs/{level1,level2,all_hierarchical}_features.npy, all_features_and_metadata.pkl and
     all_hierarchical_features.tif (scripts/2:193-258), then — `classify` in {'kmeans', 'rule_based', 'random_forest'} —
@@ -331,7 +372,10 @@ def run_scripts_2_3(image_path: str, output_dir: str, classify: Optional[str] = 
     raw: the image is a raw DN raster: stage 1 (scripts/1) runs first on the device and writes the reference's product,
     <output_dir>/preprocessed/<stem>_preprocessed.tif, and its uint8 planes go to the feature stage without leaving HBM.
     confidence: with classify='random_forest', the class probabilities and the confidence map beside the class map
-    (run_forest_confidence_stage)."""
+    (run_forest_confidence_stage).
+    importance: with classify='random_forest', a ROI mask (.npy / .tif, read as `evaluate` reads its mask): the permutation
+    importance of the forest's features over its labelled pixels, written as segmentation_results/rf_permutation_importance.json
+    (run_forest_importance_stage)."""
     if raw:
         from .preprocess import run_preprocessing_stage
         pdir = os.path.join(output_dir, "preprocessed")
@@ -359,7 +403,11 @@ def run_scripts_2_3(image_path: str, output_dir: str, classify: Optional[str] = 
         res["preprocessed"] = ppath
     if classify:
         sdir = os.path.join(output_dir, "segmentation_results")
-        if confidence and classify == "random_forest":
+        if importance and classify == "random_forest":
+            from .evaluate import ClassificationEvaluator
+            res["class_map"] = run_forest_importance_stage(paths["pkl"], ClassificationEvaluator._load(importance), sdir, True,
+                                                           confidence=confidence, ctx=ctx)
+        elif confidence and classify == "random_forest":
             res["class_map"] = run_forest_confidence_stage(paths["pkl"], sdir, True, ctx=ctx)
         else:
             res["class_map"] = run_classification_stage(paths["pkl"], classify, sdir, True, n_clusters=n_clusters, ctx=ctx)
@@ -379,6 +427,8 @@ def parse_args(ap, argv=None):
         ap.error("--evaluate needs --classify")
     if a.confidence and a.classify != "random_forest":
         ap.error("--confidence needs --classify random_forest")
+    if a.importance and a.classify != "random_forest":
+        ap.error("--importance needs --classify random_forest")
     return a
 
 
@@ -396,6 +446,9 @@ def build_parser():
                     help="the image is a raw DN raster: run stage 1 (scripts/1) on the GPU first, writing OUTPUT_DIR/preprocessed/<stem>_preprocessed.tif")
     ap.add_argument("--confidence", action="store_true",
                     help="with --classify random_forest: also write rf_class_probabilities.npy (H, W, C), rf_confidence.npy and a confidence GeoTIFF")
+    ap.add_argument("--importance", metavar="ROI_MASK",
+                    help="with --classify random_forest: permutation importance of the features over this ROI mask's labelled pixels "
+                         "(.npy / .tif) -> rf_permutation_importance.json")
     return ap
 
 
@@ -403,7 +456,7 @@ def main(argv=None) -> int:
     ap = build_parser()
     a = parse_args(ap, argv)
     res = run_scripts_2_3(a.image, a.output_dir, a.classify, not a.no_preprocessing, a.n_clusters, evaluate=a.evaluate, raw=a.raw,
-                          confidence=a.confidence)
+                          confidence=a.confidence, importance=a.importance)
     if a.raw:
         print(f"preprocessed: {res['preprocessed']}")
     for k, v in res["paths"].items():
