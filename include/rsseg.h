@@ -353,6 +353,26 @@ int rsseg_kmeans_fit_predict_mm(rsseg_ctx *ctx, const void *const *d_planes, int
                                 uint32_t seed, int max_iter, double tol, int32_t *d_labels, double *centers,
                                 rsseg_kmeans_info *info, const double *local_min, const double *local_max);
 
+/* K18: a FITTED model applied to planes it may not have been fitted on (MinMaxScaler.transform + KMeans.predict): labels,
+ * on request the distance of every pixel to the centre of its label (d_dist) and the scene's per-cluster pixel counts and
+ * inertia (info).  Inertia is the exact sum of the squared distances rounded to 2^-40; a pixel whose squared distance
+ * reaches 2^23 / chunk - 2^-41 (512 for float32, 1024 for float64) is left out of it and raises `overflow`: the call then
+ * still returns RSSEG_OK with inertia = +inf, and labels, counts and distances stay valid.
+ * The summary is this context's own: with a communicator installed the call reduces NOTHING; a sharded caller adds the
+ * counts and the inertia of its ranks itself.  n_local == 0 is legal (zero counts, inertia 0). */
+typedef struct rsseg_kmeans_apply_info {
+    int64_t counts[RSSEG_MAX_CLUSTERS];
+    double  inertia;      /* +inf when overflow */
+    int32_t overflow;
+    double  ms;           /* wall milliseconds of the call */
+} rsseg_kmeans_apply_info;
+
+int rsseg_kmeans_predict(rsseg_ctx *ctx, const void *const *d_planes, int F, int dtype, int64_t n_local, int k,
+                         const double *centers,  /* host, k*F: cluster_centers_ as the fit returns them */
+                         const double *scale, const double *min_,   /* host, F each: rsseg_kmeans_info.scale / .min */
+                         int32_t *d_labels, void *d_dist /* NULL or T[n_local] */,
+                         rsseg_kmeans_apply_info *info /* NULL: no summary */);
+
 /* ---- K11: random-forest inference ---------------------------------------------------------- */
 /* Flattened sklearn forest (tree_ arrays concatenated; children are tree-local, -1 = leaf).
  * value: (n_nodes_total x n_classes) float64 class fractions.  The forest is copied to the device

@@ -38,6 +38,15 @@ class KMeansInfo(C.Structure):
     ]
 
 
+class KMeansApplyInfo(C.Structure):
+    _fields_ = [
+        ("counts", C.c_int64 * MAX_CLUSTERS),
+        ("inertia", C.c_double),
+        ("overflow", C.c_int32),
+        ("ms", C.c_double),
+    ]
+
+
 # rsseg_forest_job of include/rsseg.h as a NumPy record: one per tree of rsseg_forest_fit_jobs
 FOREST_JOB = [("counts_row", "<i8"), ("weight_total", "<i8"), ("seed", "<u4"), ("max_depth", "<i4"), ("min_samples_split", "<i4"),
               ("min_samples_leaf", "<i4"), ("max_features", "<i4"), ("reserved", "<i4")]
@@ -115,6 +124,8 @@ SIGNATURES = {
                                         C.POINTER(C.c_double), C.POINTER(KMeansInfo)]),
     "rsseg_kmeans_fit_predict_mm": (_int, [_vp, _PP, _int, _int, _i64, _int, C.c_uint32, _int, C.c_double, _vp,
                                            C.POINTER(C.c_double), C.POINTER(KMeansInfo), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rsseg_kmeans_predict": (_int, [_vp, _PP, _int, _int, _i64, _int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _vp, _vp,
+                                    C.POINTER(KMeansApplyInfo)]),
     "rsseg_ctx_allreduce": (_int, [_vp, _i64, _i64, _int, _int]),
     "rsseg_rccl_unique_id": (_int, [C.c_char_p, _vp]),
     "rsseg_ctx_set_comm_rccl": (_int, [_vp, _int, _int, _vp, C.c_char_p, _vp, C.c_size_t]),

@@ -748,6 +748,38 @@ class Context:
                     centers=centers)
         return labels[:n], meta
 
+    # ---- K18 -----------------------------------------------------------------------------------
+    def kmeans_predict(self, planes: Sequence, centers, scale, min_, want_distance: bool = False, want_summary: bool = False):
+        """A fitted model (cluster_centers_, MinMaxScaler scale_ / min_) applied to planes: (labels int32, distance in the planes'
+        dtype or None, summary dict or None).  The summary is this context's own (nothing is reduced across ranks)."""
+        torch = _torch()
+        F, n = len(planes), planes[0].numel() if len(planes) else 0
+        if F == 0:
+            raise ValueError("kmeans: no feature planes")
+        dt = planes[0].dtype
+        if any(p.dtype != dt for p in planes) or dt not in (torch.float32, torch.float64):
+            raise ValueError("kmeans planes must all be float32 or all float64")
+        centers = np.ascontiguousarray(centers, dtype=np.float64)
+        scale = np.ascontiguousarray(scale, dtype=np.float64).reshape(-1)
+        min_ = np.ascontiguousarray(min_, dtype=np.float64).reshape(-1)
+        if centers.ndim != 2 or centers.shape[1] != F or scale.size != F or min_.size != F:
+            raise ValueError(f"kmeans_predict: the model has {centers.shape[-1] if centers.ndim else 0} features "
+                             f"(scale {scale.size}, min_ {min_.size}), the call {F} planes")
+        k = centers.shape[0]
+        labels = self.empty(max(n, 1), torch.int32)
+        dist = self.empty(max(n, 1), dt) if want_distance else None
+        info = L.KMeansApplyInfo() if want_summary else None
+        dp = C.POINTER(C.c_double)
+        self._chk(self.lib.rsseg_kmeans_predict(self.h, self._pp(planes), F, L.F32 if dt == torch.float32 else L.F64, n, k,
+                                                centers.ctypes.data_as(dp), scale.ctypes.data_as(dp), min_.ctypes.data_as(dp),
+                                                C.c_void_p(labels.data_ptr()), C.c_void_p(dist.data_ptr()) if want_distance else None,
+                                                C.byref(info) if want_summary else None))
+        summary = None
+        if want_summary:
+            summary = dict(counts=np.array(info.counts[:k], dtype=np.int64), inertia=float(info.inertia), overflow=bool(info.overflow),
+                           ms=info.ms)
+        return labels[:n], (dist[:n] if want_distance else None), summary
+
     # ---- K11 -----------------------------------------------------------------------------------
     def forest_load(self, forest: dict):
         f = forest

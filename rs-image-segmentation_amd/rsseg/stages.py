@@ -208,9 +208,71 @@ def run_forest_confidence_stage(feature_file_path, output_dir="segmentation_outp
                                labeled_roi_file, False, ctx, True)
 
 
-def _run_classification(feature_file_path, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys,
-                        labeled_roi_file, strict_reference, ctx, confidence, importance_mask=None) -> Optional[np.ndarray]:
-    from modules.features.extract import load_features, normalize_features_structure, unsupervised_kmeans_classification
+KMEANS_SUMMARY_FILE = "kmeans_model_summary.json"
+
+
+def run_kmeans_model_stage(feature_file_path, model_path, output_dir="segmentation_outputs", *, feature_keys=None,
+                           ctx: Optional[Context] = None) -> Optional[np.ndarray]:
+    """The 'kmeans' branch of run_classification_stage with a SAVED model (rsseg.kmeans_model.KMeansModel.save) instead of a
+    fit: the feature file is loaded and normalised the same way, the planes are selected as the fitted path selects them
+    (`feature_keys` as there; the model refuses another number of planes or, when it stores names, other planes), and the
+    model labels them, so that the cluster ids of this map are those of every other map of the model.  Writes
+    <output_dir>/classification_kmeans.npy (labels + 1 as uint8, the fitted path's layout), kmeans_classification_map.tif with
+    complete metadata, kmeans_distance.npy ((H, W), the distance of every pixel to its centre in the planes' dtype) and
+    kmeans_model_summary.json (counts per cluster, inertia, the overflow flag, the model file's name).  Returns the class map."""
+    from .kmeans_model import KMeansModel
+    model = KMeansModel.load(model_path)
+    feats = _load_normalised(feature_file_path, output_dir)
+    if feats is None:
+        return None
+    keys = _kmeans_keys(feats, feature_keys, False)
+    planes, shape = model.select_planes(feats, keys)
+    ctx = ctx or default_context()
+    dev = [ctx.to_device(np.ascontiguousarray(p, dtype=model.dtype).reshape(-1)) for p in _planes_in(planes, model.dtype)]
+    labels, dist, summary = ctx.kmeans_predict(dev, model.cluster_centers_.astype(np.float64), model.scale_.astype(np.float64),
+                                               model.min_.astype(np.float64), want_distance=True, want_summary=True)
+    out = (labels.cpu().numpy().reshape(shape) + 1).astype(np.uint8)
+    np.save(os.path.join(output_dir, "classification_kmeans.npy"), out)
+    _save_class_tif(out, feats, output_dir, "kmeans")
+    np.save(os.path.join(output_dir, "kmeans_distance.npy"), dist.cpu().numpy().reshape(shape))
+    import json
+    inertia = summary["inertia"]
+    with open(os.path.join(output_dir, KMEANS_SUMMARY_FILE), "w") as f:
+        json.dump({"model": os.path.basename(str(model_path)), "n_clusters": model.n_clusters, "n_features": model.n_features_in_,
+                   "counts": summary["counts"].tolist(), "inertia": inertia if np.isfinite(inertia) else None,
+                   "overflow": bool(summary["overflow"])}, f, indent=1)
+    return out
+
+
+def _planes_in(planes, dt):
+    """The selected planes must already be of the model's dtype class (float32 iff every plane is float32, as the fit stacks them)."""
+    got = np.result_type(*[np.asarray(p).dtype for p in planes])
+    got = np.dtype(np.float32) if got == np.float32 else np.dtype(np.float64)
+    if got != np.dtype(dt):
+        raise ValueError(f"KMeansModel: the selected planes stack to {got.name}, the model was fitted in {np.dtype(dt).name}")
+    return planes
+
+
+def _kmeans_keys(feats, feature_keys, strict_reference):
+    """The key selection of the 'kmeans' branch (scripts/3:377-391; see run_classification_stage)."""
+    wanted = ["ndvi", "ndwi", "ndbi", "texture_mean", "hierarchical_all"] if feature_keys is None else list(feature_keys)
+    valid = [k for k in wanted if isinstance(feats.get(k), np.ndarray) and feats[k].ndim in (2, 3)]
+    if not valid:
+        print(f"警告: 为KMeans指定的特征键 {wanted} 在数据中均不可用，将使用自动选择。")
+    return valid if (valid or strict_reference) else None      # the reference passes [] and raises (scripts/3:391, extract.py:533)
+
+
+def _save_class_tif(out, feats, output_dir, method):
+    from modules.features.extract import save_classification_as_geotiff
+    if all(feats.get(k) is not None for k in ("transform", "crs", "width", "height")):   # scripts/3:495-498
+        save_classification_as_geotiff(out, feats, os.path.join(output_dir, f"{method}_classification_map.tif"))
+    else:
+        print("警告: 元数据不完整，无法将分类结果保存为带地理参考的GeoTIFF。")
+
+
+def _load_normalised(feature_file_path, output_dir):
+    """The feature file as scripts/3:295-311 loads and checks it -> the normalised dictionary, or None after the reference's message."""
+    from modules.features.extract import load_features, normalize_features_structure
     os.makedirs(output_dir, exist_ok=True)
     try:
         raw = load_features(feature_file_path)
@@ -230,6 +292,15 @@ def _run_classification(feature_file_path, method, output_dir, use_hierarchical_
     except Exception as e:  # noqa: BLE001 — scripts/3:307-311 prints and returns
         print(f"加载或规范化特征失败: {e}")
         return None
+    return feats
+
+
+def _run_classification(feature_file_path, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys,
+                        labeled_roi_file, strict_reference, ctx, confidence, importance_mask=None,
+                        save_kmeans_model=None) -> Optional[np.ndarray]:
+    feats = _load_normalised(feature_file_path, output_dir)
+    if feats is None:
+        return None
     from . import runtime as _rt
     prev_ctx = _rt._default_ctx
     if ctx is not None:   # the mirrors run on the process-wide context: lend them this one for the duration of the call
@@ -238,18 +309,18 @@ def _run_classification(feature_file_path, method, output_dir, use_hierarchical_
         extras = None
         if (confidence or importance_mask is not None) and method in ("random_forest", "rf", "supervised"):
             extras = {"want_confidence": bool(confidence), "importance_mask": importance_mask}
+        if save_kmeans_model and method == "kmeans":
+            extras = {"want_kmeans_model": True}
         out = _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys, labeled_roi_file,
                         strict_reference, extras)
     finally:
         _rt._default_ctx = prev_ctx
     if out is None:
         return None
-    from modules.features.extract import save_classification_as_geotiff
     np.save(os.path.join(output_dir, f"classification_{method}.npy"), out)
-    if all(feats.get(k) is not None for k in ("transform", "crs", "width", "height")):   # scripts/3:495-498
-        save_classification_as_geotiff(out, feats, os.path.join(output_dir, f"{method}_classification_map.tif"))
-    else:
-        print("警告: 元数据不完整，无法将分类结果保存为带地理参考的GeoTIFF。")
+    _save_class_tif(out, feats, output_dir, method)
+    if extras and "kmeans_model" in extras:
+        print(f"KMeans模型保存至: {extras['kmeans_model'].save(save_kmeans_model)}")
     if extras and "proba" in extras:
         np.save(os.path.join(output_dir, "rf_class_probabilities.npy"), extras["proba"])
         np.save(os.path.join(output_dir, "rf_confidence.npy"), extras["confidence"])
@@ -279,7 +350,8 @@ def _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, class
               extras=None):
     """The dispatch of scripts/3_classification.py:335-488 on a normalised feature dictionary -> label map or None.
     extras: None, or a dict of requests the forest branch answers in place: 'want_confidence' -> 'proba' (H, W, C) and
-    'confidence' (H, W); 'importance_mask' (an (H, W) label mask) -> 'importance' and 'feature_names'."""
+    'confidence' (H, W); 'importance_mask' (an (H, W) label mask) -> 'importance' and 'feature_names'; the kmeans branch
+    answers 'want_kmeans_model' -> 'kmeans_model' (the KMeansModel of the fit that made the labels)."""
     from modules.features.extract import (prepare_training_samples, rule_based_classification, supervised_classification_predict,
                                           train_random_forest_classifier, unsupervised_kmeans_classification)
     shape = (feats["height"], feats["width"])
@@ -294,11 +366,11 @@ def _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, class
         rules["height"], rules["width"] = shape
         return rule_based_classification(rules)
     if method == "kmeans":
-        wanted = ["ndvi", "ndwi", "ndbi", "texture_mean", "hierarchical_all"] if feature_keys is None else list(feature_keys)
-        valid = [k for k in wanted if isinstance(feats.get(k), np.ndarray) and feats[k].ndim in (2, 3)]
-        if not valid:
-            print(f"警告: 为KMeans指定的特征键 {wanted} 在数据中均不可用，将使用自动选择。")
-        keys = valid if (valid or strict_reference) else None      # the reference passes [] and raises (scripts/3:391, extract.py:533)
+        keys = _kmeans_keys(feats, feature_keys, strict_reference)
+        if extras is not None and extras.get("want_kmeans_model"):   # the same call on the same planes, its model kept
+            from .kmeans_model import KMeansModel
+            extras["kmeans_model"], labels = KMeansModel.fit_features(feats, n_clusters, keys)
+            return (labels + 1).astype(np.uint8)
         return (unsupervised_kmeans_classification(feats, n_clusters, keys) + 1).astype(np.uint8)   # scripts/3:394
     if method in ("random_forest", "rf", "supervised"):
         arr, names = None, []
@@ -376,6 +448,14 @@ def run_scripts_2_3(image_path: str, output_dir: str, classify: Optional[str] = 
     importance: with classify='random_forest', a ROI mask (.npy / .tif, read as `evaluate` reads its mask): the permutation
     importance of the forest's features over its labelled pixels, written as segmentation_results/rf_permutation_importance.json
     (run_forest_importance_stage)."""
+    return _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters, ctx, evaluate, raw, confidence, importance)
+
+
+def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters, ctx, evaluate, raw, confidence, importance,
+                     kmeans_model: Optional[str] = None, save_kmeans_model: Optional[str] = None) -> Dict[str, object]:
+    """run_scripts_2_3, and with classify='kmeans' the two model options of the command line: `save_kmeans_model` fits as
+    always and also writes the fitted model there (KMeansModel.save; the class map is the same file byte for byte),
+    `kmeans_model` applies a saved model and fits nothing (run_kmeans_model_stage)."""
     if raw:
         from .preprocess import run_preprocessing_stage
         pdir = os.path.join(output_dir, "preprocessed")
@@ -409,6 +489,11 @@ def run_scripts_2_3(image_path: str, output_dir: str, classify: Optional[str] = 
                                                            confidence=confidence, ctx=ctx)
         elif confidence and classify == "random_forest":
             res["class_map"] = run_forest_confidence_stage(paths["pkl"], sdir, True, ctx=ctx)
+        elif kmeans_model and classify == "kmeans":
+            res["class_map"] = run_kmeans_model_stage(paths["pkl"], kmeans_model, sdir, ctx=ctx)
+        elif save_kmeans_model and classify == "kmeans":
+            res["class_map"] = _run_classification(paths["pkl"], classify, sdir, True, n_clusters, None, None, "labeled_roi.tif", False, ctx,
+                                                   False, save_kmeans_model=save_kmeans_model)
         else:
             res["class_map"] = run_classification_stage(paths["pkl"], classify, sdir, True, n_clusters=n_clusters, ctx=ctx)
         res["segmentation_dir"] = sdir
@@ -429,6 +514,10 @@ def parse_args(ap, argv=None):
         ap.error("--confidence needs --classify random_forest")
     if a.importance and a.classify != "random_forest":
         ap.error("--importance needs --classify random_forest")
+    if (a.kmeans_model or a.save_kmeans_model) and a.classify != "kmeans":
+        ap.error("--kmeans-model / --save-kmeans-model need --classify kmeans")
+    if a.kmeans_model and a.save_kmeans_model:
+        ap.error("--kmeans-model applies a saved model and fits nothing: it does not go with --save-kmeans-model")
     return a
 
 
@@ -449,14 +538,19 @@ def build_parser():
     ap.add_argument("--importance", metavar="ROI_MASK",
                     help="with --classify random_forest: permutation importance of the features over this ROI mask's labelled pixels "
                          "(.npy / .tif) -> rf_permutation_importance.json")
+    ap.add_argument("--save-kmeans-model", metavar="PATH",
+                    help="with --classify kmeans: fit as always and also write the fitted model (an .npz, rsseg.kmeans_model.KMeansModel)")
+    ap.add_argument("--kmeans-model", metavar="PATH",
+                    help="with --classify kmeans: apply this saved model instead of fitting -> the class map with the model's cluster ids, "
+                         "kmeans_distance.npy and kmeans_model_summary.json")
     return ap
 
 
 def main(argv=None) -> int:
     ap = build_parser()
     a = parse_args(ap, argv)
-    res = run_scripts_2_3(a.image, a.output_dir, a.classify, not a.no_preprocessing, a.n_clusters, evaluate=a.evaluate, raw=a.raw,
-                          confidence=a.confidence, importance=a.importance)
+    res = _run_scripts_2_3(a.image, a.output_dir, a.classify, not a.no_preprocessing, a.n_clusters, None, a.evaluate, a.raw, a.confidence,
+                           a.importance, a.kmeans_model, a.save_kmeans_model)
     if a.raw:
         print(f"preprocessed: {res['preprocessed']}")
     for k, v in res["paths"].items():
