@@ -373,6 +373,41 @@ int rsseg_kmeans_predict(rsseg_ctx *ctx, const void *const *d_planes, int F, int
                          int32_t *d_labels, void *d_dist /* NULL or T[n_local] */,
                          rsseg_kmeans_apply_info *info /* NULL: no summary */);
 
+/* ---- K19: valid masks and order-preserving compaction ------------------------------------------ */
+/* A scene with a nodata collar and holes is classified on its valid pixels only: build a mask, compact the feature planes
+ * to X[valid] in raster order (exactly the matrix scikit-learn sees), run rsseg_kmeans_fit_predict / rsseg_kmeans_predict /
+ * rsseg_forest_predict* on the compacted planes unchanged, expand the per-pixel results back with a fill value.
+ * A mask is a uint8 plane; any non-zero byte means valid.  Planes, masks and outputs may have any alignment that holds their
+ * element (16-byte accesses are used where 16-byte alignment holds).  n < 2^39.  Errors name the argument. */
+#define RSSEG_VALID_NAN 1     /* a NaN in any plane makes the pixel invalid */
+#define RSSEG_VALID_INF 2     /* +-inf in any plane */
+#define RSSEG_VALID_VALUE 4   /* a value equal to `nodata` cast to the planes' type (a value the type cannot hold matches nothing) */
+/* d_mask[i] = 1 iff pixel i passes every test of `flags` in every one of the P planes (dtype RSSEG_F32, RSSEG_F64 or RSSEG_U8;
+ * P <= 64) and, when d_and is given, d_and[i] != 0; else 0.  One pass over the planes.  *n_valid = the number of ones
+ * (integer atomics, one per workgroup).  n == 0 is legal.  Synchronous.  Profiler name "valid_mask". */
+int rsseg_valid_mask(rsseg_ctx *ctx, const void *const *d_planes, int P, int dtype, int64_t n, int flags, double nodata,
+                     const uint8_t *d_and /* NULL or uint8[n] */, uint8_t *d_mask, int64_t *n_valid);
+/* host-only: pixels per tile, and tiles one workgroup of the scan step takes per pass (tests place their seams by them) */
+int rsseg_compact_tile(void);
+int rsseg_compact_scan_span(void);
+/* The plan of a mask: d_tile_off[t] = the number of valid pixels before tile t, for t = 0 .. ceil(n / tile); the last entry
+ * and *n_valid are the mask's valid count.  Two launches (per-tile count, then one workgroup's scan over the counts), no
+ * workgroup waits for another.  d_tile_off is the CALLER's device buffer of ceil(n / tile) + 1 int64: it must outlive the
+ * classifier call that runs between compaction and expansion, and that call uses the context's workspace.  n == 0 is legal
+ * (one entry, 0).  Synchronous.  Profiler name "compact_plan". */
+int rsseg_compact_plan(rsseg_ctx *ctx, const uint8_t *d_mask, int64_t n, int64_t *d_tile_off, int64_t *n_valid);
+/* d_out[p][rank(i)] = d_in[p][i] for every valid i, in raster order (rank(i) = valid pixels before i); P planes of elements
+ * of elem_bytes (1, 4 or 8: any type of that size) in ONE launch, the mask bytes and in-tile ranks computed once per tile.
+ * d_out[p] holds n_valid elements and overlaps no input plane.  With every pixel valid the result is a plain copy; with none
+ * nothing is written.  Algorithmic HBM traffic: n mask bytes + per plane the 16-byte vectors of the input that hold a valid
+ * pixel in, n_valid * elem_bytes out.  Profiler name "compact". */
+int rsseg_compact_planes(rsseg_ctx *ctx, const uint8_t *d_mask, const int64_t *d_tile_off, int64_t n, const void *const *d_in, int P,
+                         int elem_bytes /* 1, 4, 8 */, void *const *d_out);
+/* d_out[i] = mask[i] ? d_in[rank(i)] : *fill, for i < n.  fill: host, elem_bytes.  d_in holds n_valid elements (NULL when
+ * there are none); d_out must not overlap it (RSSEG_ERR_INVALID "d_out aliases d_in").  Profiler name "expand". */
+int rsseg_expand_plane(rsseg_ctx *ctx, const uint8_t *d_mask, const int64_t *d_tile_off, int64_t n, const void *d_in, int elem_bytes,
+                       const void *fill /* host, elem_bytes */, void *d_out);
+
 /* ---- K11: random-forest inference ---------------------------------------------------------- */
 /* Flattened sklearn forest (tree_ arrays concatenated; children are tree-local, -1 = leaf).
  * value: (n_nodes_total x n_classes) float64 class fractions.  The forest is copied to the device

@@ -20,6 +20,7 @@ SUM, MIN, MAX = 0, 1, 2
 BORDER_REFLECT, BORDER_REFLECT101 = 0, 1
 MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE, MORPH_GRADIENT = 0, 1, 2, 3, 4
 MASK_AND, MASK_OR, MASK_ANDNOT, MASK_NOT = 0, 1, 2, 3
+VALID_NAN, VALID_INF, VALID_VALUE = 1, 2, 4   # rsseg_valid_mask's flags
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int)
 
@@ -126,6 +127,12 @@ SIGNATURES = {
                                            C.POINTER(C.c_double), C.POINTER(KMeansInfo), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rsseg_kmeans_predict": (_int, [_vp, _PP, _int, _int, _i64, _int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _vp, _vp,
                                     C.POINTER(KMeansApplyInfo)]),
+    "rsseg_valid_mask": (_int, [_vp, _PP, _int, _int, _i64, _int, C.c_double, _vp, _vp, C.POINTER(_i64)]),
+    "rsseg_compact_tile": (_int, []),
+    "rsseg_compact_scan_span": (_int, []),
+    "rsseg_compact_plan": (_int, [_vp, _vp, _i64, _vp, C.POINTER(_i64)]),
+    "rsseg_compact_planes": (_int, [_vp, _vp, _vp, _i64, _PP, _int, _int, _PP]),
+    "rsseg_expand_plane": (_int, [_vp, _vp, _vp, _i64, _vp, _int, _vp, _vp]),
     "rsseg_ctx_allreduce": (_int, [_vp, _i64, _i64, _int, _int]),
     "rsseg_rccl_unique_id": (_int, [C.c_char_p, _vp]),
     "rsseg_ctx_set_comm_rccl": (_int, [_vp, _int, _int, _vp, C.c_char_p, _vp, C.c_size_t]),

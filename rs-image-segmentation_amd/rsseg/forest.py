@@ -87,8 +87,12 @@ def confidence_map(model, features, ctx=None) -> np.ndarray:
     return _outputs(model, planes, False, True, ctx)[1].reshape(h, w)
 
 
-def image_proba_and_confidence(model, features, ctx=None):
-    """predict_image_proba and confidence_map from one launch."""
+def image_proba_and_confidence(model, features, ctx=None, mask=None):
+    """predict_image_proba and confidence_map from one launch.  mask ((H, W), non-zero = valid): the forest walks the valid
+    pixels only; the masked pixels get probability rows of 0 and confidence 0 (rsseg.masked)."""
+    if mask is not None:
+        from .masked import forest_proba_and_confidence_masked
+        return forest_proba_and_confidence_masked(model, features, mask, ctx)
     (h, w), planes = _image_planes(features)
     p, c = _outputs(model, planes, True, True, ctx)
     return p.reshape(h, w, -1), c.reshape(h, w)

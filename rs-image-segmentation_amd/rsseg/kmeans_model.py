@@ -70,9 +70,18 @@ class KMeansModel:
 
     # ---- fitting -----------------------------------------------------------------------------------
     @classmethod
-    def fit(cls, planes: Sequence, n_clusters: int, seed: int = 42, max_iter: int = 300, tol: float = 1e-4, feature_names=None, ctx=None):
-        """One Context.kmeans_fit_predict call -> (model, labels); the labels are the call's own."""
+    def fit(cls, planes: Sequence, n_clusters: int, seed: int = 42, max_iter: int = 300, tol: float = 1e-4, feature_names=None, ctx=None,
+            mask=None):
+        """One Context.kmeans_fit_predict call -> (model, labels); the labels are the call's own.
+        mask (non-zero = valid, of the planes' size): the fit sees the valid pixels only (rsseg.masked), labels are -1 at the
+        masked pixels and n_samples_fit_ is the valid count."""
         ctx = ctx or _default_ctx()
+        if mask is not None:
+            from .masked import kmeans_fit_predict_masked
+            labels, meta = kmeans_fit_predict_masked(planes, mask, int(n_clusters), seed, max_iter, tol, -1, ctx)
+            dt = np.float32 if all("float32" in str(p.dtype) for p in planes) else np.float64
+            return cls(meta["centers"].astype(dt), meta["scale"].astype(dt), meta["min"].astype(dt), feature_names, meta["n_iter"], seed,
+                       meta["n_valid"]), labels
         host = isinstance(planes[0], np.ndarray)
         shape = planes[0].shape if host else None
         if host:
@@ -86,7 +95,7 @@ class KMeansModel:
         return model, (labels.cpu().numpy().reshape(shape) if host else labels)
 
     # ---- applying ----------------------------------------------------------------------------------
-    def _apply(self, planes: Sequence, want_distance: bool, want_summary: bool, ctx):
+    def _apply(self, planes: Sequence, want_distance: bool, want_summary: bool, ctx, mask=None):
         ctx = ctx or _default_ctx()
         if len(planes) != self.n_features_in_:
             raise ValueError(f"KMeansModel: {len(planes)} planes, the model was fitted on {self.n_features_in_}")
@@ -100,8 +109,15 @@ class KMeansModel:
             planes = [ctx.to_device(np.ascontiguousarray(p, dtype=dt).reshape(-1)) for p in planes]
         elif self.dtype.name not in str(planes[0].dtype):
             raise ValueError(f"KMeansModel: {planes[0].dtype} planes, the model was fitted in {self.dtype.name}")
-        labels, dist, summary = ctx.kmeans_predict(planes, self.cluster_centers_.astype(np.float64), self.scale_.astype(np.float64),
-                                                   self.min_.astype(np.float64), want_distance=want_distance, want_summary=want_summary)
+        model = (self.cluster_centers_.astype(np.float64), self.scale_.astype(np.float64), self.min_.astype(np.float64))
+        if mask is None:
+            labels, dist, summary = ctx.kmeans_predict(planes, *model, want_distance=want_distance, want_summary=want_summary)
+        else:
+            from .masked import kmeans_predict_masked
+            labels, dist, summary, n_valid = kmeans_predict_masked(ctx, planes, mask, *model, want_distance=want_distance,
+                                                                   want_summary=want_summary)
+            if summary is not None:
+                summary = dict(summary, n_valid=n_valid)
         if host:
             labels = labels.cpu().numpy().reshape(shape)
             dist = None if dist is None else dist.cpu().numpy().reshape(shape)
@@ -110,17 +126,20 @@ class KMeansModel:
             summary["score"] = -summary["inertia"]
         return labels, dist, summary
 
-    def predict(self, planes: Sequence, ctx=None):
-        """int32 labels: NumPy planes in -> an array of the planes' shape; device tensors in -> a flat device tensor."""
-        return self._apply(planes, False, False, ctx)[0]
+    def predict(self, planes: Sequence, ctx=None, mask=None):
+        """int32 labels: NumPy planes in -> an array of the planes' shape; device tensors in -> a flat device tensor.
+        mask (non-zero = valid): only the valid pixels are labelled, the others get -1."""
+        return self._apply(planes, False, False, ctx, mask)[0]
 
-    def predict_with_distance(self, planes: Sequence, ctx=None):
-        """(labels, distance): the Euclidean distance of every scaled pixel to the centre of its label, in the planes' dtype."""
-        return self._apply(planes, True, False, ctx)[:2]
+    def predict_with_distance(self, planes: Sequence, ctx=None, mask=None):
+        """(labels, distance): the Euclidean distance of every scaled pixel to the centre of its label, in the planes' dtype.
+        With a mask: -1 and NaN at the masked pixels."""
+        return self._apply(planes, True, False, ctx, mask)[:2]
 
-    def summary(self, planes: Sequence, ctx=None) -> dict:
-        """counts (int64 per cluster), inertia, overflow, score = -inertia of this scene under the model."""
-        return self._apply(planes, False, True, ctx)[2]
+    def summary(self, planes: Sequence, ctx=None, mask=None) -> dict:
+        """counts (int64 per cluster), inertia, overflow, score = -inertia of this scene under the model.  With a mask they
+        cover the valid pixels only, and n_valid is added."""
+        return self._apply(planes, False, True, ctx, mask)[2]
 
     def select_planes(self, features_dict, feature_keys_to_use=None):
         """The planes unsupervised_kmeans_classification would cluster, checked against the model -> (planes, (H, W))."""
@@ -135,18 +154,20 @@ class KMeansModel:
                 raise ValueError(f"KMeansModel: the selected planes are not the ones the model was fitted on ({', '.join(diff[:4])})")
         return planes, shape
 
-    def predict_features(self, features_dict, feature_keys_to_use=None, ctx=None):
-        """unsupervised_kmeans_classification's selection of planes, labelled by this model -> (H, W) int32."""
+    def predict_features(self, features_dict, feature_keys_to_use=None, ctx=None, mask=None):
+        """unsupervised_kmeans_classification's selection of planes, labelled by this model -> (H, W) int32 (-1 where an (H, W)
+        `mask` is zero)."""
         planes, shape = self.select_planes(features_dict, feature_keys_to_use)
-        return self.predict([np.asarray(p) for p in planes], ctx=ctx).reshape(shape)
+        return self.predict([np.asarray(p) for p in planes], ctx=ctx, mask=mask).reshape(shape)
 
     @classmethod
-    def fit_features(cls, features_dict, n_clusters: int = 5, feature_keys_to_use=None, seed: int = 42, ctx=None):
-        """unsupervised_kmeans_classification that keeps its model -> (model, (H, W) int32 labels)."""
+    def fit_features(cls, features_dict, n_clusters: int = 5, feature_keys_to_use=None, seed: int = 42, ctx=None, mask=None):
+        """unsupervised_kmeans_classification that keeps its model -> (model, (H, W) int32 labels; -1 where an (H, W) `mask` is
+        zero, and the fit has not seen those pixels)."""
         from modules.features.extract import _select_planes
         planes, shape = _select_planes(features_dict, feature_keys_to_use)
         model, labels = cls.fit([np.asarray(p) for p in planes], n_clusters, seed=seed,
-                                feature_names=plane_names(features_dict, feature_keys_to_use), ctx=ctx)
+                                feature_names=plane_names(features_dict, feature_keys_to_use), ctx=ctx, mask=mask)
         return model, labels.reshape(shape)
 
     # ---- scikit-learn ------------------------------------------------------------------------------

@@ -30,6 +30,15 @@ def _torch():
     return torch
 
 
+class CompactPlan:
+    """What Context.compact_plan returns and compact / expand take: the mask (flat uint8 device tensor), its tile offsets
+    (device int64, ceil(n / tile) + 1 entries, the plan's own memory), the pixel count n and the valid count n_valid."""
+    __slots__ = ("mask", "tile_off", "n", "n_valid")
+
+    def __init__(self, mask, tile_off, n: int, n_valid: int):
+        self.mask, self.tile_off, self.n, self.n_valid = mask, tile_off, int(n), int(n_valid)
+
+
 def make_allreduce_hook(buf, group=None, stream=None):
     """The Python side of rsseg_allreduce_fn: reduces `count` elements of `dtype` at byte `offset` of the
     communication buffer `buf` (a uint8 tensor; on the GPU in production, so the collective is RCCL over
@@ -779,6 +788,76 @@ class Context:
             summary = dict(counts=np.array(info.counts[:k], dtype=np.int64), inertia=float(info.inertia), overflow=bool(info.overflow),
                            ms=info.ms)
         return labels[:n], (dist[:n] if want_distance else None), summary
+
+    # ---- K19: valid masks and order-preserving compaction --------------------------------------
+    def valid_mask(self, planes: Sequence, nan: bool = True, inf: bool = False, nodata=None, and_mask=None):
+        """(uint8 mask, n_valid): a pixel is valid iff no plane holds a NaN (`nan`), +-inf (`inf`) or `nodata` (cast to the
+        planes' dtype) there and, when given, and_mask is non-zero there.  planes: flat float32, float64 or uint8 device
+        tensors of one dtype and length."""
+        torch = _torch()
+        if not len(planes):
+            raise ValueError("valid_mask: no planes")
+        dt, n = planes[0].dtype, planes[0].numel()
+        codes = {torch.float32: L.F32, torch.float64: L.F64, torch.uint8: L.U8}
+        if dt not in codes or any(p.dtype != dt or p.numel() != n for p in planes):
+            raise ValueError("valid_mask: planes must be float32, float64 or uint8, all of one dtype and length")
+        if and_mask is not None and (and_mask.dtype != torch.uint8 or and_mask.numel() != n):
+            raise ValueError("valid_mask: and_mask must be a uint8 plane of the planes' length")
+        flags = (L.VALID_NAN if nan else 0) | (L.VALID_INF if inf else 0) | (L.VALID_VALUE if nodata is not None else 0)
+        mask = self.empty(max(n, 1), torch.uint8)
+        nv = C.c_int64(0)
+        self._chk(self.lib.rsseg_valid_mask(self.h, self._pp(planes), len(planes), codes[dt], n, flags,
+                                            C.c_double(0.0 if nodata is None else float(nodata)),
+                                            None if and_mask is None else C.c_void_p(and_mask.data_ptr()), C.c_void_p(mask.data_ptr()),
+                                            C.byref(nv)))
+        return mask[:n], int(nv.value)
+
+    def compact_plan(self, mask) -> "CompactPlan":
+        """The plan compact() and expand() share for one mask (a flat uint8 device tensor, non-zero = valid): the tile offsets
+        live in a tensor of the plan's own, not in the context's workspace, so a classifier call may run in between."""
+        torch = _torch()
+        if mask.dtype != torch.uint8:
+            raise ValueError("compact_plan: the mask must be a uint8 plane")
+        n = mask.numel()
+        tile = self.lib.rsseg_compact_tile()
+        off = self.empty((n + tile - 1) // tile + 1, torch.int64)
+        nv = C.c_int64(0)
+        self._chk(self.lib.rsseg_compact_plan(self.h, C.c_void_p(mask.data_ptr()) if n else None, n, C.c_void_p(off.data_ptr()), C.byref(nv)))
+        return CompactPlan(mask, off, n, int(nv.value))
+
+    def compact(self, plan: "CompactPlan", planes: Sequence) -> List:
+        """planes[p][mask != 0] for every plane, in raster order: a list of new tensors of plan.n_valid elements.  Planes of one
+        element size (1, 4 or 8 bytes) share a launch."""
+        outs = [None] * len(planes)
+        by_size = {}
+        for i, p in enumerate(planes):
+            if p.numel() != plan.n:
+                raise ValueError(f"compact: plane {i} has {p.numel()} elements, the mask {plan.n}")
+            by_size.setdefault(p.element_size(), []).append(i)
+        for eb, idx in by_size.items():
+            if eb not in (1, 4, 8):
+                raise ValueError(f"compact: elements of {eb} bytes (1, 4 or 8 are taken)")
+            full = [self.empty(max(plan.n_valid, 1), planes[i].dtype) for i in idx]
+            self._chk(self.lib.rsseg_compact_planes(self.h, C.c_void_p(plan.mask.data_ptr()) if plan.n else None,
+                                                    C.c_void_p(plan.tile_off.data_ptr()), plan.n, self._pp([planes[i] for i in idx]), len(idx), eb,
+                                                    self._pp(full)))
+            for i, t in zip(idx, full):
+                outs[i] = t[:plan.n_valid]
+        return outs
+
+    def expand(self, plan: "CompactPlan", plane, fill):
+        """A tensor of plan.n elements: plane[rank(i)] where the mask is set, `fill` (cast to the plane's dtype) elsewhere."""
+        torch = _torch()
+        if plane.numel() != plan.n_valid:
+            raise ValueError(f"expand: the plane has {plane.numel()} elements, the mask {plan.n_valid} valid pixels")
+        eb = plane.element_size()
+        if eb not in (1, 4, 8):
+            raise ValueError(f"expand: elements of {eb} bytes (1, 4 or 8 are taken)")
+        fb = np.array(fill, dtype=torch.empty(0, dtype=plane.dtype).numpy().dtype).tobytes()
+        out = self.empty(max(plan.n, 1), plane.dtype)
+        self._chk(self.lib.rsseg_expand_plane(self.h, C.c_void_p(plan.mask.data_ptr()) if plan.n else None, C.c_void_p(plan.tile_off.data_ptr()),
+                                              plan.n, C.c_void_p(plane.data_ptr()) if plan.n_valid else None, eb, fb, C.c_void_p(out.data_ptr())))
+        return out[:plan.n]
 
     # ---- K11 -----------------------------------------------------------------------------------
     def forest_load(self, forest: dict):

@@ -131,15 +131,27 @@ def save_class_map_tif(class_map: np.ndarray, out_tif: str, transform=None, crs=
     return out_tif
 
 
-def run_kmeans_stage(hierarchical_all: np.ndarray, n_clusters: int = 7, ctx: Optional[Context] = None) -> np.ndarray:
+def run_kmeans_stage(hierarchical_all: np.ndarray, n_clusters: int = 7, ctx: Optional[Context] = None, *, valid_mask=None) -> np.ndarray:
     """KMeans branch of run_classification_stage on the 19-feature stack: labels + 1 as uint8
-    (scripts/3:390-394, 509-538: final_map = labels + 1, saved as uint8 with nodata 0)."""
+    (scripts/3:390-394, 509-538: final_map = labels + 1, saved as uint8 with nodata 0).
+    valid_mask ((H, W), non-zero = valid): the fit sees the valid pixels only and the class map is 0 at the others."""
     ctx = ctx or default_context()
     h, w, c = hierarchical_all.shape
     dt = np.float32 if hierarchical_all.dtype == np.float32 else np.float64
     dev = [ctx.to_device(np.ascontiguousarray(hierarchical_all[:, :, i], dtype=dt).reshape(-1)) for i in range(c)]
-    labels, _ = ctx.kmeans_fit_predict(dev, n_clusters)
+    if valid_mask is not None:
+        from .masked import kmeans_fit_predict_masked
+        labels, _ = kmeans_fit_predict_masked(dev, _check_valid_mask(valid_mask, (h, w)), n_clusters, ctx=ctx)
+    else:
+        labels, _ = ctx.kmeans_fit_predict(dev, n_clusters)
     return (labels.cpu().numpy().reshape(h, w) + 1).astype(np.uint8)
+
+
+def _check_valid_mask(valid_mask, shape):
+    m = np.asarray(valid_mask)
+    if m.shape != tuple(shape):
+        raise ValueError(f"valid_mask: shape {m.shape}, the raster is {tuple(shape)}")
+    return m
 
 
 RF_MODEL_FILE = "random_forest_model.joblib"   # scripts/3_classification.py:459
@@ -174,9 +186,25 @@ def run_classification_stage(feature_file_path, method='rule_based', output_dir=
     (scripts/3:495-498), <output_dir>/<method>_classification_map.tif (uint8 labels, nodata 0, LZW tiles); the PNG of
     scripts/3:491 is plotting (out of scope).  The reference returns None; this returns the label map as well (None on the
     reference's error paths, which print and return).  run_forest_confidence_stage is the 'random_forest' branch with the
-    class probabilities and the confidence map written beside the class map."""
+    class probabilities and the confidence map written beside the class map, run_masked_classification_stage the same
+    dispatch on the valid pixels of a scene with nodata."""
     return _run_classification(feature_file_path, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys,
                                labeled_roi_file, strict_reference, ctx, False)
+
+
+def run_masked_classification_stage(feature_file_path, method='rule_based', output_dir="segmentation_outputs", use_hierarchical_all=True, *,
+                                    valid_mask=None, n_clusters: int = 7, classifier=None, feature_keys=None,
+                                    labeled_roi_file: str = "labeled_roi.tif", strict_reference: bool = False, confidence: bool = False,
+                                    ctx: Optional[Context] = None) -> Optional[np.ndarray]:
+    """run_classification_stage with valid_mask ((H, W), non-zero = valid; rsseg.masked): the classifier sees the valid pixels
+    only — KMeans is fitted on them alone, the forest walks its trees for them alone — and the class map is 0 at the others,
+    which is what the GeoTIFF's nodata 0 says.  The rule-based map is painted 0 there.  Feature extraction came first and is
+    not masked.  valid_mask=None is run_classification_stage itself.  confidence (method 'random_forest'): the files of
+    run_forest_confidence_stage as well, with probability rows of 0 and confidence 0 at the masked pixels.  (A function of its
+    own, like run_forest_confidence_stage: the signatures of run_classification_stage and run_forest_confidence_stage are the
+    reference's plus a fixed set of keyword-only additions.)"""
+    return _run_classification(feature_file_path, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys,
+                               labeled_roi_file, strict_reference, ctx, bool(confidence), valid_mask=valid_mask)
 
 
 IMPORTANCE_FILE = "rf_permutation_importance.json"
@@ -203,7 +231,8 @@ def run_forest_confidence_stage(feature_file_path, output_dir="segmentation_outp
     and beside them <output_dir>/rf_class_probabilities.npy, (H, W, C) float64 = the forest's predict_proba of every pixel in
     the order of classes_, <output_dir>/rf_confidence.npy, (H, W) float64 = the largest of them, and, with complete
     metadata, <output_dir>/random_forest_confidence_map.tif (float64, LZW tiles).  Returns the label map.  (A function of
-    its own: the signature of run_classification_stage is the reference's plus a fixed set of keyword-only additions.)"""
+    its own: the signature of run_classification_stage is the reference's plus a fixed set of keyword-only additions.)
+    On a scene with nodata: run_masked_classification_stage(..., 'random_forest', valid_mask=..., confidence=True)."""
     return _run_classification(feature_file_path, "random_forest", output_dir, use_hierarchical_all, 7, classifier, None,
                                labeled_roi_file, False, ctx, True)
 
@@ -212,14 +241,16 @@ KMEANS_SUMMARY_FILE = "kmeans_model_summary.json"
 
 
 def run_kmeans_model_stage(feature_file_path, model_path, output_dir="segmentation_outputs", *, feature_keys=None,
-                           ctx: Optional[Context] = None) -> Optional[np.ndarray]:
+                           ctx: Optional[Context] = None, valid_mask=None) -> Optional[np.ndarray]:
     """The 'kmeans' branch of run_classification_stage with a SAVED model (rsseg.kmeans_model.KMeansModel.save) instead of a
     fit: the feature file is loaded and normalised the same way, the planes are selected as the fitted path selects them
     (`feature_keys` as there; the model refuses another number of planes or, when it stores names, other planes), and the
     model labels them, so that the cluster ids of this map are those of every other map of the model.  Writes
     <output_dir>/classification_kmeans.npy (labels + 1 as uint8, the fitted path's layout), kmeans_classification_map.tif with
     complete metadata, kmeans_distance.npy ((H, W), the distance of every pixel to its centre in the planes' dtype) and
-    kmeans_model_summary.json (counts per cluster, inertia, the overflow flag, the model file's name).  Returns the class map."""
+    kmeans_model_summary.json (counts per cluster, inertia, the overflow flag, the model file's name).  Returns the class map.
+    valid_mask ((H, W), non-zero = valid): only the valid pixels are labelled; the class map is 0 and the distance NaN at the
+    others, counts and inertia cover the valid pixels, and the summary also carries n_valid."""
     from .kmeans_model import KMeansModel
     model = KMeansModel.load(model_path)
     feats = _load_normalised(feature_file_path, output_dir)
@@ -229,8 +260,16 @@ def run_kmeans_model_stage(feature_file_path, model_path, output_dir="segmentati
     planes, shape = model.select_planes(feats, keys)
     ctx = ctx or default_context()
     dev = [ctx.to_device(np.ascontiguousarray(p, dtype=model.dtype).reshape(-1)) for p in _planes_in(planes, model.dtype)]
-    labels, dist, summary = ctx.kmeans_predict(dev, model.cluster_centers_.astype(np.float64), model.scale_.astype(np.float64),
-                                               model.min_.astype(np.float64), want_distance=True, want_summary=True)
+    extra = {}
+    if valid_mask is not None:
+        from .masked import kmeans_predict_masked
+        labels, dist, summary, n_valid = kmeans_predict_masked(ctx, dev, _check_valid_mask(valid_mask, shape),
+                                                               model.cluster_centers_.astype(np.float64), model.scale_.astype(np.float64),
+                                                               model.min_.astype(np.float64), want_distance=True, want_summary=True)
+        extra = {"n_valid": n_valid}
+    else:
+        labels, dist, summary = ctx.kmeans_predict(dev, model.cluster_centers_.astype(np.float64), model.scale_.astype(np.float64),
+                                                   model.min_.astype(np.float64), want_distance=True, want_summary=True)
     out = (labels.cpu().numpy().reshape(shape) + 1).astype(np.uint8)
     np.save(os.path.join(output_dir, "classification_kmeans.npy"), out)
     _save_class_tif(out, feats, output_dir, "kmeans")
@@ -240,7 +279,7 @@ def run_kmeans_model_stage(feature_file_path, model_path, output_dir="segmentati
     with open(os.path.join(output_dir, KMEANS_SUMMARY_FILE), "w") as f:
         json.dump({"model": os.path.basename(str(model_path)), "n_clusters": model.n_clusters, "n_features": model.n_features_in_,
                    "counts": summary["counts"].tolist(), "inertia": inertia if np.isfinite(inertia) else None,
-                   "overflow": bool(summary["overflow"])}, f, indent=1)
+                   "overflow": bool(summary["overflow"]), **extra}, f, indent=1)
     return out
 
 
@@ -297,10 +336,12 @@ def _load_normalised(feature_file_path, output_dir):
 
 def _run_classification(feature_file_path, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys,
                         labeled_roi_file, strict_reference, ctx, confidence, importance_mask=None,
-                        save_kmeans_model=None) -> Optional[np.ndarray]:
+                        save_kmeans_model=None, valid_mask=None) -> Optional[np.ndarray]:
     feats = _load_normalised(feature_file_path, output_dir)
     if feats is None:
         return None
+    if valid_mask is not None:
+        valid_mask = _check_valid_mask(valid_mask, (feats["height"], feats["width"]))
     from . import runtime as _rt
     prev_ctx = _rt._default_ctx
     if ctx is not None:   # the mirrors run on the process-wide context: lend them this one for the duration of the call
@@ -312,7 +353,7 @@ def _run_classification(feature_file_path, method, output_dir, use_hierarchical_
         if save_kmeans_model and method == "kmeans":
             extras = {"want_kmeans_model": True}
         out = _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys, labeled_roi_file,
-                        strict_reference, extras)
+                        strict_reference, extras, valid_mask)
     finally:
         _rt._default_ctx = prev_ctx
     if out is None:
@@ -347,8 +388,9 @@ def _save_importance(path: str, imp, names) -> None:
 
 
 def _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys, labeled_roi_file, strict_reference,
-              extras=None):
+              extras=None, valid_mask=None):
     """The dispatch of scripts/3_classification.py:335-488 on a normalised feature dictionary -> label map or None.
+    valid_mask: None, or an (H, W) array, non-zero = valid (run_classification_stage): class 0 at the other pixels.
     extras: None, or a dict of requests the forest branch answers in place: 'want_confidence' -> 'proba' (H, W, C) and
     'confidence' (H, W); 'importance_mask' (an (H, W) label mask) -> 'importance' and 'feature_names'; the kmeans branch
     answers 'want_kmeans_model' -> 'kmeans_model' (the KMeansModel of the fit that made the labels)."""
@@ -364,13 +406,22 @@ def _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, class
             if v is not None:
                 rules[k] = v
         rules["height"], rules["width"] = shape
-        return rule_based_classification(rules)
+        out = rule_based_classification(rules)
+        if valid_mask is not None and out is not None:
+            out = np.where(valid_mask != 0, out, 0).astype(out.dtype)
+        return out
     if method == "kmeans":
         keys = _kmeans_keys(feats, feature_keys, strict_reference)
         if extras is not None and extras.get("want_kmeans_model"):   # the same call on the same planes, its model kept
             from .kmeans_model import KMeansModel
-            extras["kmeans_model"], labels = KMeansModel.fit_features(feats, n_clusters, keys)
+            extras["kmeans_model"], labels = KMeansModel.fit_features(feats, n_clusters, keys, mask=valid_mask)
             return (labels + 1).astype(np.uint8)
+        if valid_mask is not None:   # labels -1 at the masked pixels: class 0
+            from modules.features.extract import _select_planes
+            from .masked import kmeans_fit_predict_masked
+            planes, _ = _select_planes(feats, keys)
+            labels, _ = kmeans_fit_predict_masked([np.asarray(p) for p in planes], valid_mask, int(n_clusters))
+            return (labels.reshape(shape) + 1).astype(np.uint8)
         return (unsupervised_kmeans_classification(feats, n_clusters, keys) + 1).astype(np.uint8)   # scripts/3:394
     if method in ("random_forest", "rf", "supervised"):
         arr, names = None, []
@@ -405,10 +456,17 @@ def _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, class
                 classifier = train_random_forest_classifier(X, y, feature_names_for_training=names)
                 joblib.dump(classifier, model_path)
                 print(f"随机森林模型训练并保存至: {model_path}")
-            out = supervised_classification_predict(arr, classifier)
+            if valid_mask is not None:
+                from .masked import forest_predict_masked
+                out = forest_predict_masked(classifier, arr, valid_mask, 0)
+            else:
+                out = supervised_classification_predict(arr, classifier)
             if extras is not None and extras.get("want_confidence"):   # the same pixels as the label map saw: NaN -> 0 (extract.py:690-719)
                 from .forest import image_proba_and_confidence
-                extras["proba"], extras["confidence"] = image_proba_and_confidence(classifier, np.nan_to_num(arr, nan=0.0))
+                if valid_mask is not None:
+                    extras["proba"], extras["confidence"] = image_proba_and_confidence(classifier, arr, mask=valid_mask)
+                else:
+                    extras["proba"], extras["confidence"] = image_proba_and_confidence(classifier, np.nan_to_num(arr, nan=0.0))
             if extras is not None and extras.get("importance_mask") is not None:
                 from .forest_importance import permutation_importance_image
                 extras["importance"] = permutation_importance_image(classifier, arr, extras["importance_mask"],
@@ -451,11 +509,39 @@ def run_scripts_2_3(image_path: str, output_dir: str, classify: Optional[str] = 
     return _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters, ctx, evaluate, raw, confidence, importance)
 
 
+MASK_NODATA_FROM_TAG = "tag"   # --mask-nodata without a value
+
+
+def resolve_mask_nodata(option, tag) -> Optional[float]:
+    """The nodata value --mask-nodata masks by: `option` is None (not asked for: None comes back), MASK_NODATA_FROM_TAG (the
+    file's GDAL_NODATA tag `tag`; SystemExit with a message when the file has none) or the value given on the command line."""
+    if option is None:
+        return None
+    if option != MASK_NODATA_FROM_TAG:
+        return float(option)
+    if tag is None:
+        raise SystemExit("--mask-nodata: the image carries no GDAL_NODATA tag; name the value: --mask-nodata VALUE")
+    return float(tag)
+
+
+def nodata_valid_mask(ctx: Context, arr: np.ndarray, nodata: float) -> Tuple[np.ndarray, int]:
+    """'Every band holds data' on the device (Context.valid_mask): pixel (y, x) of the (bands, H, W) raster is valid iff no band
+    equals `nodata` there (8-bit bands compared as bytes, every other dtype as the float32 the feature stage reads) or holds a
+    NaN.  Returns ((H, W) uint8 of 0 / 1, valid count)."""
+    dt = np.uint8 if arr.dtype == np.uint8 else np.float32
+    dev = [ctx.to_device(np.ascontiguousarray(arr[i], dtype=dt).reshape(-1)) for i in range(arr.shape[0])]
+    mask, n_valid = ctx.valid_mask(dev, nan=True, nodata=nodata)
+    return mask.cpu().numpy().reshape(arr.shape[1:]), n_valid
+
+
 def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters, ctx, evaluate, raw, confidence, importance,
-                     kmeans_model: Optional[str] = None, save_kmeans_model: Optional[str] = None) -> Dict[str, object]:
+                     kmeans_model: Optional[str] = None, save_kmeans_model: Optional[str] = None, mask_nodata=None) -> Dict[str, object]:
     """run_scripts_2_3, and with classify='kmeans' the two model options of the command line: `save_kmeans_model` fits as
     always and also writes the fitted model there (KMeansModel.save; the class map is the same file byte for byte),
-    `kmeans_model` applies a saved model and fits nothing (run_kmeans_model_stage)."""
+    `kmeans_model` applies a saved model and fits nothing (run_kmeans_model_stage).
+    mask_nodata (None, MASK_NODATA_FROM_TAG or a value; resolve_mask_nodata): the classifier sees only the pixels where every
+    band holds data; the mask is also written as <output_dir>/feature_outputs/valid_mask.npy and the class map is 0 elsewhere."""
+    valid_mask = None
     if raw:
         from .preprocess import run_preprocessing_stage
         pdir = os.path.join(output_dir, "preprocessed")
@@ -467,10 +553,17 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
         from .tiff import read_tiff, read_tiff_georef
         arr = read_tiff(image_path)
         geo = read_tiff_georef(image_path)
+        nodata = resolve_mask_nodata(mask_nodata, geo["nodata"])
+        if nodata is not None:
+            valid_mask, n_valid = nodata_valid_mask(ctx or default_context(), arr, nodata)
+            print(f"valid pixels: {n_valid} of {valid_mask.size} (nodata {nodata:g})")
         bands = []
         for i in range(arr.shape[0]):
             b = arr[i] if arr.dtype == np.uint8 and geo["nodata"] is None else arr[i].astype(np.float32)
-            if geo["nodata"] is not None:
+            # with a valid mask the mask carries the nodata meaning and the bands keep their values: a NaN in a band makes
+            # robust_normalize's percentiles NaN and PCA refuses the stack (scikit-learn's "Input X contains NaN"), so a scene
+            # with nodata pixels never reached the classifier
+            if geo["nodata"] is not None and valid_mask is None:
                 b[b == geo["nodata"]] = np.nan
             bands.append(b)
         h, w = arr.shape[1:]
@@ -481,7 +574,22 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
     res: Dict[str, object] = {"paths": paths, "shape": (h, w)}
     if raw:
         res["preprocessed"] = ppath
-    if classify:
+    if valid_mask is not None:
+        res["valid_mask_path"] = os.path.join(fdir, "valid_mask.npy")
+        np.save(res["valid_mask_path"], valid_mask)
+    if classify and valid_mask is not None:
+        sdir = os.path.join(output_dir, "segmentation_results")
+        if confidence and classify == "random_forest":
+            res["class_map"] = run_masked_classification_stage(paths["pkl"], classify, sdir, True, valid_mask=valid_mask, confidence=True, ctx=ctx)
+        elif kmeans_model and classify == "kmeans":
+            res["class_map"] = run_kmeans_model_stage(paths["pkl"], kmeans_model, sdir, ctx=ctx, valid_mask=valid_mask)
+        elif save_kmeans_model and classify == "kmeans":
+            res["class_map"] = _run_classification(paths["pkl"], classify, sdir, True, n_clusters, None, None, "labeled_roi.tif", False, ctx,
+                                                   False, save_kmeans_model=save_kmeans_model, valid_mask=valid_mask)
+        else:
+            res["class_map"] = run_masked_classification_stage(paths["pkl"], classify, sdir, True, valid_mask=valid_mask, n_clusters=n_clusters,
+                                                               ctx=ctx)
+    elif classify:
         sdir = os.path.join(output_dir, "segmentation_results")
         if importance and classify == "random_forest":
             from .evaluate import ClassificationEvaluator
@@ -496,6 +604,7 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
                                                    False, save_kmeans_model=save_kmeans_model)
         else:
             res["class_map"] = run_classification_stage(paths["pkl"], classify, sdir, True, n_clusters=n_clusters, ctx=ctx)
+    if classify:
         res["segmentation_dir"] = sdir
         if evaluate and res["class_map"] is not None:
             from .evaluate import ClassificationEvaluator
@@ -518,6 +627,10 @@ def parse_args(ap, argv=None):
         ap.error("--kmeans-model / --save-kmeans-model need --classify kmeans")
     if a.kmeans_model and a.save_kmeans_model:
         ap.error("--kmeans-model applies a saved model and fits nothing: it does not go with --save-kmeans-model")
+    if a.mask_nodata is not None and not a.classify:
+        ap.error("--mask-nodata needs --classify")
+    if a.mask_nodata is not None and (a.raw or a.importance):
+        ap.error("--mask-nodata does not go with --raw or --importance")
     return a
 
 
@@ -543,6 +656,13 @@ def build_parser():
     ap.add_argument("--kmeans-model", metavar="PATH",
                     help="with --classify kmeans: apply this saved model instead of fitting -> the class map with the model's cluster ids, "
                          "kmeans_distance.npy and kmeans_model_summary.json")
+    def nodata_value(s):   # argparse hands a string `const` to `type` as well
+        return s if s == MASK_NODATA_FROM_TAG else float(s)
+    nodata_value.__name__ = "float"   # the word argparse's "invalid ... value" message uses
+    ap.add_argument("--mask-nodata", nargs="?", type=nodata_value, const=MASK_NODATA_FROM_TAG, default=None, metavar="VALUE",
+                    help="with --classify: classify only the pixels where every band holds data (differs from VALUE; without VALUE, "
+                         "from the file's GDAL_NODATA tag); the class map is 0 elsewhere and the mask is written as "
+                         "feature_outputs/valid_mask.npy")
     return ap
 
 
@@ -550,7 +670,7 @@ def main(argv=None) -> int:
     ap = build_parser()
     a = parse_args(ap, argv)
     res = _run_scripts_2_3(a.image, a.output_dir, a.classify, not a.no_preprocessing, a.n_clusters, None, a.evaluate, a.raw, a.confidence,
-                           a.importance, a.kmeans_model, a.save_kmeans_model)
+                           a.importance, a.kmeans_model, a.save_kmeans_model, a.mask_nodata)
     if a.raw:
         print(f"preprocessed: {res['preprocessed']}")
     for k, v in res["paths"].items():
