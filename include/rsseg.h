@@ -545,6 +545,37 @@ int rsseg_remove_small_components_u8(rsseg_ctx *ctx, const uint8_t *d_mask, int 
  * Whole raster on one GPU. */
 int rsseg_fill_holes_u8(rsseg_ctx *ctx, const uint8_t *d_mask, int H, int W, uint8_t *d_out);
 
+/* ---- K20: clean-up of a class map (no counterpart in the reference) --------------------------- */
+/* A class map is a uint8 plane; every result below is an integer, so the kernels are exact by construction.
+ * counts (host, 256): how often every byte value occurs among the n bytes of d_q.  Profiler name "class_hist". */
+int rsseg_hist_u8(rsseg_ctx *ctx, const uint8_t *d_q, int64_t n, int64_t *counts);
+/* d_q[i] = to wherever d_q[i] == from, in place; n_replaced (may be NULL): how many.  from, to in 0 ... 255. */
+int rsseg_replace_u8(rsseg_ctx *ctx, uint8_t *d_q, int64_t n, int from, int to, int64_t *n_replaced);
+/* k x k majority (mode) filter, k odd in 3 ... 15.  The window is centred on the pixel and clipped to the image: cells
+ * outside do not vote.  ignore / fill: a value 0 ... 255 or -1 for none (equal values are refused).  `ignore` pixels never
+ * vote and are never changed; `fill` pixels never vote and take their window's winner when the window has a voter, else
+ * stay; with fill_only != 0 every pixel that is not `fill` keeps its value.  Winner: the label with the most votes; on a tie
+ * the centre's own label if it votes and is among the maxima, otherwise the smallest tied label.
+ * Rows form: d_q holds Hin rows, which are rows [img_y0, img_y0 + Hin) of an image of img_H rows; rows [y0, y1) of the
+ * plane are produced into the compact (y1 - y0) x W plane d_out (not d_q).  The window is clipped against the image's first
+ * and last row, so every image row it reaches must be in the plane (R = k / 2 halo rows on a side that is not an image
+ * edge), and a stripe gets exactly the rows of the un-sharded result.  The whole map: y0 = img_y0 = 0, y1 = Hin = img_H.
+ * group_mask: bit g set when a label in 8g ... 8g + 7 may occur (a superset is exact, only slower; the output's labels are
+ * among the input's, so one mask serves repeated passes); 0: taken from a histogram of the plane inside the call.
+ * n_changed: produced pixels whose output differs from their input; n_unfilled: produced `fill` pixels still `fill`.
+ * RSSEG_ERR_INVALID, naming the argument: null pointers, d_out == d_q, k, ignore, fill, rows outside the plane, a plane
+ * outside the image, a missing halo.  Synchronous (the counters are on the host).  Profiler name "majority". */
+int rsseg_majority_u8(rsseg_ctx *ctx, const uint8_t *d_q, int Hin, int W, int y0, int y1, int img_y0, int img_H, int k, int ignore, int fill,
+                      int fill_only, uint32_t group_mask, uint8_t *d_out, int64_t *n_changed, int64_t *n_unfilled);
+/* Multi-class sieve: pixels are connected when they are 8-neighbours (connectivity 8) or 4-neighbours (4), hold the same
+ * label and that label is not `ignore` (0 ... 255, or -1 for none); every component of fewer than min_area pixels is written
+ * as removed_value (0 ... 255), everything else is copied; min_area <= 1 is the identity.  n_removed: the pixels of the
+ * removed components.  One labelling pass for any number of classes (the union-find of rsseg_remove_small_components_u8).
+ * Whole raster on one GPU; H * W <= 2^31 - 1, else RSSEG_ERR_UNSUPPORTED.  RSSEG_ERR_INVALID, naming the argument: null
+ * pointers, d_out == d_q, connectivity, ignore, removed_value.  Synchronous.  Profiler name "sieve". */
+int rsseg_sieve_u8(rsseg_ctx *ctx, const uint8_t *d_q, int H, int W, int min_area, int connectivity, int ignore, int removed_value,
+                   uint8_t *d_out, int64_t *n_removed);
+
 /* ---- K13: remaining texture members of the feature dictionary ---------------- */
 /* calculate_lbp_features (indices.py:320-344): skimage.feature.local_binary_pattern(u8, n_points, radius, 'uniform');
  * d_out: the codes 0 .. n_points + 1 as uint8 (the caller divides by their maximum in float64, :342). */

@@ -17,6 +17,7 @@
 // min_area pixels.  The result depends on connectivity and areas only, so it equals scipy's label + bincount filter
 // whatever order the atomics land in.  binary_fill_holes is the same union-find on the BACKGROUND with 4-connectivity
 // (scipy's default structure): a hole is a background component that owns no pixel of the image border.
+#include "cc.h"       // cc_find, cc_union (shared with k20_postclass.hip)
 #include "common.h"
 
 #include <float.h>
@@ -167,30 +168,6 @@ __global__ __launch_bounds__(K12_THREADS) void k12_morph_any(const uint8_t *__re
 }
 
 // ---- connected components ----
-__device__ __forceinline__ int cc_find(const int *L, int i)
-{
-    int p = L[i];
-    while (p != i) { i = p; p = L[i]; }
-    return i;
-}
-__device__ __forceinline__ void cc_union(int *L, int a, int b)
-{
-    bool done;
-    do {
-        a = cc_find(L, a);
-        b = cc_find(L, b);
-        if (a < b) {
-            const int old = atomicMin(&L[b], a);
-            done = old == b;
-            b = old;
-        } else if (b < a) {
-            const int old = atomicMin(&L[a], b);
-            done = old == a;
-            a = old;
-        } else
-            done = true;
-    } while (!done);
-}
 __global__ __launch_bounds__(K12_THREADS) void k12_cc_init(const uint8_t *__restrict__ m, int64_t n, int *__restrict__ L, int *__restrict__ area)
 {
     for (int64_t i = (int64_t)blockIdx.x * K12_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * K12_THREADS) {

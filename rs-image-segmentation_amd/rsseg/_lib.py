@@ -159,6 +159,11 @@ SIGNATURES = {
     "rsseg_mask_paint_u8": (_int, [_vp, _vp, _vp, _i64, _int, _int]),
     "rsseg_morph_ellipse_u8": (_int, [_vp, _vp, _int, _int, _int, _int, _vp]),
     "rsseg_remove_small_components_u8": (_int, [_vp, _vp, _int, _int, _int, _vp]),
+    "rsseg_hist_u8": (_int, [_vp, _vp, _i64, C.POINTER(_i64)]),
+    "rsseg_replace_u8": (_int, [_vp, _vp, _i64, _int, _int, C.POINTER(_i64)]),
+    "rsseg_majority_u8": (_int, [_vp, _vp, _int, _int, _int, _int, _int, _int, _int, _int, _int, _int, C.c_uint32, _vp, C.POINTER(_i64),
+                                 C.POINTER(_i64)]),
+    "rsseg_sieve_u8": (_int, [_vp, _vp, _int, _int, _int, _int, _int, _int, _vp, C.POINTER(_i64)]),
     "rsseg_lbp_uniform_u8": (_int, [_vp, _vp, _int, _int, _int, C.c_double, _vp]),
     "rsseg_rank_entropy_u8": (_int, [_vp, _vp, _int, _int, _int, _vp]),
     "rsseg_gaussian_blur_u8": (_int, [_vp, _vp, _int, _int, _int, _vp]),

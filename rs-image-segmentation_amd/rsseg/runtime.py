@@ -730,6 +730,45 @@ class Context:
         self._chk(self.lib.rsseg_remove_small_components_u8(self.h, C.c_void_p(mask.data_ptr()), H, W, int(min_area), C.c_void_p(out.data_ptr())))
         return out
 
+    # ---- K20: class-map clean-up (rsseg/postclass.py) --------------------------------------------
+    def hist_u8(self, q) -> np.ndarray:
+        """How often every byte value occurs in a uint8 device plane: int64[256]."""
+        counts = np.zeros(256, np.int64)
+        self._chk(self.lib.rsseg_hist_u8(self.h, C.c_void_p(q.data_ptr()), q.numel(), counts.ctypes.data_as(C.POINTER(C.c_int64))))
+        return counts
+
+    def replace_u8(self, q, old: int, new: int) -> int:
+        """q[q == old] = new in place on a uint8 device plane; how many pixels that was."""
+        n = C.c_int64(0)
+        self._chk(self.lib.rsseg_replace_u8(self.h, C.c_void_p(q.data_ptr()), q.numel(), int(old), int(new), C.byref(n)))
+        return n.value
+
+    def majority_u8(self, q, H: int, W: int, k: int, ignore: int = -1, fill: int = -1, fill_only: bool = False, rows=None, image_rows=None,
+                    group_mask: int = 0, out=None):
+        """k x k majority filter of a uint8 class map (include/rsseg.h, rsseg_majority_u8): (out, n_changed, n_unfilled).
+        rows=(y0, y1): the plane holds H rows and rows [y0, y1) are produced (compact output); image_rows=(img_y0, img_H):
+        the plane is rows [img_y0, img_y0 + H) of an image img_H rows tall, against whose edges the window is clipped
+        (default: the plane is the image).  group_mask: bit g when a label in 8g .. 8g + 7 may occur; 0 = found in the call."""
+        torch = _torch()
+        y0, y1 = self._rows(H, rows)
+        img_y0, img_h = (0, H) if image_rows is None else (int(image_rows[0]), int(image_rows[1]))
+        if out is None:   # `out`: a uint8 plane of (y1 - y0) * W pixels to write instead (repeated passes ping-pong two buffers)
+            out = self.empty(max((y1 - y0) * W, 1), torch.uint8)[:max(y1 - y0, 0) * W]   # an empty stripe still hands the library a pointer
+        nc, nu = C.c_int64(0), C.c_int64(0)
+        self._chk(self.lib.rsseg_majority_u8(self.h, C.c_void_p(q.data_ptr()), H, W, y0, y1, img_y0, img_h, int(k), int(ignore), int(fill),
+                                             int(bool(fill_only)), int(group_mask), C.c_void_p(out.data_ptr()), C.byref(nc), C.byref(nu)))
+        return out, nc.value, nu.value
+
+    def sieve_u8(self, q, H: int, W: int, min_area: int, connectivity: int = 8, ignore: int = 0, removed_value: int = 0):
+        """Multi-class sieve (rsseg_sieve_u8): same-label components of fewer than min_area pixels become removed_value;
+        (out, n_removed).  Whole raster on one GPU."""
+        torch = _torch()
+        out = self.empty(H * W, torch.uint8)
+        nr = C.c_int64(0)
+        self._chk(self.lib.rsseg_sieve_u8(self.h, C.c_void_p(q.data_ptr()), H, W, int(min_area), int(connectivity), int(ignore), int(removed_value),
+                                          C.c_void_p(out.data_ptr()), C.byref(nr)))
+        return out, nr.value
+
     # ---- K9/K10 --------------------------------------------------------------------------------
     def kmeans_fit_predict(self, planes: Sequence, n_clusters: int, seed: int = 42, max_iter: int = 300, tol: float = 1e-4):
         torch = _torch()

@@ -534,8 +534,46 @@ def nodata_valid_mask(ctx: Context, arr: np.ndarray, nodata: float) -> Tuple[np.
     return mask.cpu().numpy().reshape(arr.shape[1:]), n_valid
 
 
+POSTCLASS_STATS_FILE = "postclass_stats.json"
+
+
+def run_postclass_stage(class_map, output_dir: str, method: str, min_area: int = 0, window: int = 0, majority_iterations: int = 1, *,
+                        nodata: int = 0, transform=None, crs=None, ctx: Optional[Context] = None) -> Tuple[np.ndarray, Dict[str, object]]:
+    """Clean-up of a finished class map (rsseg.postclass.clean_class_map; no counterpart in the reference): components of fewer
+    than min_area pixels are removed and grown over from their surroundings, then — window != 0 — majority_iterations passes of
+    a window x window majority filter run.  window = 0: no majority pass, the holes are filled with a 3 x 3 window.
+    Writes, beside the raw map's files that stay as they are: <output_dir>/classification_<method>_clean.npy,
+    <method>_classification_map_clean.tif (uint8, nodata 0, LZW tiles; georeferenced when transform and crs are given) and
+    postclass_stats.json (the parameters, clean_class_map's statistics, pixels per class before and after).
+    Returns (clean map, that dictionary)."""
+    import json
+    from . import postclass as PC
+    from .tiff import write_tiff
+    raw = PC.check_class_map(class_map)
+    if _is_device_tensor(raw):
+        raw = raw.cpu().numpy()
+    clean, st = PC.clean_class_map(raw, min_area=min_area, window=window or 3, nodata=nodata, majority_iterations=majority_iterations if window else 0,
+                                   ctx=ctx, return_stats=True)
+    os.makedirs(output_dir, exist_ok=True)
+    np.save(os.path.join(output_dir, f"classification_{method}_clean.npy"), clean)
+    write_tiff(os.path.join(output_dir, f"{method}_classification_map_clean.tif"), clean, transform=transform, epsg=_epsg_of(crs),
+               geographic=_is_geographic(crs), nodata=0, compress="lzw", tiled=True)
+    stats: Dict[str, object] = {"method": method, "min_area": int(min_area), "window": int(window or 3),
+                                "majority_iterations": int(majority_iterations if window else 0), "nodata": int(nodata), **st,
+                                "class_counts_before": {str(k): v for k, v in PC.class_counts(raw).items()},
+                                "class_counts_after": {str(k): v for k, v in PC.class_counts(clean).items()}}
+    with open(os.path.join(output_dir, POSTCLASS_STATS_FILE), "w") as f:
+        json.dump(stats, f, indent=1)
+    return clean, stats
+
+
+def _is_device_tensor(x) -> bool:
+    return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
+
+
 def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters, ctx, evaluate, raw, confidence, importance,
-                     kmeans_model: Optional[str] = None, save_kmeans_model: Optional[str] = None, mask_nodata=None) -> Dict[str, object]:
+                     kmeans_model: Optional[str] = None, save_kmeans_model: Optional[str] = None, mask_nodata=None, sieve: int = 0,
+                     majority: int = 0, majority_iterations: int = 1) -> Dict[str, object]:
     """run_scripts_2_3, and with classify='kmeans' the two model options of the command line: `save_kmeans_model` fits as
     always and also writes the fitted model there (KMeansModel.save; the class map is the same file byte for byte),
     `kmeans_model` applies a saved model and fits nothing (run_kmeans_model_stage).
@@ -612,6 +650,14 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
             edir = os.path.join(output_dir, "evaluation_results")
             res["metrics"], res["cluster_mapping"] = ev.evaluate_maps(res["class_map"], ev.load_roi_mask(evaluate), edir)
             res["evaluation_dir"] = edir
+        if (sieve or majority) and res["class_map"] is not None:
+            # sieve / majority: the cleaned map beside the raw one (whose files and evaluation stay byte for byte what they are)
+            res["class_map_clean"], res["postclass_stats"] = run_postclass_stage(res["class_map"], sdir, classify, sieve, majority, majority_iterations,
+                                                                                 transform=geo["transform"], crs=crs, ctx=ctx)
+            if evaluate:
+                cdir = os.path.join(output_dir, "evaluation_results_clean")
+                res["metrics_clean"], _ = ev.evaluate_maps(res["class_map_clean"], ev.load_roi_mask(evaluate), cdir)
+                res["evaluation_dir_clean"] = cdir
     return res
 
 
@@ -631,6 +677,14 @@ def parse_args(ap, argv=None):
         ap.error("--mask-nodata needs --classify")
     if a.mask_nodata is not None and (a.raw or a.importance):
         ap.error("--mask-nodata does not go with --raw or --importance")
+    if (a.sieve or a.majority) and not a.classify:
+        ap.error("--sieve / --majority need --classify")
+    if a.sieve < 0:
+        ap.error("--sieve takes a non-negative pixel count")
+    if a.majority and a.majority not in (3, 5, 7, 9, 11, 13, 15):
+        ap.error("--majority takes an odd window in 3..15")
+    if a.majority_iterations < 0:
+        ap.error("--majority-iterations takes a non-negative count")
     return a
 
 
@@ -663,6 +717,13 @@ def build_parser():
                     help="with --classify: classify only the pixels where every band holds data (differs from VALUE; without VALUE, "
                          "from the file's GDAL_NODATA tag); the class map is 0 elsewhere and the mask is written as "
                          "feature_outputs/valid_mask.npy")
+    ap.add_argument("--sieve", type=int, default=0, metavar="MIN_AREA",
+                    help="with --classify: also write a cleaned class map (classification_<method>_clean.npy, "
+                         "<method>_classification_map_clean.tif, postclass_stats.json): same-class components of fewer than MIN_AREA "
+                         "pixels are removed and grown over from their surroundings (rsseg.postclass)")
+    ap.add_argument("--majority", type=int, default=0, metavar="K",
+                    help="with --classify: K x K majority filter (K odd, 3..15) of the (sieved) class map, written as the cleaned map")
+    ap.add_argument("--majority-iterations", type=int, default=1, metavar="N", help="with --majority: up to N passes (stopped once one changes nothing)")
     return ap
 
 
@@ -670,7 +731,7 @@ def main(argv=None) -> int:
     ap = build_parser()
     a = parse_args(ap, argv)
     res = _run_scripts_2_3(a.image, a.output_dir, a.classify, not a.no_preprocessing, a.n_clusters, None, a.evaluate, a.raw, a.confidence,
-                           a.importance, a.kmeans_model, a.save_kmeans_model, a.mask_nodata)
+                           a.importance, a.kmeans_model, a.save_kmeans_model, a.mask_nodata, a.sieve, a.majority, a.majority_iterations)
     if a.raw:
         print(f"preprocessed: {res['preprocessed']}")
     for k, v in res["paths"].items():
@@ -681,6 +742,13 @@ def main(argv=None) -> int:
         if "metrics" in res:
             m = res["metrics"]
             print(f"evaluation: OA {m['overall_accuracy'] * 100:.2f}%, kappa {m['kappa_coefficient']:.4f} -> {res['evaluation_dir']}")
+        if "postclass_stats" in res:
+            s = res["postclass_stats"]
+            print(f"cleaned map: {s['removed']} pixels sieved out, {s['filled']} filled, {s['left_as_nodata']} left as nodata, "
+                  f"majority passes changed {s['changed']} -> {res['segmentation_dir']}")
+        if "metrics_clean" in res:
+            m = res["metrics_clean"]
+            print(f"evaluation of the cleaned map: OA {m['overall_accuracy'] * 100:.2f}%, kappa {m['kappa_coefficient']:.4f} -> {res['evaluation_dir_clean']}")
         return 0 if cm is not None else 1
     return 0
 
