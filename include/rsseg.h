@@ -1,6 +1,8 @@
 /*
  * rsseg.h — C ABI of librsseg_hip.so: MI355X (gfx950) kernels for the per-pixel
- * feature-extraction -> clustering / classification path of beilsme/rs-image-segmentation.
+ * feature-extraction -> clustering / classification path of beilsme/rs-image-segmentation, the stages around it
+ * (preprocessing, accuracy assessment, class-map clean-up) and, beyond the reference, the geometric correction from
+ * ground control points that its stage 1 only stubs (rsseg_warp_poly).
  *
  * The reference has no FFI: its boundary for this path is a set of NumPy-in / NumPy-out Python
  * functions.  Each entry point below names the reference function (file:line,
@@ -632,6 +634,28 @@ int rsseg_preprocess_u8(rsseg_ctx *ctx, const void *const *d_in, int in_dtype, i
  * output), or float32 for RSSEG_F32 input (float32 constants and operations, as NumPy 2 promotes).  in_dtype as above;
  * gain and bias finite. */
 int rsseg_radiometric(rsseg_ctx *ctx, const void *d_in, int in_dtype, int64_t n, double gain, double bias, void *d_out);
+
+/* ---- K21: geometric correction (beyond the reference, whose geometric_correction warps with the identity) -------- */
+#define RSSEG_WARP_NEAREST 0
+#define RSSEG_WARP_BILINEAR 1
+#define RSSEG_WARP_CUBIC 2   /* cubic convolution, Keys a = -0.5 */
+/* Polynomial resampling of n_planes (1 ... 16) source planes of H x W pixels and one dtype (RSSEG_U8, RSSEG_I16, RSSEG_U16,
+ * RSSEG_I32, RSSEG_F32, RSSEG_F64; anything else is RSSEG_ERR_INVALID, named) onto Ho x Wo planes of out_dtype (in_dtype,
+ * RSSEG_F32 or RSSEG_F64).  coef = {p0..p5, q0..q5}; per output pixel (r, c), in double and one IEEE operation per written
+ * operation:  X = (c + 0.5) - cx, Y = (r + 0.5) - cy,
+ *   u = ((((p0 + p1*X) + p2*Y) + p3*(X*X)) + p4*(X*Y)) + p5*(Y*Y), v likewise from q: the source position in pixel-corner
+ * coordinates (the first pixel's centre is (0.5, 0.5)).  The pixel is valid iff 0 <= u < W && 0 <= v < H (a NaN is not);
+ * an invalid pixel gets `fill` and mask 0.  A valid one samples at fx = u - 0.5, fy = v - 0.5 with edge-replicated taps:
+ * nearest (the tap floor(fy + 0.5), floor(fx + 0.5), bits preserved), bilinear (top = g00*(1-tx) + g01*tx, bot likewise,
+ * top*(1-ty) + bot*ty) or cubic convolution (rows i = -1..2 summed ascending from 0.0, then columns), in double; integer
+ * outputs are rint (half to even) and saturated, float32 is one cast.  tests/warp_ref.py restates it; results are bit-equal.
+ * d_mask: NULL, or Ho * Wo uint8 (1 = sampled, 0 = fill); n_valid: NULL, or the number of valid pixels (the one host wait).
+ * fill must be a value of an integer out_dtype (RSSEG_ERR_INVALID otherwise); coef, cx, cy finite; H, W, Ho, Wo >= 1 and
+ * H * W, Ho * Wo < 2^39 (RSSEG_ERR_UNSUPPORTED).  Whole planes on one GPU: RSSEG_ERR_UNSUPPORTED on a context with a
+ * communication path.  Planes aligned to their element.  Profiler name "warp". */
+int rsseg_warp_poly(rsseg_ctx *ctx, const void *const *d_in, int in_dtype, int n_planes, int H, int W, const double *coef, double cx,
+                    double cy, int method, double fill, void *const *d_out, int out_dtype, int Ho, int Wo, uint8_t *d_mask,
+                    int64_t *n_valid);
 
 /* ---- host-only helper (no GPU needed) ------------------------------------------------------- */
 /* The random draws of k-means++ as the library makes them (numpy RandomState(seed): MT19937, random_sample,

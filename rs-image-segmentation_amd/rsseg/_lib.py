@@ -21,6 +21,8 @@ BORDER_REFLECT, BORDER_REFLECT101 = 0, 1
 MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE, MORPH_GRADIENT = 0, 1, 2, 3, 4
 MASK_AND, MASK_OR, MASK_ANDNOT, MASK_NOT = 0, 1, 2, 3
 VALID_NAN, VALID_INF, VALID_VALUE = 1, 2, 4   # rsseg_valid_mask's flags
+WARP_NEAREST, WARP_BILINEAR, WARP_CUBIC = 0, 1, 2
+WARP_MAX_BANDS = 16
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int)
 
@@ -172,6 +174,8 @@ SIGNATURES = {
     "rsseg_preprocess_u8": (_int, [_vp, _PP, _int, _int, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), _PP,
                                    C.POINTER(C.c_double)]),
     "rsseg_radiometric": (_int, [_vp, _vp, _int, _i64, C.c_double, C.c_double, _vp]),
+    "rsseg_warp_poly": (_int, [_vp, _PP, _int, _int, _int, _int, C.POINTER(C.c_double), C.c_double, C.c_double, _int, C.c_double, _PP, _int,
+                               _int, _int, _vp, C.POINTER(_i64)]),
     "rsseg_host_gaussian_kernel_fixed": (_int, [_int, C.POINTER(_int)]),
     "rsseg_host_lzw_encode": (_i64, [_vp, _i64, _vp, _i64]),
     "rsseg_host_lzw_decode": (_i64, [_vp, _i64, _vp, _i64]),

@@ -9,6 +9,11 @@ uint8 values with the input's georeferencing.  The figures of scripts/1 are out 
 created and nothing is drawn.
 
     python -m rsseg.preprocess RAW.tif OUT.tif [--viz-dir DIR]
+
+Beyond the reference (whose geometric_correction ignores its GCPs): with --gcps FILE the DN planes are first rectified on the
+device by the polynomial fitted to the ground control points (rsseg/georect.py, K21) and then go through K15 unchanged.
+
+    python -m rsseg.preprocess RAW.tif OUT.tif --gcps FILE [--warp-order 1|2] [--resampling nearest|bilinear|cubic] [--pixel-size S]
 """
 from __future__ import annotations
 
@@ -156,9 +161,39 @@ def write_processed_tif(path: str, bands_u8: Sequence[np.ndarray], transform=Non
     return path
 
 
-def run_preprocessing_stage(input_file, output_file, visualization_output_dir, ctx: Optional[Context] = None, return_device: bool = False):
+def warp_dn_planes(ctx: Optional[Context], dn_planes: Sequence, src_shape, gcps, warp_order: int = 1, resampling: str = "nearest",
+                   pixel_size: Optional[float] = None):
+    """The DN planes rectified on the device by the transform fitted to `gcps` (a path, the text of a GCP file, or an (N, 4)
+    array): (device planes, mask, n_valid, transform, plan).  nearest keeps the DN dtype; bilinear and cubic write float64
+    for integer DN (K15 then computes the radiance in float64, as it does for integer DN) and float DN keep their dtype.
+    Pixels outside the source are 0 DN."""
+    from . import georect as G
+    g = G.parse_gcps(gcps) if isinstance(gcps, (str, os.PathLike)) else np.asarray(gcps, np.float64)
+    t = G.fit_gcp_transform(g, warp_order)
+    ho, wo, out_transform = G.output_grid(t, src_shape, pixel_size)
+    plan = G.warp_plan(t, (ho, wo), out_transform, src_shape)
+    planes = list(dn_planes)
+    dt = check_dn_dtype(str(planes[0].dtype).split(".")[-1])
+    out_dtype = np.float64 if resampling != "nearest" and dt.kind in "iu" else None
+    outs, mask, n_valid = G.warp_planes(ctx, planes, src_shape, plan, method=resampling, fill=0, out_dtype=out_dtype)
+    return outs, mask, n_valid, t, plan
+
+
+def run_preprocessing_stage(input_file, output_file, visualization_output_dir, ctx: Optional[Context] = None, return_device: bool = False,
+                            gcps=None, warp_order: int = 1, resampling: str = "nearest", pixel_size: Optional[float] = None,
+                            nodata: Optional[float] = None):
     """scripts/1_preprocessing.py:25-85: raw DN GeoTIFF -> calibrated, stretched, Float32 GeoTIFF; returns output_file.
-    return_device: (output_file, uint8 device planes, (H, W), georef) instead, for a caller that goes on on the device."""
+    return_device: (output_file, uint8 device planes, (H, W), georef) instead, for a caller that goes on on the device.
+
+    gcps (beyond the reference; a GCP file, its text or an (N, 4) array of pixel, line, x, y): the DN planes are rectified
+    first (warp_dn_planes) and then calibrated and stretched as they are.  Calibration is linear per band, so this is the
+    reference's calibrate -> warp -> stretch up to rounding, and exactly that for `nearest`.  The pixels outside the source
+    are 0 DN and take part in the stretch, as the constant border of cv2.warpAffine would.  The output carries the
+    rectified grid's transform; OUT_valid.npy (the uint8 mask, 1 = sampled) and OUT_geometric_correction.json (order, method,
+    coefficients, per-GCP residuals, RMSE, output shape and transform, n_valid) are written beside it, and return_device
+    gives (output_file, planes, (Ho, Wo), georef, mask) with georef["transform"] the new one.  nodata (with gcps and
+    return_device): the returned mask is also 0 where a warped DN band equals `nodata` or holds a NaN (Context.valid_mask
+    with the warp's mask as and_mask; 16- and 32-bit integer DN are compared as float32); the file keeps the warp's mask."""
     from .tiff import read_tiff, read_tiff_georef
     print("开始数据预处理阶段...")
     print(f"输入文件: {input_file}")
@@ -168,13 +203,42 @@ def run_preprocessing_stage(input_file, output_file, visualization_output_dir, c
     arr = read_tiff(input_file)
     geo = read_tiff_georef(input_file)
     h, w = arr.shape[1:]
-    planes = preprocess_to_device(ctx, [arr[i] for i in range(arr.shape[0])])
+    dn = [arr[i] for i in range(arr.shape[0])]
+    mask = None
+    if gcps is not None:
+        import json
+        from .georect import correction_record
+        if len(dn) > len(GAIN):
+            raise IndexError("list index out of range")   # gain[7], before any work
+        dn, mask, n_valid, t, plan = warp_dn_planes(ctx, dn, (h, w), gcps, warp_order, resampling, pixel_size)
+        h, w = plan.out_shape
+        geo = dict(geo, transform=tuple(plan.out_transform))
+        stem = os.path.splitext(output_file)[0]
+        np.save(stem + "_valid.npy", mask.cpu().numpy().reshape(h, w))
+        with open(stem + "_geometric_correction.json", "w", encoding="utf-8") as f:
+            json.dump(correction_record(t, plan, resampling, n_valid), f, indent=1)
+        if nodata is not None and return_device:
+            torch = __import__("torch")
+            c = ctx or default_context()
+            cmp = [p if p.dtype in (torch.uint8, torch.float32, torch.float64) else p.to(torch.float32) for p in dn]
+            mask, _ = c.valid_mask(cmp, nan=True, nodata=nodata, and_mask=mask)
+        print(f"几何校正: order {t.order}, {resampling}, RMSE {t.rmse:.4f} px, {h} x {w}, {n_valid} valid pixels")
+    planes = preprocess_to_device(ctx, dn)
     write_processed_tif(output_file, [p.cpu().numpy().reshape(h, w) for p in planes], geo["transform"], geo["epsg"])
     print(f"已保存处理后的影像到: {output_file}")
     print("数据预处理阶段完成")
     if return_device:
-        return output_file, planes, (h, w), geo
+        return (output_file, planes, (h, w), geo) + (() if mask is None else (mask,))
     return output_file
+
+
+def add_gcp_arguments(ap) -> None:
+    """The geometric-correction options shared by `python -m rsseg.preprocess` and `python -m rsseg.stages --raw`."""
+    ap.add_argument("--gcps", default=None, metavar="FILE", help="ground control points, one `pixel line x y` per line: rectify the DN "
+                    "planes on the GPU before calibration (beyond the reference, which ignores its GCPs)")
+    ap.add_argument("--warp-order", type=int, choices=(1, 2), default=1, help="polynomial order of the GCP transform (default 1)")
+    ap.add_argument("--resampling", choices=("nearest", "bilinear", "cubic"), default="nearest", help="interpolator of the warp (default nearest)")
+    ap.add_argument("--pixel-size", type=float, default=None, help="output pixel size in map units (default: from the transform)")
 
 
 def main(argv=None) -> int:
@@ -184,9 +248,11 @@ def main(argv=None) -> int:
     ap.add_argument("input_file")
     ap.add_argument("output_file")
     ap.add_argument("--viz-dir", default=None, help="visualisation directory (created; nothing is drawn). Default: next to OUT")
+    add_gcp_arguments(ap)
     a = ap.parse_args(argv)
     viz = a.viz_dir or (os.path.dirname(a.output_file) or ".")
-    run_preprocessing_stage(a.input_file, a.output_file, viz)
+    run_preprocessing_stage(a.input_file, a.output_file, viz, gcps=a.gcps, warp_order=a.warp_order, resampling=a.resampling,
+                            pixel_size=a.pixel_size)
     return 0
 
 

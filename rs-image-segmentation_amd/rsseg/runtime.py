@@ -1136,6 +1136,51 @@ class Context:
                                              C.c_void_p(out.data_ptr())))
         return out
 
+    # ---- K21 -----------------------------------------------------------------------------------
+    WARP_METHODS = {"nearest": L.WARP_NEAREST, "bilinear": L.WARP_BILINEAR, "cubic": L.WARP_CUBIC}
+
+    def warp_poly(self, planes: Sequence, H: int, W: int, coef, cx: float, cy: float, Ho: int, Wo: int, method: str = "nearest",
+                  fill=0, out_dtype=None, want_mask: bool = True, out: Optional[Sequence] = None):
+        """rsseg_warp_poly: the H x W device planes (one dtype out of K15's six, at most 16) resampled onto Ho x Wo planes
+        at the source positions the two polynomials coef = (p0..p5, q0..q5) give (include/rsseg.h).  method: 'nearest',
+        'bilinear' or 'cubic'; out_dtype: None (the planes' dtype), torch.float32 or torch.float64; fill: the value of
+        the pixels that fall outside the source (it must be a value of an integer output dtype).  Returns
+        (flat output planes, uint8 validity mask or None, n_valid).  `out`: planes to write instead of new ones."""
+        torch = _torch()
+        planes = list(planes)
+        if not planes:
+            raise ValueError("warp_poly: planes is empty")
+        if len(planes) > L.WARP_MAX_BANDS:
+            raise ValueError(f"warp_poly: planes holds {len(planes)} planes, at most {L.WARP_MAX_BANDS} are taken in one call")
+        code = self._dn_code(planes[0], "warp_poly: planes")
+        H, W, Ho, Wo = int(H), int(W), int(Ho), int(Wo)
+        if any(p.dtype != planes[0].dtype or p.numel() != H * W for p in planes):
+            raise ValueError(f"warp_poly: planes must share one dtype and hold H * W = {H} * {W} = {H * W} pixels each")
+        if method not in self.WARP_METHODS:
+            raise ValueError(f"warp_poly: method {method!r} is not one of 'nearest', 'bilinear', 'cubic'")
+        odt = planes[0].dtype if out_dtype is None else out_dtype
+        if odt != planes[0].dtype and odt not in (torch.float32, torch.float64):
+            raise ValueError(f"warp_poly: out_dtype {odt} is neither the planes' dtype nor float32 / float64")
+        ocode = code if odt == planes[0].dtype else (L.F32 if odt == torch.float32 else L.F64)
+        c = np.ascontiguousarray(np.asarray(coef, np.float64).reshape(-1))
+        if c.size != 12:
+            raise ValueError(f"warp_poly: coef must hold 12 values (p0..p5, q0..q5), not {c.size}")
+        ins = [p.reshape(-1) if p.is_contiguous() else p.contiguous().reshape(-1) for p in planes]
+        n_out = Ho * Wo
+        if Ho < 1 or Wo < 1:
+            raise ValueError(f"warp_poly: Ho = {Ho}, Wo = {Wo}: both must be at least 1")
+        outs = list(out) if out is not None else [self.empty(n_out, odt) for _ in ins]
+        if len(outs) != len(ins) or any(o.dtype != odt or o.numel() != n_out or not o.is_contiguous() for o in outs):
+            raise ValueError(f"warp_poly: out must hold one contiguous {odt} plane of Ho * Wo = {n_out} values per input plane")
+        mask = self.empty(n_out, torch.uint8) if want_mask else None
+        if self._needs_keep():
+            self._keep.extend(ins)
+        nv = C.c_int64(0)
+        self._chk(self.lib.rsseg_warp_poly(self.h, self._pp(ins), code, len(ins), H, W, c.ctypes.data_as(C.POINTER(C.c_double)), float(cx),
+                                           float(cy), self.WARP_METHODS[method], float(fill), self._pp(outs), ocode, Ho, Wo,
+                                           None if mask is None else C.c_void_p(mask.data_ptr()), C.byref(nv)))
+        return outs, mask, int(nv.value)
+
 
 _default_ctx: Optional[Context] = None
 

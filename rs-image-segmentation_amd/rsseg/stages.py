@@ -573,19 +573,38 @@ def _is_device_tensor(x) -> bool:
 
 def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters, ctx, evaluate, raw, confidence, importance,
                      kmeans_model: Optional[str] = None, save_kmeans_model: Optional[str] = None, mask_nodata=None, sieve: int = 0,
-                     majority: int = 0, majority_iterations: int = 1) -> Dict[str, object]:
+                     majority: int = 0, majority_iterations: int = 1, gcps=None, warp_order: int = 1, resampling: str = "nearest",
+                     pixel_size: Optional[float] = None) -> Dict[str, object]:
     """run_scripts_2_3, and with classify='kmeans' the two model options of the command line: `save_kmeans_model` fits as
     always and also writes the fitted model there (KMeansModel.save; the class map is the same file byte for byte),
     `kmeans_model` applies a saved model and fits nothing (run_kmeans_model_stage).
     mask_nodata (None, MASK_NODATA_FROM_TAG or a value; resolve_mask_nodata): the classifier sees only the pixels where every
-    band holds data; the mask is also written as <output_dir>/feature_outputs/valid_mask.npy and the class map is 0 elsewhere."""
+    band holds data; the mask is also written as <output_dir>/feature_outputs/valid_mask.npy and the class map is 0 elsewhere.
+    gcps (with raw; beyond the reference): stage 1 rectifies the DN planes first (rsseg.georect, K21) and the feature stage goes
+    on from the warped planes with the new shape and georeferencing.  With mask_nodata the warp's validity mask is AND-ed into
+    the nodata mask of the warped DN planes (a bare --mask-nodata on a file without a GDAL_NODATA tag masks by the warp alone);
+    without it the collar outside the source is classified as data, as it would be after a cv2.warpAffine."""
     valid_mask = None
     if raw:
         from .preprocess import run_preprocessing_stage
         pdir = os.path.join(output_dir, "preprocessed")
         stem = os.path.splitext(os.path.basename(image_path))[0]
-        ppath, dev, (h, w), geo = run_preprocessing_stage(image_path, os.path.join(pdir, f"{stem}_preprocessed.tif"), pdir, ctx=ctx,
-                                                          return_device=True)
+        ppath = os.path.join(pdir, f"{stem}_preprocessed.tif")
+        if gcps is None:
+            ppath, dev, (h, w), geo = run_preprocessing_stage(image_path, ppath, pdir, ctx=ctx, return_device=True)
+        else:
+            nodata = None
+            if mask_nodata is not None:
+                from .tiff import read_tiff_georef
+                tag = read_tiff_georef(image_path)["nodata"]
+                nodata = None if mask_nodata == MASK_NODATA_FROM_TAG and tag is None else resolve_mask_nodata(mask_nodata, tag)
+            ppath, dev, (h, w), geo, wmask = run_preprocessing_stage(image_path, ppath, pdir, ctx=ctx, return_device=True, gcps=gcps,
+                                                                     warp_order=warp_order, resampling=resampling, pixel_size=pixel_size,
+                                                                     nodata=nodata)
+            if mask_nodata is not None:
+                valid_mask = wmask.cpu().numpy().reshape(h, w)
+                print(f"valid pixels: {int(valid_mask.sum())} of {valid_mask.size} (warp mask"
+                      + ("" if nodata is None else f" and nodata {nodata:g}") + ")")
         fd, hier = _feature_extraction_on_device(ctx or default_context(), dev, h, w, preprocessing)
     else:
         from .tiff import read_tiff, read_tiff_georef
@@ -675,7 +694,9 @@ def parse_args(ap, argv=None):
         ap.error("--kmeans-model applies a saved model and fits nothing: it does not go with --save-kmeans-model")
     if a.mask_nodata is not None and not a.classify:
         ap.error("--mask-nodata needs --classify")
-    if a.mask_nodata is not None and (a.raw or a.importance):
+    if a.gcps and not a.raw:
+        ap.error("--gcps needs --raw: the ground control points rectify the raw DN raster in stage 1")
+    if a.mask_nodata is not None and ((a.raw and not a.gcps) or a.importance):
         ap.error("--mask-nodata does not go with --raw or --importance")
     if (a.sieve or a.majority) and not a.classify:
         ap.error("--sieve / --majority need --classify")
@@ -724,6 +745,8 @@ def build_parser():
     ap.add_argument("--majority", type=int, default=0, metavar="K",
                     help="with --classify: K x K majority filter (K odd, 3..15) of the (sieved) class map, written as the cleaned map")
     ap.add_argument("--majority-iterations", type=int, default=1, metavar="N", help="with --majority: up to N passes (stopped once one changes nothing)")
+    from .preprocess import add_gcp_arguments
+    add_gcp_arguments(ap)   # with --raw
     return ap
 
 
@@ -731,7 +754,8 @@ def main(argv=None) -> int:
     ap = build_parser()
     a = parse_args(ap, argv)
     res = _run_scripts_2_3(a.image, a.output_dir, a.classify, not a.no_preprocessing, a.n_clusters, None, a.evaluate, a.raw, a.confidence,
-                           a.importance, a.kmeans_model, a.save_kmeans_model, a.mask_nodata, a.sieve, a.majority, a.majority_iterations)
+                           a.importance, a.kmeans_model, a.save_kmeans_model, a.mask_nodata, a.sieve, a.majority, a.majority_iterations,
+                           gcps=a.gcps, warp_order=a.warp_order, resampling=a.resampling, pixel_size=a.pixel_size)
     if a.raw:
         print(f"preprocessed: {res['preprocessed']}")
     for k, v in res["paths"].items():
