@@ -410,6 +410,26 @@ int rsseg_compact_planes(rsseg_ctx *ctx, const uint8_t *d_mask, const int64_t *d
 int rsseg_expand_plane(rsseg_ctx *ctx, const uint8_t *d_mask, const int64_t *d_tile_off, int64_t n, const void *d_in, int elem_bytes,
                        const void *fill /* host, elem_bytes */, void *d_out);
 
+/* ---- K22: Gaussian maximum-likelihood / Mahalanobis / minimum-distance classification ------------ */
+/* One per-pixel sweep over F feature planes (RSSEG_F32 or RSSEG_F64, band-planar) for a model of k classes, all host arrays:
+ * mean[k][F]; whiten[k][F (F + 1) / 2], the rows of a lower-triangular W_j packed row-major; offset[k]; class_values[k],
+ * distinct and 1..255 (0 is the label of an unclassified pixel); max_dist2 (+inf: no threshold).
+ * Per pixel, in float64, j ascending: x_f = the plane value (a NaN reads as 0); d_f = x_f - mean[j][f]; z_i = the fma chain
+ * over f = 0..i of W_j[i][f] * d_f from +0; m_j = the fma chain over i of z_i * z_i from +0; g_j = m_j + offset[j]; the
+ * strictly smallest g_j wins (ties to the lowest j, a NaN g_j never wins) and the second smallest is the runner-up.
+ *   d_labels  class_values[winner], or 0 when no class won or m_winner > max_dist2
+ *   d_dist2   NULL or float32(m_winner), NaN when no class won (written whether or not the threshold zeroed the label)
+ *   d_margin  NULL or float32(second - best), NaN when no class won, +inf when k == 1
+ * The kernel equals tests/gaussian_ref.py bit for bit.  Limits: 1 <= F <= 64 and 1 <= k <= 64, beyond them
+ * RSSEG_ERR_UNSUPPORTED.  RSSEG_ERR_INVALID, naming the argument: a null or misaligned plane or output, a non-finite mean,
+ * whiten or offset, a class value of 0 or one that occurs twice, a NaN max_dist2.  n == 0 returns RSSEG_OK and touches
+ * nothing.  Planes and outputs may have any alignment that holds their element (16-byte loads where every plane is 16-byte
+ * aligned and F <= 32).  Synchronous.  Profiler name "gauss_classify". */
+int rsseg_gauss_classify(rsseg_ctx *ctx, const void *const *d_planes, int F, int dtype /* RSSEG_F32 | RSSEG_F64 */, int64_t n, int k,
+                         const double *mean, const double *whiten, const double *offset, /* host */
+                         const uint8_t *class_values, double max_dist2,
+                         uint8_t *d_labels, float *d_dist2 /* or NULL */, float *d_margin /* or NULL */);
+
 /* ---- K11: random-forest inference ---------------------------------------------------------- */
 /* Flattened sklearn forest (tree_ arrays concatenated; children are tree-local, -1 = leaf).
  * value: (n_nodes_total x n_classes) float64 class fractions.  The forest is copied to the device

@@ -129,6 +129,8 @@ SIGNATURES = {
                                            C.POINTER(C.c_double), C.POINTER(KMeansInfo), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rsseg_kmeans_predict": (_int, [_vp, _PP, _int, _int, _i64, _int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _vp, _vp,
                                     C.POINTER(KMeansApplyInfo)]),
+    "rsseg_gauss_classify": (_int, [_vp, _PP, _int, _int, _i64, _int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_uint8), C.c_double, _vp, _vp, _vp]),
     "rsseg_valid_mask": (_int, [_vp, _PP, _int, _int, _i64, _int, C.c_double, _vp, _vp, C.POINTER(_i64)]),
     "rsseg_compact_tile": (_int, []),
     "rsseg_compact_scan_span": (_int, []),

@@ -898,6 +898,41 @@ class Context:
                                               plan.n, C.c_void_p(plane.data_ptr()) if plan.n_valid else None, eb, fb, C.c_void_p(out.data_ptr())))
         return out[:plan.n]
 
+    # ---- K22: Gaussian maximum-likelihood / Mahalanobis / minimum-distance classification ---------
+    def gauss_classify(self, planes: Sequence, mean, whiten, offset, class_values, max_dist2=float("inf"), want_dist2: bool = False,
+                       want_margin: bool = False):
+        """rsseg_gauss_classify (include/rsseg.h) on flat float32 / float64 device planes: (labels uint8, dist2 float32 or None,
+        margin float32 or None).  mean (k, F), whiten (k, F (F + 1) / 2) the packed rows of the lower-triangular whitening
+        matrices, offset (k,), class_values (k,) distinct in 1..255; max_dist2=inf: no threshold."""
+        torch = _torch()
+        F = len(planes)
+        if F == 0:
+            raise ValueError("gauss_classify: no feature planes")
+        dt, n = planes[0].dtype, planes[0].numel()
+        if any(p.dtype != dt or p.numel() != n for p in planes) or dt not in (torch.float32, torch.float64):
+            raise ValueError("gauss_classify: planes must all be float32 or all float64, of one length")
+        mean = np.ascontiguousarray(mean, dtype=np.float64)
+        offset = np.ascontiguousarray(offset, dtype=np.float64).reshape(-1)
+        k = offset.size
+        whiten = np.ascontiguousarray(whiten, dtype=np.float64).reshape(k, -1) if k else np.zeros((0, 0))
+        cv = np.asarray(class_values).reshape(-1)
+        if mean.ndim != 2 or mean.shape != (k, F) or whiten.shape != (k, F * (F + 1) // 2) or cv.size != k:
+            raise ValueError(f"gauss_classify: the model's shapes (mean {mean.shape}, whiten {whiten.shape}, offset {offset.shape}, "
+                             f"class_values {cv.shape}) do not describe k classes over the call's {F} planes")
+        if np.any(cv != cv.astype(np.uint8)):
+            raise ValueError("gauss_classify: class_values must be integers in 1..255")
+        cv = np.ascontiguousarray(cv, dtype=np.uint8)
+        labels = self.empty(max(n, 1), torch.uint8)
+        dist2 = self.empty(max(n, 1), torch.float32) if want_dist2 else None
+        margin = self.empty(max(n, 1), torch.float32) if want_margin else None
+        dp = C.POINTER(C.c_double)
+        self._chk(self.lib.rsseg_gauss_classify(self.h, self._pp(planes), F, L.F32 if dt == torch.float32 else L.F64, n, k,
+                                                mean.ctypes.data_as(dp), whiten.ctypes.data_as(dp), offset.ctypes.data_as(dp),
+                                                cv.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_double(float(max_dist2)),
+                                                C.c_void_p(labels.data_ptr()), C.c_void_p(dist2.data_ptr()) if want_dist2 else None,
+                                                C.c_void_p(margin.data_ptr()) if want_margin else None))
+        return labels[:n], (dist2[:n] if want_dist2 else None), (margin[:n] if want_margin else None)
+
     # ---- K11 -----------------------------------------------------------------------------------
     def forest_load(self, forest: dict):
         f = forest

@@ -155,6 +155,7 @@ def _check_valid_mask(valid_mask, shape):
 
 
 RF_MODEL_FILE = "random_forest_model.joblib"   # scripts/3_classification.py:459
+GAUSS_METHODS = ("maximum_likelihood", "mahalanobis", "minimum_distance")   # rsseg.gaussian.STAGE_METHODS
 
 
 def run_classification_stage(feature_file_path, method='rule_based', output_dir="segmentation_outputs", use_hierarchical_all=True, *,
@@ -181,6 +182,9 @@ def run_classification_stage(feature_file_path, method='rule_based', output_dir=
                        `labeled_roi_file` (prepare_training_samples + train_random_forest_classifier, :450-475: K16 on the GPU,
                        the same trees scikit-learn grows) and cached as that joblib file.  Without a model and without the label raster the stage
                        reports that and returns None (the reference insists on the label raster even when the cache exists, :405-409).
+      'maximum_likelihood', 'mahalanobis', 'minimum_distance'   (beyond the reference) rsseg.gaussian.GaussianClassifier, K22:
+                       trained from `labeled_roi_file` on the feature array the forest branch takes, applied to every pixel
+                       on the GPU; also writes <output_dir>/<method>_model.npz (GaussianClassifier.save).
 
     Writes <output_dir>/classification_<method>.npy and, when the feature file carries transform / crs / width / height
     (scripts/3:495-498), <output_dir>/<method>_classification_map.tif (uint8 labels, nodata 0, LZW tiles); the PNG of
@@ -336,7 +340,7 @@ def _load_normalised(feature_file_path, output_dir):
 
 def _run_classification(feature_file_path, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys,
                         labeled_roi_file, strict_reference, ctx, confidence, importance_mask=None,
-                        save_kmeans_model=None, valid_mask=None) -> Optional[np.ndarray]:
+                        save_kmeans_model=None, valid_mask=None, ml_threshold=None, rule_image=False) -> Optional[np.ndarray]:
     feats = _load_normalised(feature_file_path, output_dir)
     if feats is None:
         return None
@@ -352,6 +356,8 @@ def _run_classification(feature_file_path, method, output_dir, use_hierarchical_
             extras = {"want_confidence": bool(confidence), "importance_mask": importance_mask}
         if save_kmeans_model and method == "kmeans":
             extras = {"want_kmeans_model": True}
+        if method in GAUSS_METHODS:
+            extras = {"ml_threshold": ml_threshold, "want_rule_image": bool(rule_image)}
         out = _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys, labeled_roi_file,
                         strict_reference, extras, valid_mask)
     finally:
@@ -369,6 +375,11 @@ def _run_classification(feature_file_path, method, output_dir, use_hierarchical_
             from .tiff import write_tiff
             write_tiff(os.path.join(output_dir, f"{method}_confidence_map.tif"), extras["confidence"], transform=feats["transform"],
                        epsg=_epsg_of(feats["crs"]), geographic=_is_geographic(feats["crs"]), compress="lzw", tiled=True)
+    if extras and "gauss_model" in extras:
+        print(f"{method} 模型保存至: {extras['gauss_model'].save(os.path.join(output_dir, f'{method}_model.npz'))}")
+    if extras and "dist2" in extras:
+        np.save(os.path.join(output_dir, f"{method}_dist2.npy"), extras["dist2"])
+        np.save(os.path.join(output_dir, f"{method}_margin.npy"), extras["margin"])
     if extras and "importance" in extras:
         _save_importance(os.path.join(output_dir, IMPORTANCE_FILE), extras["importance"], extras["feature_names"])
     return out
@@ -423,21 +434,27 @@ def _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, class
             labels, _ = kmeans_fit_predict_masked([np.asarray(p) for p in planes], valid_mask, int(n_clusters))
             return (labels.reshape(shape) + 1).astype(np.uint8)
         return (unsupervised_kmeans_classification(feats, n_clusters, keys) + 1).astype(np.uint8)   # scripts/3:394
+    if method in GAUSS_METHODS:
+        arr, names = _supervised_feature_array(feats, use_hierarchical_all, shape)
+        if arr is None:
+            return None
+        if not os.path.exists(labeled_roi_file):
+            print(f"错误: 监督分类所需的标签ROI文件 '{labeled_roi_file}' 未找到。")
+            return None
+        from .gaussian import STAGE_METHODS, GaussianClassifier
+        extras = {} if extras is None else extras
+        X, y = prepare_training_samples(arr, labeled_roi_file)
+        clf = GaussianClassifier(STAGE_METHODS[method], threshold=extras.get("ml_threshold")).fit(X, y)
+        rule = bool(extras.get("want_rule_image"))
+        res = clf.predict_image(arr, mask=valid_mask, want_dist2=rule, want_margin=rule)
+        extras["gauss_model"] = clf
+        if rule:
+            res, extras["dist2"], extras["margin"] = res
+        return res
     if method in ("random_forest", "rf", "supervised"):
-        arr, names = None, []
-        if use_hierarchical_all:
-            for key in ("hierarchical_all", "hierarchical_features_all"):
-                v = feats.get(key)
-                if isinstance(v, np.ndarray) and v.ndim == 3 and v.shape[:2] == shape:
-                    arr = v
-                    names = [f"hierarchical_feature_{i + 1}" for i in range(v.shape[-1])]
-                    break
-        if arr is None:   # scripts/3:425-437: every 2-D plane of the image's shape, in dict order
-            names = [k for k, v in feats.items() if isinstance(v, np.ndarray) and v.ndim == 2 and v.shape == shape]
-            if not names:
-                print("错误: 为随机森林指定的特征键在数据中均不可用或不是匹配图像形状的2D数组。")
-                return None
-            arr = np.stack([feats[k] for k in names], axis=-1)
+        arr, names = _supervised_feature_array(feats, use_hierarchical_all, shape)
+        if arr is None:
+            return None
         model_path = os.path.join(output_dir, RF_MODEL_FILE)
         try:
             import joblib
@@ -480,6 +497,26 @@ def _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, class
             return None
     print(f"错误: 不支持的分割方法 '{method}'")
     return None
+
+
+def _supervised_feature_array(feats, use_hierarchical_all, shape):
+    """The feature array of the supervised branches (scripts/3:413-437) -> ((H, W, F) array, feature names), or (None, []) after
+    the reference's message."""
+    arr, names = None, []
+    if use_hierarchical_all:
+        for key in ("hierarchical_all", "hierarchical_features_all"):
+            v = feats.get(key)
+            if isinstance(v, np.ndarray) and v.ndim == 3 and v.shape[:2] == shape:
+                arr = v
+                names = [f"hierarchical_feature_{i + 1}" for i in range(v.shape[-1])]
+                break
+    if arr is None:   # scripts/3:425-437: every 2-D plane of the image's shape, in dict order
+        names = [k for k, v in feats.items() if isinstance(v, np.ndarray) and v.ndim == 2 and v.shape == shape]
+        if not names:
+            print("错误: 为随机森林指定的特征键在数据中均不可用或不是匹配图像形状的2D数组。")
+            return None, []
+        arr = np.stack([feats[k] for k in names], axis=-1)
+    return arr, names
 
 
 def _rt_unsupported():
@@ -574,7 +611,7 @@ def _is_device_tensor(x) -> bool:
 def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters, ctx, evaluate, raw, confidence, importance,
                      kmeans_model: Optional[str] = None, save_kmeans_model: Optional[str] = None, mask_nodata=None, sieve: int = 0,
                      majority: int = 0, majority_iterations: int = 1, gcps=None, warp_order: int = 1, resampling: str = "nearest",
-                     pixel_size: Optional[float] = None) -> Dict[str, object]:
+                     pixel_size: Optional[float] = None, ml_threshold: Optional[float] = None, rule_image: bool = False) -> Dict[str, object]:
     """run_scripts_2_3, and with classify='kmeans' the two model options of the command line: `save_kmeans_model` fits as
     always and also writes the fitted model there (KMeansModel.save; the class map is the same file byte for byte),
     `kmeans_model` applies a saved model and fits nothing (run_kmeans_model_stage).
@@ -583,7 +620,9 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
     gcps (with raw; beyond the reference): stage 1 rectifies the DN planes first (rsseg.georect, K21) and the feature stage goes
     on from the warped planes with the new shape and georeferencing.  With mask_nodata the warp's validity mask is AND-ed into
     the nodata mask of the warped DN planes (a bare --mask-nodata on a file without a GDAL_NODATA tag masks by the warp alone);
-    without it the collar outside the source is classified as data, as it would be after a cv2.warpAffine."""
+    without it the collar outside the source is classified as data, as it would be after a cv2.warpAffine.
+    ml_threshold, rule_image (classify in GAUSS_METHODS): the chi-square quantile beyond which a pixel stays unclassified, and
+    the rule images <method>_dist2.npy / <method>_margin.npy beside the class map."""
     valid_mask = None
     if raw:
         from .preprocess import run_preprocessing_stage
@@ -636,7 +675,10 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
         np.save(res["valid_mask_path"], valid_mask)
     if classify and valid_mask is not None:
         sdir = os.path.join(output_dir, "segmentation_results")
-        if confidence and classify == "random_forest":
+        if classify in GAUSS_METHODS:
+            res["class_map"] = _run_classification(paths["pkl"], classify, sdir, True, n_clusters, None, None, "labeled_roi.tif", False, ctx,
+                                                   False, valid_mask=valid_mask, ml_threshold=ml_threshold, rule_image=rule_image)
+        elif confidence and classify == "random_forest":
             res["class_map"] = run_masked_classification_stage(paths["pkl"], classify, sdir, True, valid_mask=valid_mask, confidence=True, ctx=ctx)
         elif kmeans_model and classify == "kmeans":
             res["class_map"] = run_kmeans_model_stage(paths["pkl"], kmeans_model, sdir, ctx=ctx, valid_mask=valid_mask)
@@ -648,7 +690,10 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
                                                                ctx=ctx)
     elif classify:
         sdir = os.path.join(output_dir, "segmentation_results")
-        if importance and classify == "random_forest":
+        if classify in GAUSS_METHODS:
+            res["class_map"] = _run_classification(paths["pkl"], classify, sdir, True, n_clusters, None, None, "labeled_roi.tif", False, ctx,
+                                                   False, ml_threshold=ml_threshold, rule_image=rule_image)
+        elif importance and classify == "random_forest":
             from .evaluate import ClassificationEvaluator
             res["class_map"] = run_forest_importance_stage(paths["pkl"], ClassificationEvaluator._load(importance), sdir, True,
                                                            confidence=confidence, ctx=ctx)
@@ -692,6 +737,10 @@ def parse_args(ap, argv=None):
         ap.error("--kmeans-model / --save-kmeans-model need --classify kmeans")
     if a.kmeans_model and a.save_kmeans_model:
         ap.error("--kmeans-model applies a saved model and fits nothing: it does not go with --save-kmeans-model")
+    if (a.ml_threshold is not None or a.rule_image) and a.classify not in GAUSS_METHODS:
+        ap.error("--ml-threshold / --rule-image need --classify maximum_likelihood, mahalanobis or minimum_distance")
+    if a.ml_threshold is not None and not (0.0 < a.ml_threshold < 1.0):
+        ap.error("--ml-threshold takes a probability in (0, 1)")
     if a.mask_nodata is not None and not a.classify:
         ap.error("--mask-nodata needs --classify")
     if a.gcps and not a.raw:
@@ -715,7 +764,7 @@ def build_parser():
                                  description="feature extraction (scripts/2) and optionally classification (scripts/3) of one GeoTIFF on the GPU")
     ap.add_argument("image")
     ap.add_argument("output_dir")
-    ap.add_argument("--classify", choices=["kmeans", "rule_based", "random_forest"])
+    ap.add_argument("--classify", choices=["kmeans", "rule_based", "random_forest", *GAUSS_METHODS])
     ap.add_argument("--n-clusters", type=int, default=7)
     ap.add_argument("--no-preprocessing", action="store_true")
     ap.add_argument("--evaluate", metavar="ROI_MASK", help="accuracy assessment (scripts/4) of the class map against this ROI mask (.npy / .tif)")
@@ -731,6 +780,12 @@ def build_parser():
     ap.add_argument("--kmeans-model", metavar="PATH",
                     help="with --classify kmeans: apply this saved model instead of fitting -> the class map with the model's cluster ids, "
                          "kmeans_distance.npy and kmeans_model_summary.json")
+    ap.add_argument("--ml-threshold", type=float, default=None, metavar="P",
+                    help="with --classify maximum_likelihood / mahalanobis / minimum_distance: a pixel farther from its class than the "
+                         "chi-square quantile P (0 < P < 1, F degrees of freedom) stays unclassified (0)")
+    ap.add_argument("--rule-image", action="store_true",
+                    help="with --classify maximum_likelihood / mahalanobis / minimum_distance: also write <method>_dist2.npy (squared distance "
+                         "to the winning class) and <method>_margin.npy (runner-up minus winner)")
     def nodata_value(s):   # argparse hands a string `const` to `type` as well
         return s if s == MASK_NODATA_FROM_TAG else float(s)
     nodata_value.__name__ = "float"   # the word argparse's "invalid ... value" message uses
@@ -755,7 +810,8 @@ def main(argv=None) -> int:
     a = parse_args(ap, argv)
     res = _run_scripts_2_3(a.image, a.output_dir, a.classify, not a.no_preprocessing, a.n_clusters, None, a.evaluate, a.raw, a.confidence,
                            a.importance, a.kmeans_model, a.save_kmeans_model, a.mask_nodata, a.sieve, a.majority, a.majority_iterations,
-                           gcps=a.gcps, warp_order=a.warp_order, resampling=a.resampling, pixel_size=a.pixel_size)
+                           gcps=a.gcps, warp_order=a.warp_order, resampling=a.resampling, pixel_size=a.pixel_size, ml_threshold=a.ml_threshold,
+                           rule_image=a.rule_image)
     if a.raw:
         print(f"preprocessed: {res['preprocessed']}")
     for k, v in res["paths"].items():
