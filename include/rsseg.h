@@ -598,6 +598,46 @@ int rsseg_majority_u8(rsseg_ctx *ctx, const uint8_t *d_q, int Hin, int W, int y0
 int rsseg_sieve_u8(rsseg_ctx *ctx, const uint8_t *d_q, int H, int W, int min_area, int connectivity, int ignore, int removed_value,
                    uint8_t *d_out, int64_t *n_removed);
 
+/* ---- K23: SLIC superpixels and object-based class maps (no counterpart in the reference) -------- */
+/* Superpixels of P (1 ... 16) uint8 planes of H x W pixels; d_mask: NULL (all valid) or H * W bytes, 0 = not valid.  Every
+ * result has one right answer, restated in tests/slic_ref.py, and the kernels give it bit for bit.
+ * Grid: ny = ceil(H / S), nx = ceil(W / S) centres, id k = cy * nx + cx; the cell of a pixel is (y / S, x / S) and its
+ * first label is its cell's id.  Centre k: count, sum y, sum x, sum q_p over the valid pixels labelled k (integers), each
+ * mean float64(sum) / float64(count); a centre without a pixel is dead.  Iteration t = 1 ... max_iter: every valid pixel takes,
+ * among the live centres of the 3 x 3 cells around its cell, visited in ascending id, the first with a strictly smaller
+ *   D = dc + weight * ds,  dc = sum_p (q_p - c_p)^2 (p ascending, from 0.0),  ds = (y - c_y)^2 + (x - c_x)^2
+ * (float64, every multiply and add one IEEE operation); if no label changed the iterations stop with *n_iter = t, otherwise
+ * the centres are recomputed; *n_iter = max_iter when they never stop, and max_iter = 0 leaves the grid.
+ * Connectivity (always): the 4-connected components of equal label; those of fewer than min_area pixels (none when
+ * min_area <= 1) give up their pixels, which are regrown in rounds: every unassigned valid pixel takes the segment of the
+ * first of its up, left, right, down neighbours that was assigned when the round began, until a round assigns none
+ * (*n_regrown: pixels assigned this way).  What no round reaches keeps its small component as its segment.
+ * d_labels (int32, H * W, 4-byte aligned): 0 for a masked pixel, else 1 ... *n_segments, numbered in the order of the
+ * segments' smallest pixel index.  weight: finite, >= 0 ((m / S)^2 for compactness m); 2 <= S <= 4096; max_iter, min_area >= 0
+ * (RSSEG_ERR_INVALID, naming the argument); P > 16 or H * W > 2^31 - 1: RSSEG_ERR_UNSUPPORTED.  Whole raster on one GPU.
+ * Synchronous.  Profiler names "slic_init", "slic_assign", "slic_enforce", "slic_relabel". */
+int rsseg_slic_u8(rsseg_ctx *ctx, const uint8_t *const *d_planes, int P, int H, int W, const uint8_t *d_mask, int S, double weight, int max_iter,
+                  int min_area, int32_t *d_labels, int64_t *n_segments, int *n_iter, int64_t *n_regrown);
+/* host-only: the tile of the assignment kernel (columns, rows), for the tests that straddle its seams */
+void rsseg_slic_tile(int *tile_w, int *tile_h);
+/* The reductions below take a segment plane d_seg (int32) with labels 0 ... n_segments, 0 meaning "no segment"; a label
+ * outside that range is RSSEG_ERR_INVALID (it is never used as an index).
+ * d_sums (device, int64[(n_segments + 1)][3 + P], row 0 all zero): per segment the pixel count, sum y, sum x and the sum of
+ * each of the P (0 ... 16) planes, over the pixels whose d_mask byte (NULL: all) is non-zero.  dtype RSSEG_U8: the bytes;
+ * RSSEG_F32: llrint(x * 2^40) (round to nearest even), exact for |x| < 2^11; the caller keeps count * max|x| below 2^23 and
+ * NaN out.  Integer sums: the result does not depend on the order of the atomics.  Profiler name "segment_sums". */
+int rsseg_segment_sums(rsseg_ctx *ctx, const int32_t *d_seg, int H, int W, int64_t n_segments, const void *const *d_planes, int P, int dtype,
+                       const uint8_t *d_mask, int64_t *d_sums);
+/* d_table (device, uint8[n_segments + 1]): per segment the label of d_class (uint8, n pixels) with the most votes among its
+ * pixels, ties to the smallest label; `ignore` (0 ... 255, -1: none) never votes; a segment without a voter, and entry 0,
+ * get `fill` (0 ... 255).  The vote table is n_segments x (largest voting label + 1) int32: above 2 GiB is
+ * RSSEG_ERR_UNSUPPORTED.  Profiler name "segment_majority". */
+int rsseg_segment_majority_u8(rsseg_ctx *ctx, const int32_t *d_seg, int64_t n, int64_t n_segments, const uint8_t *d_class, int ignore, int fill,
+                              uint8_t *d_table);
+/* d_out[i] = d_table[d_seg[i]]; elements of elem_bytes = 1 or 4 (uint8, float32, int32); entry 0 is the caller's.
+ * Profiler name "segment_paint". */
+int rsseg_segment_paint(rsseg_ctx *ctx, const int32_t *d_seg, int64_t n, int64_t n_segments, const void *d_table, int elem_bytes, void *d_out);
+
 /* ---- K13: remaining texture members of the feature dictionary ---------------- */
 /* calculate_lbp_features (indices.py:320-344): skimage.feature.local_binary_pattern(u8, n_points, radius, 'uniform');
  * d_out: the codes 0 .. n_points + 1 as uint8 (the caller divides by their maximum in float64, :342). */

@@ -168,6 +168,11 @@ SIGNATURES = {
     "rsseg_majority_u8": (_int, [_vp, _vp, _int, _int, _int, _int, _int, _int, _int, _int, _int, _int, C.c_uint32, _vp, C.POINTER(_i64),
                                  C.POINTER(_i64)]),
     "rsseg_sieve_u8": (_int, [_vp, _vp, _int, _int, _int, _int, _int, _int, _vp, C.POINTER(_i64)]),
+    "rsseg_slic_u8": (_int, [_vp, _PP, _int, _int, _int, _vp, _int, C.c_double, _int, _int, _vp, C.POINTER(_i64), C.POINTER(_int), C.POINTER(_i64)]),
+    "rsseg_slic_tile": (None, [C.POINTER(_int), C.POINTER(_int)]),
+    "rsseg_segment_sums": (_int, [_vp, _vp, _int, _int, _i64, _PP, _int, _int, _vp, _vp]),
+    "rsseg_segment_majority_u8": (_int, [_vp, _vp, _i64, _i64, _vp, _int, _int, _vp]),
+    "rsseg_segment_paint": (_int, [_vp, _vp, _i64, _i64, _vp, _int, _vp]),
     "rsseg_lbp_uniform_u8": (_int, [_vp, _vp, _int, _int, _int, C.c_double, _vp]),
     "rsseg_rank_entropy_u8": (_int, [_vp, _vp, _int, _int, _int, _vp]),
     "rsseg_gaussian_blur_u8": (_int, [_vp, _vp, _int, _int, _int, _vp]),

@@ -769,6 +769,59 @@ class Context:
                                           C.c_void_p(out.data_ptr()), C.byref(nr)))
         return out, nr.value
 
+    # ---- K23: superpixels and per-segment reductions (rsseg/segment.py) ---------------------------
+    def slic_tile(self) -> Tuple[int, int]:
+        """(columns, rows) of the assignment kernel's tile."""
+        tw, th = C.c_int(0), C.c_int(0)
+        self.lib.rsseg_slic_tile(C.byref(tw), C.byref(th))
+        return tw.value, th.value
+
+    def slic_u8(self, planes: Sequence, H: int, W: int, step: int, weight: float, max_iter: int = 10, min_area: int = 0, mask=None):
+        """SLIC superpixels of uint8 device planes (include/rsseg.h, rsseg_slic_u8): (labels int32 of H * W with 0 = masked and
+        1 ... n_segments, n_segments, n_iter, n_regrown).  mask: None or a uint8 plane, 0 = not valid."""
+        torch = _torch()
+        labels = self.empty(H * W, torch.int32)
+        ns, ni, nr = C.c_int64(0), C.c_int(0), C.c_int64(0)
+        self._chk(self.lib.rsseg_slic_u8(self.h, self._pp(planes), len(planes), int(H), int(W), None if mask is None else C.c_void_p(mask.data_ptr()),
+                                         int(step), C.c_double(weight), int(max_iter), int(min_area), C.c_void_p(labels.data_ptr()), C.byref(ns),
+                                         C.byref(ni), C.byref(nr)))
+        return labels, ns.value, ni.value, nr.value
+
+    def segment_sums(self, seg, H: int, W: int, n_segments: int, planes: Sequence = (), mask=None):
+        """int64 device table [(n_segments + 1), 3 + P] of rsseg_segment_sums: area, sum y, sum x and the sum of every plane per
+        segment (uint8 planes as integers, float32 planes in units of 2^-40).  At most 16 planes of one dtype per call."""
+        torch = _torch()
+        P = len(planes)
+        u8 = [self._is_u8(p) for p in planes]
+        if any(u8) and not all(u8):
+            raise ValueError("segment_sums: uint8 and float32 planes cannot be mixed in one call")
+        if P and not all(u8) and any(p.dtype != torch.float32 for p in planes):
+            raise ValueError("segment_sums: planes must be uint8 or float32")
+        out = self.empty((int(n_segments) + 1) * (3 + P), torch.int64)
+        self._chk(self.lib.rsseg_segment_sums(self.h, C.c_void_p(seg.data_ptr()), int(H), int(W), int(n_segments), self._pp(planes) if P else None, P,
+                                              L.U8 if (P == 0 or all(u8)) else L.F32, None if mask is None else C.c_void_p(mask.data_ptr()),
+                                              C.c_void_p(out.data_ptr())))
+        return out.reshape(int(n_segments) + 1, 3 + P)
+
+    def segment_majority_u8(self, seg, n_segments: int, class_map, ignore: int = -1, fill: int = 0):
+        """uint8 device table [n_segments + 1] of rsseg_segment_majority_u8: every segment's most frequent label of class_map
+        (ties: the smallest; `ignore` never votes; no voter, and entry 0: `fill`)."""
+        torch = _torch()
+        table = self.empty(int(n_segments) + 1, torch.uint8)
+        self._chk(self.lib.rsseg_segment_majority_u8(self.h, C.c_void_p(seg.data_ptr()), seg.numel(), int(n_segments), C.c_void_p(class_map.data_ptr()),
+                                                     int(ignore), int(fill), C.c_void_p(table.data_ptr())))
+        return table
+
+    def segment_paint(self, seg, n_segments: int, table):
+        """out[i] = table[seg[i]] for a uint8, float32 or int32 device table of n_segments + 1 entries."""
+        if table.numel() != int(n_segments) + 1 or table.element_size() not in (1, 4):
+            raise ValueError(f"segment_paint: the table has {table.numel()} entries of {table.element_size()} bytes, "
+                             f"{int(n_segments) + 1} of 1 or 4 bytes are needed")
+        out = self.empty(seg.numel(), table.dtype)
+        self._chk(self.lib.rsseg_segment_paint(self.h, C.c_void_p(seg.data_ptr()), seg.numel(), int(n_segments), C.c_void_p(table.data_ptr()),
+                                               table.element_size(), C.c_void_p(out.data_ptr())))
+        return out
+
     # ---- K9/K10 --------------------------------------------------------------------------------
     def kmeans_fit_predict(self, planes: Sequence, n_clusters: int, seed: int = 42, max_iter: int = 300, tol: float = 1e-4):
         torch = _torch()

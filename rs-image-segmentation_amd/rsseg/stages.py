@@ -608,10 +608,59 @@ def _is_device_tensor(x) -> bool:
     return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
 
 
+SEGMENT_STATS_FILE = "segment_stats.json"
+
+
+def run_segment_stage(feature_file_path, class_map, output_dir: str, method: str, step: int, compactness: float = 10.0, iterations: int = 10,
+                      object_based: bool = False, *, valid_mask=None, nodata: int = 0, transform=None, crs=None,
+                      ctx: Optional[Context] = None) -> Tuple[np.ndarray, Dict[str, object], Optional[np.ndarray]]:
+    """Superpixels of the feature stack (rsseg.segment.slic; no counterpart in the reference) and, with object_based, the class
+    map voted per superpixel.  The planes are the (H, W, F) stack of the feature file the supervised classifiers read
+    (hierarchical_all, else every 2-D plane); a stack of more than 16 planes is segmented on its first 16 (segment_stats.json
+    names how many).  valid_mask: pixels outside it belong to no segment and stay `nodata` in the object map.
+    Writes, beside the raw map's files that stay as they are: <output_dir>/segments.npy (int32, 0 = masked), segment_stats.json
+    (the parameters, n_segments, n_iter, n_regrown, the smallest / median / largest area) and, with object_based,
+    classification_<method>_objects.npy and <method>_classification_map_objects.tif (uint8, nodata 0, LZW tiles).
+    Returns (segments, that dictionary, object map or None)."""
+    import json
+    from . import segment as SG
+    from .tiff import write_tiff
+    feats = _load_normalised(feature_file_path, output_dir)
+    if feats is None:
+        raise ValueError(f"run_segment_stage: {feature_file_path} holds no feature stack")
+    shape = (int(feats["height"]), int(feats["width"]))
+    arr, names = _supervised_feature_array(feats, True, shape)
+    if arr is None:
+        raise ValueError(f"run_segment_stage: {feature_file_path} holds no plane of shape {shape}")
+    used = min(arr.shape[-1], SG.MAX_PLANES)
+    if used < arr.shape[-1]:
+        print(f"segments: the feature stack has {arr.shape[-1]} planes, the first {used} are segmented ({', '.join(names[:used])})")
+    planes = [np.ascontiguousarray(arr[..., i]) for i in range(used)]
+    segments, st = SG.slic(planes, step=step, compactness=compactness, max_iter=iterations, mask=valid_mask, ctx=ctx, return_stats=True)
+    area = np.bincount(segments.reshape(-1), minlength=st["n_segments"] + 1)[1:]
+    stats: Dict[str, object] = {"method": method, **st, "planes_in_stack": int(arr.shape[-1]), "planes_used": int(used),
+                                "masked_pixels": int((segments == 0).sum()),
+                                "area_min": int(area.min()) if area.size else 0, "area_median": float(np.median(area)) if area.size else 0.0,
+                                "area_max": int(area.max()) if area.size else 0, "object_based": bool(object_based)}
+    os.makedirs(output_dir, exist_ok=True)
+    np.save(os.path.join(output_dir, "segments.npy"), segments)
+    objects = None
+    if object_based:
+        objects = SG.object_classify(segments, class_map, nodata=nodata, ctx=ctx)
+        np.save(os.path.join(output_dir, f"classification_{method}_objects.npy"), objects)
+        write_tiff(os.path.join(output_dir, f"{method}_classification_map_objects.tif"), objects, transform=transform, epsg=_epsg_of(crs),
+                   geographic=_is_geographic(crs), nodata=0, compress="lzw", tiled=True)
+        stats["pixels_changed_by_objects"] = int((objects != np.asarray(class_map)).sum())
+    with open(os.path.join(output_dir, SEGMENT_STATS_FILE), "w") as f:
+        json.dump(stats, f, indent=1)
+    return segments, stats, objects
+
+
 def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters, ctx, evaluate, raw, confidence, importance,
                      kmeans_model: Optional[str] = None, save_kmeans_model: Optional[str] = None, mask_nodata=None, sieve: int = 0,
                      majority: int = 0, majority_iterations: int = 1, gcps=None, warp_order: int = 1, resampling: str = "nearest",
-                     pixel_size: Optional[float] = None, ml_threshold: Optional[float] = None, rule_image: bool = False) -> Dict[str, object]:
+                     pixel_size: Optional[float] = None, ml_threshold: Optional[float] = None, rule_image: bool = False, segment: int = 0,
+                     compactness: float = 10.0, segment_iterations: int = 10, object_based: bool = False) -> Dict[str, object]:
     """run_scripts_2_3, and with classify='kmeans' the two model options of the command line: `save_kmeans_model` fits as
     always and also writes the fitted model there (KMeansModel.save; the class map is the same file byte for byte),
     `kmeans_model` applies a saved model and fits nothing (run_kmeans_model_stage).
@@ -622,7 +671,9 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
     the nodata mask of the warped DN planes (a bare --mask-nodata on a file without a GDAL_NODATA tag masks by the warp alone);
     without it the collar outside the source is classified as data, as it would be after a cv2.warpAffine.
     ml_threshold, rule_image (classify in GAUSS_METHODS): the chi-square quantile beyond which a pixel stays unclassified, and
-    the rule images <method>_dist2.npy / <method>_margin.npy beside the class map."""
+    the rule images <method>_dist2.npy / <method>_margin.npy beside the class map.
+    segment (a grid step), compactness, segment_iterations, object_based: run_segment_stage on the feature file, under the same
+    valid mask; the object-based map is evaluated into <output_dir>/evaluation_results_objects."""
     valid_mask = None
     if raw:
         from .preprocess import run_preprocessing_stage
@@ -722,6 +773,15 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
                 cdir = os.path.join(output_dir, "evaluation_results_clean")
                 res["metrics_clean"], _ = ev.evaluate_maps(res["class_map_clean"], ev.load_roi_mask(evaluate), cdir)
                 res["evaluation_dir_clean"] = cdir
+        if segment and res["class_map"] is not None:
+            # superpixels, and the class map voted per superpixel, beside the raw map (whose files stay byte for byte what they are)
+            res["segments"], res["segment_stats"], res["class_map_objects"] = run_segment_stage(
+                paths["pkl"], res["class_map"], sdir, classify, segment, compactness, segment_iterations, object_based, valid_mask=valid_mask,
+                transform=geo["transform"], crs=crs, ctx=ctx)
+            if evaluate and object_based:
+                odir = os.path.join(output_dir, "evaluation_results_objects")
+                res["metrics_objects"], _ = ev.evaluate_maps(res["class_map_objects"], ev.load_roi_mask(evaluate), odir)
+                res["evaluation_dir_objects"] = odir
     return res
 
 
@@ -755,6 +815,16 @@ def parse_args(ap, argv=None):
         ap.error("--majority takes an odd window in 3..15")
     if a.majority_iterations < 0:
         ap.error("--majority-iterations takes a non-negative count")
+    if a.segment and not a.classify:
+        ap.error("--segment needs --classify")
+    if a.segment and not 2 <= a.segment <= 4096:
+        ap.error("--segment takes a grid step in 2..4096")
+    if (a.object_based or a.compactness is not None or a.segment_iterations is not None) and not a.segment:
+        ap.error("--compactness / --segment-iterations / --object-based need --segment")
+    if a.compactness is not None and not (a.compactness >= 0.0 and a.compactness < float("inf")):
+        ap.error("--compactness takes a finite non-negative number")
+    if a.segment_iterations is not None and a.segment_iterations < 0:
+        ap.error("--segment-iterations takes a non-negative count")
     return a
 
 
@@ -800,6 +870,15 @@ def build_parser():
     ap.add_argument("--majority", type=int, default=0, metavar="K",
                     help="with --classify: K x K majority filter (K odd, 3..15) of the (sieved) class map, written as the cleaned map")
     ap.add_argument("--majority-iterations", type=int, default=1, metavar="N", help="with --majority: up to N passes (stopped once one changes nothing)")
+    ap.add_argument("--segment", type=int, default=0, metavar="STEP",
+                    help="with --classify: also cut the feature stack into SLIC superpixels on a grid of STEP pixels (rsseg.segment) -> "
+                         "segments.npy (int32, 0 = masked) and segment_stats.json")
+    ap.add_argument("--compactness", type=float, default=None, metavar="M",
+                    help="with --segment: weight of the pixel distance beside the 8-bit feature distance (default 10)")
+    ap.add_argument("--segment-iterations", type=int, default=None, metavar="N", help="with --segment: at most N assignment iterations (default 10)")
+    ap.add_argument("--object-based", action="store_true",
+                    help="with --segment: also write the class map voted per superpixel (classification_<method>_objects.npy, "
+                         "<method>_classification_map_objects.tif)")
     from .preprocess import add_gcp_arguments
     add_gcp_arguments(ap)   # with --raw
     return ap
@@ -811,7 +890,8 @@ def main(argv=None) -> int:
     res = _run_scripts_2_3(a.image, a.output_dir, a.classify, not a.no_preprocessing, a.n_clusters, None, a.evaluate, a.raw, a.confidence,
                            a.importance, a.kmeans_model, a.save_kmeans_model, a.mask_nodata, a.sieve, a.majority, a.majority_iterations,
                            gcps=a.gcps, warp_order=a.warp_order, resampling=a.resampling, pixel_size=a.pixel_size, ml_threshold=a.ml_threshold,
-                           rule_image=a.rule_image)
+                           rule_image=a.rule_image, segment=a.segment, compactness=10.0 if a.compactness is None else a.compactness,
+                           segment_iterations=10 if a.segment_iterations is None else a.segment_iterations, object_based=a.object_based)
     if a.raw:
         print(f"preprocessed: {res['preprocessed']}")
     for k, v in res["paths"].items():
@@ -829,6 +909,14 @@ def main(argv=None) -> int:
         if "metrics_clean" in res:
             m = res["metrics_clean"]
             print(f"evaluation of the cleaned map: OA {m['overall_accuracy'] * 100:.2f}%, kappa {m['kappa_coefficient']:.4f} -> {res['evaluation_dir_clean']}")
+        if "segment_stats" in res:
+            s = res["segment_stats"]
+            print(f"segments: {s['n_segments']} superpixels of {s['area_min']} .. {s['area_max']} pixels after {s['n_iter']} iterations, "
+                  f"{s['n_regrown']} pixels regrown -> {res['segmentation_dir']}")
+        if "metrics_objects" in res:
+            m = res["metrics_objects"]
+            print(f"evaluation of the object-based map: OA {m['overall_accuracy'] * 100:.2f}%, kappa {m['kappa_coefficient']:.4f} -> "
+                  f"{res['evaluation_dir_objects']}")
         return 0 if cm is not None else 1
     return 0
 
