@@ -638,6 +638,33 @@ int rsseg_segment_majority_u8(rsseg_ctx *ctx, const int32_t *d_seg, int64_t n, i
  * Profiler name "segment_paint". */
 int rsseg_segment_paint(rsseg_ctx *ctx, const int32_t *d_seg, int64_t n, int64_t n_segments, const void *d_table, int elem_bytes, void *d_out);
 
+/* ---- K24: class signatures: per-label sums of 1, x and x x^T (no counterpart in the reference) -- */
+/* d_out (device, int64[n_classes][1 + F + F (F + 1) / 2], 8-byte aligned): per label the exact integer moments of F
+ * feature planes (RSSEG_F32 or RSSEG_U8, band-planar, n_local pixels) over the counted pixels.  One right answer, restated in
+ * tests/moments_ref.py; the kernel gives it bit for bit whatever the workgroup count, tile or path.
+ * Counted: the mask byte is non-zero (d_mask NULL: all) and the label (RSSEG_U8 or RSSEG_I32) differs from `ignore` (-1: no
+ * label is ignored).  A counted label outside 0 ... n_classes - 1 is RSSEG_ERR_INVALID and is never used as an index.
+ * RSSEG_F32: v_f = the plane value, a NaN read as +0; u_f = v_f * 2^plane_exp[f] (exact, in float64); a counted pixel with any
+ * |u_f| > 1 (+-inf included) enters no column and is counted in *n_left_out.  Otherwise row `label` takes
+ *   column 0                  += 1
+ *   column 1 + f              += rint(u_f * 2^Q)
+ *   column 1 + F + tri(a, b)  += rint(u_a * 2^Q * u_b)     a <= b, tri = the row-major index in the upper triangle
+ * the product exact (two 24-bit significands) and rounded once, to nearest-even: fma(u_a * 2^Q, u_b, 1.5 * 2^52).
+ * RSSEG_U8: the columns are the plain integers 1, v_f and v_a * v_b; plane_exp must be NULL and Q 0; *n_left_out = 0.
+ * Limits: 1 <= F <= 64 and 1 <= n_classes <= 256 (above: RSSEG_ERR_UNSUPPORTED); 0 <= Q <= 50, n_local * 2^Q < 2^62,
+ * |plane_exp[f]| <= 300; RSSEG_ERR_INVALID, naming the argument, for these, a null pointer or a plane, label plane or table
+ * not aligned to its element.  n_local == 0 writes zeros.  Planes, labels and mask may have any alignment that holds their
+ * element.  With a communication hook installed the table and *n_left_out are summed over the ranks (int64 SUM through the
+ * communication buffer).  Synchronous.  Profiler name "class_moments". */
+int rsseg_class_moments(rsseg_ctx *ctx, const void *const *d_planes, int F, int dtype /* RSSEG_F32 | RSSEG_U8 */, int64_t n_local,
+                        const void *d_labels, int label_dtype /* RSSEG_U8 | RSSEG_I32 */, int n_classes, int ignore /* -1: none */,
+                        const uint8_t *d_mask /* NULL or n_local bytes, 0 = not counted */,
+                        const int *plane_exp /* host, F */, int Q,
+                        int64_t *d_out /* device, int64[n_classes][1 + F + F (F + 1) / 2] */, int64_t *n_left_out /* host */);
+/* host-only: *path = 0 when the workgroup keeps its table in LDS (Path A), 1 when it adds into the global table (Path B), -1
+ * outside the limits; *tile_pixels = the pixels a workgroup stages at a time.  For the tests that straddle the seams. */
+void rsseg_class_moments_plan(int F, int n_classes, int dtype, int *path, int *tile_pixels);
+
 /* ---- K13: remaining texture members of the feature dictionary ---------------- */
 /* calculate_lbp_features (indices.py:320-344): skimage.feature.local_binary_pattern(u8, n_points, radius, 'uniform');
  * d_out: the codes 0 .. n_points + 1 as uint8 (the caller divides by their maximum in float64, :342). */

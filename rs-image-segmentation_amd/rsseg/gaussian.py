@@ -154,8 +154,69 @@ class GaussianClassifier:
             raise ValueError("roi_mask labels no pixel")
         return np.nan_to_num(features.reshape(-1, features.shape[2])[keep, :], nan=0.0), flat[keep]
 
-    def fit_image(self, features, roi_mask) -> "GaussianClassifier":
+    def fit_image(self, features, roi_mask, device: bool = False, ctx=None) -> "GaussianClassifier":
+        """device=True: the classes' moments are taken from the raster on the GPU (rsseg.signatures.class_moments, K24) and the
+        model comes from them (fit_moments); no host sample matrix is built.  features may then also be device planes."""
+        if device:
+            from .signatures import class_moments
+            roi = roi_mask
+            if not hasattr(roi, "data_ptr"):   # a host raster: 0 and NaN label nothing (training_samples' rule), the rest is 1..255
+                roi = np.asarray(roi)
+                if roi.dtype != np.uint8:
+                    r64 = np.nan_to_num(roi.astype(np.float64), nan=0.0)
+                    if np.any(r64 != np.floor(r64)) or np.any(r64 < 0) or np.any(r64 > 255):
+                        raise ValueError("GaussianClassifier.fit: class labels must be integers in 1..255 (0 is 'unclassified')")
+                    roi = r64.astype(np.uint8)
+            return self.fit_moments(class_moments(features, roi, ignore=0, ctx=ctx))
         return self.fit(*self.training_samples(features, roi_mask))
+
+    def fit_moments(self, moments) -> "GaussianClassifier":
+        """fit() from the counts, means and covariances of a rsseg.signatures.ClassMoments (the table's row is the class label)
+        instead of a sample matrix: the same checks, priors and whitening."""
+        if moments.n_left_out:
+            raise ValueError("GaussianClassifier.fit: X holds NaN or infinite values")
+        classes = np.asarray(moments.classes, np.int64)
+        if classes.size == 0:
+            raise ValueError("roi_mask labels no pixel")
+        if classes.min() < 1 or classes.max() > 255:
+            raise ValueError(f"GaussianClassifier.fit: class labels must be integers in 1..255 (0 is 'unclassified'), got "
+                             f"{[int(c) for c in classes if c < 1 or c > 255][:5]}")
+        F, k = moments.n_features, classes.size
+        counts = moments.counts[classes].astype(np.int64)
+        n = int(counts.sum())
+        if isinstance(self.priors, str):
+            pri = counts / float(n) if self.priors == "empirical" else np.full(k, 1.0 / k)
+        else:
+            pri = np.asarray(self.priors, np.float64).reshape(-1)
+            if pri.size != k or not np.all(np.isfinite(pri)) or np.any(pri <= 0) or abs(pri.sum() - 1.0) > 1e-8:
+                raise ValueError(f"GaussianClassifier.fit: priors must be {k} positive probabilities that sum to 1")
+        W = np.zeros((k, F, F))
+        offset = np.zeros(k)
+        if self.method == "ml":
+            for j, c in enumerate(classes):
+                if counts[j] < F + 1:
+                    raise ValueError(f"GaussianClassifier.fit: class {c} has {counts[j]} samples, a covariance of {F} features needs "
+                                     f"at least {F + 1}")
+            cov = moments.cov()
+            for j, c in enumerate(classes):
+                W[j], logdet = _whitening(cov[j], f"class {c}")
+                offset[j] = logdet - 2.0 * np.log(pri[j])
+        elif self.method == "mahalanobis":
+            if n - k < 1:
+                raise ValueError(f"GaussianClassifier.fit: {n} samples of {k} classes leave nothing for the pooled covariance")
+            W[:], _ = _whitening(moments.pooled_cov(), "the pooled classes")
+        else:
+            W[:] = np.eye(F)
+        self.classes_ = classes
+        self.class_counts_ = counts
+        self.priors_ = pri
+        self.n_features_in_ = F
+        self.mean_ = moments.mean()
+        self.whiten_ = pack_lower(W)
+        self.offset_ = offset
+        self.class_values_ = classes.astype(np.uint8)
+        self.max_dist2_ = self._resolve_max_dist2(F)
+        return self
 
     # ---- the model as arrays -------------------------------------------------------------------------------------------
     def _check_fitted(self):

@@ -986,6 +986,44 @@ class Context:
                                                 C.c_void_p(margin.data_ptr()) if want_margin else None))
         return labels[:n], (dist2[:n] if want_dist2 else None), (margin[:n] if want_margin else None)
 
+    # ---- K24: class signatures (rsseg/signatures.py) ----------------------------------------------
+    def class_moments_plan(self, F: int, n_classes: int, u8: bool = False) -> Tuple[int, int]:
+        """(path, tile_pixels) of rsseg_class_moments for F planes and n_classes labels: path 0 keeps the workgroup's table in
+        LDS, 1 adds into the global table."""
+        path, tile = C.c_int(0), C.c_int(0)
+        self.lib.rsseg_class_moments_plan(int(F), int(n_classes), L.U8 if u8 else L.F32, C.byref(path), C.byref(tile))
+        return path.value, tile.value
+
+    def class_moments(self, planes: Sequence, labels, n_classes: int, plane_exp, Q: int, ignore: int = -1, mask=None):
+        """rsseg_class_moments (include/rsseg.h) on flat float32 or uint8 device planes and a uint8 or int32 label plane:
+        (int64 device table [n_classes, 1 + F + F (F + 1) / 2], n_left_out).  plane_exp: F ints for float32 planes, None for
+        uint8 planes (whose Q is 0).  mask: None or a uint8 plane, 0 = not counted."""
+        torch = _torch()
+        F = len(planes)
+        if F == 0:
+            raise ValueError("class_moments: no feature planes")
+        dt, n = planes[0].dtype, planes[0].numel()
+        if any(p.dtype != dt or p.numel() != n for p in planes) or dt not in (torch.float32, torch.uint8):
+            raise ValueError("class_moments: planes must all be float32 or all uint8, of one length")
+        if labels.dtype not in (torch.uint8, torch.int32) or labels.numel() != n:
+            raise ValueError("class_moments: labels must be a uint8 or int32 plane of the planes' length")
+        if mask is not None and (mask.dtype != torch.uint8 or mask.numel() != n):
+            raise ValueError("class_moments: mask must be a uint8 plane of the planes' length")
+        pe = None
+        if plane_exp is not None:
+            pe = np.ascontiguousarray(plane_exp, dtype=np.int32).reshape(-1)
+            if pe.size != F:
+                raise ValueError(f"class_moments: {pe.size} plane exponents for {F} planes")
+        cols = 1 + F + F * (F + 1) // 2
+        out = self.empty(max(int(n_classes), 1) * cols, torch.int64)
+        left = C.c_int64(0)
+        self._chk(self.lib.rsseg_class_moments(self.h, self._pp(planes), F, L.F32 if dt == torch.float32 else L.U8, n,
+                                               C.c_void_p(labels.data_ptr()) if n else None, L.U8 if labels.dtype == torch.uint8 else L.I32,
+                                               int(n_classes), int(ignore), None if mask is None else C.c_void_p(mask.data_ptr()),
+                                               None if pe is None else pe.ctypes.data_as(C.POINTER(C.c_int)), int(Q), C.c_void_p(out.data_ptr()),
+                                               C.byref(left)))
+        return out.reshape(max(int(n_classes), 1), cols), left.value
+
     # ---- K11 -----------------------------------------------------------------------------------
     def forest_load(self, forest: dict):
         f = forest

@@ -340,7 +340,8 @@ def _load_normalised(feature_file_path, output_dir):
 
 def _run_classification(feature_file_path, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys,
                         labeled_roi_file, strict_reference, ctx, confidence, importance_mask=None,
-                        save_kmeans_model=None, valid_mask=None, ml_threshold=None, rule_image=False) -> Optional[np.ndarray]:
+                        save_kmeans_model=None, valid_mask=None, ml_threshold=None, rule_image=False,
+                        fit_on_device=False) -> Optional[np.ndarray]:
     feats = _load_normalised(feature_file_path, output_dir)
     if feats is None:
         return None
@@ -358,6 +359,8 @@ def _run_classification(feature_file_path, method, output_dir, use_hierarchical_
             extras = {"want_kmeans_model": True}
         if method in GAUSS_METHODS:
             extras = {"ml_threshold": ml_threshold, "want_rule_image": bool(rule_image)}
+            if fit_on_device:
+                extras["fit_on_device"] = True
         out = _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys, labeled_roi_file,
                         strict_reference, extras, valid_mask)
     finally:
@@ -443,8 +446,15 @@ def _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, class
             return None
         from .gaussian import STAGE_METHODS, GaussianClassifier
         extras = {} if extras is None else extras
-        X, y = prepare_training_samples(arr, labeled_roi_file)
-        clf = GaussianClassifier(STAGE_METHODS[method], threshold=extras.get("ml_threshold")).fit(X, y)
+        if extras.get("fit_on_device"):   # the classes' moments from the raster on the GPU (K24): no host sample matrix
+            from .tiff import read_tiff
+            roi = read_tiff(labeled_roi_file)[0]
+            if roi.shape != shape:
+                raise ValueError(f"标签ROI文件 '{labeled_roi_file}' (形状 {roi.shape}) 尺寸与特征数据 (期望的2D形状 {shape}) 不匹配。")
+            clf = GaussianClassifier(STAGE_METHODS[method], threshold=extras.get("ml_threshold")).fit_image(arr, roi, device=True)
+        else:
+            X, y = prepare_training_samples(arr, labeled_roi_file)
+            clf = GaussianClassifier(STAGE_METHODS[method], threshold=extras.get("ml_threshold")).fit(X, y)
         rule = bool(extras.get("want_rule_image"))
         res = clf.predict_image(arr, mask=valid_mask, want_dist2=rule, want_margin=rule)
         extras["gauss_model"] = clf
@@ -609,6 +619,51 @@ def _is_device_tensor(x) -> bool:
 
 
 SEGMENT_STATS_FILE = "segment_stats.json"
+SIGNATURES_OF_MAP = "class-map"   # --signatures without a value: the classes of the raw class map just produced
+
+
+def run_signatures_stage(feature_file_path, label_map, output_dir: str, method: str, *, valid_mask=None, ignore: int = 0,
+                         ctx: Optional[Context] = None):
+    """Class signatures of a label raster over the feature stack (rsseg.signatures, K24; no counterpart in the reference): the
+    count, mean vector and covariance matrix of every class of `label_map` (an (H, W) uint8 class map, or an ROI raster of
+    training classes; `ignore`, default 0, labels nothing), taken in one pass on the GPU, and their pairwise separability.
+    The planes are the (H, W, F) stack of the feature file the supervised classifiers read (hierarchical_all, else every 2-D
+    plane), as float32.  valid_mask: pixels outside it are not counted.
+    Writes <output_dir>/signatures_<method>.npz (ClassMoments.save: the integer table, so that signature files of several
+    scenes merge) and separability_<method>.json (separability_report: Jeffries-Matusita and transformed divergence, the least
+    separable pair, per class the count, mean and standard deviation; a class whose covariance is singular is named under
+    "error" in place of the matrices).  Returns (ClassMoments, that dictionary)."""
+    import json
+    from . import signatures as SIG
+    feats = _load_normalised(feature_file_path, output_dir)
+    if feats is None:
+        raise ValueError(f"run_signatures_stage: {feature_file_path} holds no feature stack")
+    shape = (int(feats["height"]), int(feats["width"]))
+    arr, names = _supervised_feature_array(feats, True, shape)
+    if arr is None:
+        raise ValueError(f"run_signatures_stage: {feature_file_path} holds no plane of shape {shape}")
+    lab = label_map.cpu().numpy() if _is_device_tensor(label_map) else np.asarray(label_map)
+    if lab.shape != shape:
+        raise ValueError(f"run_signatures_stage: the label raster is {lab.shape}, the features are {shape}")
+    if lab.dtype != np.uint8:
+        l64 = np.nan_to_num(lab.astype(np.float64), nan=0.0)
+        if np.any(l64 != np.floor(l64)) or np.any(l64 < 0) or np.any(l64 > 255):
+            raise ValueError("run_signatures_stage: the labels must be integers in 0..255")
+        lab = l64.astype(np.uint8)
+    if valid_mask is not None:
+        valid_mask = _check_valid_mask(valid_mask, shape)
+    mom = SIG.class_moments(np.asarray(arr, np.float32) if arr.dtype != np.uint8 else arr, lab, ignore=ignore, mask=valid_mask, ctx=ctx)
+    os.makedirs(output_dir, exist_ok=True)
+    mom.save(os.path.join(output_dir, f"signatures_{method}.npz"))
+    try:
+        report = SIG.separability_report(mom)
+    except ValueError as e:   # a singular class: the per-class figures still stand
+        report = SIG.separability_report(mom, kinds=())
+        report["error"] = str(e)
+    report = {"method": method, "feature_names": list(names), **report}
+    with open(os.path.join(output_dir, f"separability_{method}.json"), "w") as f:
+        json.dump(report, f, indent=1)
+    return mom, report
 
 
 def run_segment_stage(feature_file_path, class_map, output_dir: str, method: str, step: int, compactness: float = 10.0, iterations: int = 10,
@@ -660,7 +715,8 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
                      kmeans_model: Optional[str] = None, save_kmeans_model: Optional[str] = None, mask_nodata=None, sieve: int = 0,
                      majority: int = 0, majority_iterations: int = 1, gcps=None, warp_order: int = 1, resampling: str = "nearest",
                      pixel_size: Optional[float] = None, ml_threshold: Optional[float] = None, rule_image: bool = False, segment: int = 0,
-                     compactness: float = 10.0, segment_iterations: int = 10, object_based: bool = False) -> Dict[str, object]:
+                     compactness: float = 10.0, segment_iterations: int = 10, object_based: bool = False, signatures: Optional[str] = None,
+                     fit_on_device: bool = False) -> Dict[str, object]:
     """run_scripts_2_3, and with classify='kmeans' the two model options of the command line: `save_kmeans_model` fits as
     always and also writes the fitted model there (KMeansModel.save; the class map is the same file byte for byte),
     `kmeans_model` applies a saved model and fits nothing (run_kmeans_model_stage).
@@ -673,7 +729,10 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
     ml_threshold, rule_image (classify in GAUSS_METHODS): the chi-square quantile beyond which a pixel stays unclassified, and
     the rule images <method>_dist2.npy / <method>_margin.npy beside the class map.
     segment (a grid step), compactness, segment_iterations, object_based: run_segment_stage on the feature file, under the same
-    valid mask; the object-based map is evaluated into <output_dir>/evaluation_results_objects."""
+    valid mask; the object-based map is evaluated into <output_dir>/evaluation_results_objects.
+    signatures (SIGNATURES_OF_MAP or the path of an ROI raster): run_signatures_stage on the raw class map, or on the ROI's
+    training classes, under the same valid mask.  fit_on_device (classify in GAUSS_METHODS): the model is fitted from moments
+    taken on the GPU (GaussianClassifier.fit_image(..., device=True))."""
     valid_mask = None
     if raw:
         from .preprocess import run_preprocessing_stage
@@ -728,7 +787,8 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
         sdir = os.path.join(output_dir, "segmentation_results")
         if classify in GAUSS_METHODS:
             res["class_map"] = _run_classification(paths["pkl"], classify, sdir, True, n_clusters, None, None, "labeled_roi.tif", False, ctx,
-                                                   False, valid_mask=valid_mask, ml_threshold=ml_threshold, rule_image=rule_image)
+                                                   False, valid_mask=valid_mask, ml_threshold=ml_threshold, rule_image=rule_image,
+                                                   fit_on_device=fit_on_device)
         elif confidence and classify == "random_forest":
             res["class_map"] = run_masked_classification_stage(paths["pkl"], classify, sdir, True, valid_mask=valid_mask, confidence=True, ctx=ctx)
         elif kmeans_model and classify == "kmeans":
@@ -743,7 +803,7 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
         sdir = os.path.join(output_dir, "segmentation_results")
         if classify in GAUSS_METHODS:
             res["class_map"] = _run_classification(paths["pkl"], classify, sdir, True, n_clusters, None, None, "labeled_roi.tif", False, ctx,
-                                                   False, ml_threshold=ml_threshold, rule_image=rule_image)
+                                                   False, ml_threshold=ml_threshold, rule_image=rule_image, fit_on_device=fit_on_device)
         elif importance and classify == "random_forest":
             from .evaluate import ClassificationEvaluator
             res["class_map"] = run_forest_importance_stage(paths["pkl"], ClassificationEvaluator._load(importance), sdir, True,
@@ -773,6 +833,13 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
                 cdir = os.path.join(output_dir, "evaluation_results_clean")
                 res["metrics_clean"], _ = ev.evaluate_maps(res["class_map_clean"], ev.load_roi_mask(evaluate), cdir)
                 res["evaluation_dir_clean"] = cdir
+        if signatures and res["class_map"] is not None:
+            if signatures == SIGNATURES_OF_MAP:
+                sig_labels = res["class_map"]
+            else:
+                from .evaluate import ClassificationEvaluator
+                sig_labels = ClassificationEvaluator._load(signatures)
+            res["signatures"], res["separability"] = run_signatures_stage(paths["pkl"], sig_labels, sdir, classify, valid_mask=valid_mask, ctx=ctx)
         if segment and res["class_map"] is not None:
             # superpixels, and the class map voted per superpixel, beside the raw map (whose files stay byte for byte what they are)
             res["segments"], res["segment_stats"], res["class_map_objects"] = run_segment_stage(
@@ -801,6 +868,10 @@ def parse_args(ap, argv=None):
         ap.error("--ml-threshold / --rule-image need --classify maximum_likelihood, mahalanobis or minimum_distance")
     if a.ml_threshold is not None and not (0.0 < a.ml_threshold < 1.0):
         ap.error("--ml-threshold takes a probability in (0, 1)")
+    if (a.signatures is not None or a.fit_on_device) and not a.classify:
+        ap.error("--signatures / --fit-on-device need --classify")
+    if a.fit_on_device and a.classify not in GAUSS_METHODS:
+        ap.error("--fit-on-device needs --classify maximum_likelihood, mahalanobis or minimum_distance")
     if a.mask_nodata is not None and not a.classify:
         ap.error("--mask-nodata needs --classify")
     if a.gcps and not a.raw:
@@ -856,6 +927,13 @@ def build_parser():
     ap.add_argument("--rule-image", action="store_true",
                     help="with --classify maximum_likelihood / mahalanobis / minimum_distance: also write <method>_dist2.npy (squared distance "
                          "to the winning class) and <method>_margin.npy (runner-up minus winner)")
+    ap.add_argument("--fit-on-device", action="store_true",
+                    help="with --classify maximum_likelihood / mahalanobis / minimum_distance: fit the model from class moments taken "
+                         "from the ROI raster on the GPU (rsseg.signatures) instead of a host sample matrix")
+    ap.add_argument("--signatures", nargs="?", const=SIGNATURES_OF_MAP, default=None, metavar="ROI_MASK",
+                    help="with --classify: also write signatures_<method>.npz (per-class count, mean and covariance as an exact integer "
+                         "table) and separability_<method>.json (Jeffries-Matusita, transformed divergence) of the classes of the raw "
+                         "class map, or, with ROI_MASK (.npy / .tif), of that raster's training classes")
     def nodata_value(s):   # argparse hands a string `const` to `type` as well
         return s if s == MASK_NODATA_FROM_TAG else float(s)
     nodata_value.__name__ = "float"   # the word argparse's "invalid ... value" message uses
@@ -891,7 +969,8 @@ def main(argv=None) -> int:
                            a.importance, a.kmeans_model, a.save_kmeans_model, a.mask_nodata, a.sieve, a.majority, a.majority_iterations,
                            gcps=a.gcps, warp_order=a.warp_order, resampling=a.resampling, pixel_size=a.pixel_size, ml_threshold=a.ml_threshold,
                            rule_image=a.rule_image, segment=a.segment, compactness=10.0 if a.compactness is None else a.compactness,
-                           segment_iterations=10 if a.segment_iterations is None else a.segment_iterations, object_based=a.object_based)
+                           segment_iterations=10 if a.segment_iterations is None else a.segment_iterations, object_based=a.object_based,
+                           signatures=a.signatures, fit_on_device=a.fit_on_device)
     if a.raw:
         print(f"preprocessed: {res['preprocessed']}")
     for k, v in res["paths"].items():
@@ -913,6 +992,11 @@ def main(argv=None) -> int:
             s = res["segment_stats"]
             print(f"segments: {s['n_segments']} superpixels of {s['area_min']} .. {s['area_max']} pixels after {s['n_iter']} iterations, "
                   f"{s['n_regrown']} pixels regrown -> {res['segmentation_dir']}")
+        if "separability" in res:
+            s = res["separability"]
+            worst = (s.get("jm") or {}).get("least_separable")
+            print(f"signatures: {len(s['classes'])} classes"
+                  + (f", least separable {worst['classes']} (JM {worst['value']:.4f})" if worst else "") + f" -> {res['segmentation_dir']}")
         if "metrics_objects" in res:
             m = res["metrics_objects"]
             print(f"evaluation of the object-based map: OA {m['overall_accuracy'] * 100:.2f}%, kappa {m['kappa_coefficient']:.4f} -> "
