@@ -80,6 +80,23 @@ __device__ __forceinline__ void load_pxf(const void *plane, int64_t base, int64_
     }
 }
 
+// Plane f of a FULL tile for the software-pipelined walks (k9_kmeans.hip): always exactly one 16-byte request, on every path.
+// A plane beyond F repeats plane F - 1 — a line the lane has just asked for, never an address outside a plane — and its
+// value is not used.  With `if (f < F)` around a load the compiler cannot count the requests between a load and its first use
+// (the count differs between the paths that meet behind the branch) and waits for ALL outstanding loads, the next tile's
+// included; with a fixed count it waits for the one plane it needs and leaves the later ones in flight.
+// The address is (plane + chunk0), uniform, plus the lane's 32-bit pixel offset inside the chunk: one offset register serves
+// all planes (scalar base + vector offset addressing) instead of a 64-bit address pair per plane.
+template <typename T>
+__device__ __forceinline__ void load_pxq(const planes_t &pl, int F, int f, int64_t chunk0, uint32_t off, T *o)
+{
+    typedef T ntvec __attribute__((ext_vector_type(vt<T>::PXL)));
+    const char *p = reinterpret_cast<const char *>(reinterpret_cast<const T *>(pl.p[f < F ? f : F - 1]) + chunk0);
+    const ntvec v = __builtin_nontemporal_load(reinterpret_cast<const ntvec *>(p + (size_t)(off * (uint32_t)sizeof(T))));
+#pragma unroll
+    for (int i = 0; i < vt<T>::PXL; i++) o[i] = v[i];
+}
+
 template <typename T> __device__ __forceinline__ T scaled(T x, T sc, T mn)
 {
     if (x != x) x = (T)0;  // extract.py:548-556  NaN -> 0

@@ -28,6 +28,34 @@
 #include "k9_kmeans.h"
 
 // ------------------------------------------------------------------------------------------------
+// The software-pipelined tile walk of the register-resident sweeps (km_kpp, km_lloyd; km_moment does the same with two
+// sets of its batches).  Before, a wave asked for the F x 16 B of a tile, waited for all of it, did the whole arithmetic and
+// only then asked again, so its requests came in bursts.  Now the register set ROLLS: as soon as plane f of tile t has been
+// used for the last time (in the feature loop of km_kpp and of the final E-step; in the accumulation loop of the update
+// sweep, which needs the values again behind the argmin), plane f of tile t + 1 is requested into the same registers.  A wave
+// always has most of a tile of reads in flight, and the walk costs no second register set (with one offset register for
+// all planes it needs fewer registers than before).
+// Same arithmetic in the same order per pixel, same partial sums: only the place of the loads moves.
+//   * A tile is requested ahead only if it is a FULL tile of this chunk (km_full_tiles), so no request names an address at
+//     or beyond n; the ragged tile keeps the bounds-checked loads and is never requested ahead.
+//   * The requests are unconditional (load_pxq, k9_kmeans.h): the compiler then knows how many are outstanding behind the
+//     plane it needs and waits for that plane only (s_waitcnt vmcnt(15) ... instead of vmcnt(0)).
+// ------------------------------------------------------------------------------------------------
+// Which instantiations walk this way is decided by their code objects: none may use scratch or lose
+// occupancy.  Every km_kpp form gains or holds; km_lloyd with 64 clusters (one wave per SIMD either way, the rolling form
+// spills) and the final E-step over at most 8 planes (100 -> 134 registers for float32) keep the plain walk.
+template <typename T> constexpr bool lloyd_pipelined(int KMAX, int FR, bool UPDATE) { return KMAX <= 32 && (UPDATE || FR >= 16); }
+template <typename T> constexpr bool kpp_pipelined(int NL, int FR) { return true; }
+// number of full tiles of the chunk that starts at pixel chunk0
+template <typename T> __device__ __forceinline__ int km_full_tiles(int64_t chunk0, int64_t n)
+{
+    const int64_t left = n - chunk0;
+    if (left <= 0) return 0;
+    const int64_t full = left / km_tile<T>();
+    return full < KM_TILES_PER_CHUNK ? (int)full : KM_TILES_PER_CHUNK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // pass A: per-feature min / max (NaN -> 0).  grid (nblk, F); partial[f][blk] = {min, max}
 // ------------------------------------------------------------------------------------------------
 template <typename T>
@@ -75,14 +103,32 @@ __global__ __launch_bounds__(KM_THREADS) void km_moment(planes_t pl, int64_t n, 
     constexpr int UNR = 4;  // vector loads in flight per lane
     const int64_t stride = (int64_t)gridDim.x * KM_THREADS * PXL;
     int64_t base = ((int64_t)blockIdx.x * KM_THREADS + threadIdx.x) * PXL;
-    for (; base + (UNR - 1) * stride + PXL <= n; base += UNR * stride) {
-        T v[UNR][PXL];
+    // software-pipelined: the next batch of UNR vectors is requested before the arithmetic of the current one (two register
+    // sets, rotated by unrolling twice); a batch is requested only if all of it lies below n
+    auto fits = [&](int64_t b) { return b + (UNR - 1) * stride + PXL <= n; };
+    auto request = [&](T (&v)[UNR][PXL], int64_t b) {
 #pragma unroll
-        for (int u = 0; u < UNR; u++) load_pxf<T, true>(pl.p[f], base + u * stride, n, v[u]);
+        for (int u = 0; u < UNR; u++) load_pxf<T, true>(pl.p[f], b + u * stride, n, v[u]);
+    };
+    auto consume = [&](T (&v)[UNR][PXL]) {
 #pragma unroll
         for (int u = 0; u < UNR; u++)
 #pragma unroll
             for (int i = 0; i < PXL; i++) acc += to_fixed40((double)scaled<T>(v[u][i], sc, mnv));
+    };
+    if (fits(base)) {
+        T va[UNR][PXL], vb[UNR][PXL];
+        request(va, base);
+        for (;;) {
+            base += UNR * stride;
+            if (!fits(base)) { consume(va); break; }
+            request(vb, base);
+            consume(va);
+            base += UNR * stride;
+            if (!fits(base)) { consume(vb); break; }
+            request(va, base);
+            consume(vb);
+        }
     }
     for (; base < n; base += stride) {
         T v[PXL];
@@ -125,7 +171,9 @@ __global__ void km_gather_row(planes_t pl, int F, int64_t idx, const scaler_t<T>
 // stable_cumsum, _kmeans.py:243-246): the chosen candidate's min-plane is never stored, the next round
 // re-derives it as its pending update (same arithmetic, same bits) and km_kpp_chunkq does so for the one chunk a
 // sample falls into.  Traffic per round: 4F + 8 B/px (read F planes + closest, write closest).
-// As in km_lloyd the F feature vectors of a lane's pixels are requested back to back into registers.
+// The last round (store = 0) does not write the plane: nothing reads it afterwards, its folded values only enter that
+// round's potentials.  As in km_lloyd the F feature vectors of a lane's pixels live in a rolling register set: plane f of the
+// next full tile is requested as soon as plane f of this one has gone through the feature loop.
 // ------------------------------------------------------------------------------------------------
 #define KPP_MAXL 8
 #define KPP_STRIDE (KPP_MAXL + 1)
@@ -146,10 +194,12 @@ template <typename T> __device__ __forceinline__ T kpp_close(double dot, double 
 template <typename T, int NL, int FR, int MODE>
 __global__ __launch_bounds__(KM_THREADS) void km_kpp(planes_t pl, int F, int64_t n, const scaler_t<T> *__restrict__ sp,
                                                      const double *__restrict__ candT, const double *__restrict__ cc, int L,
-                                                     T *__restrict__ closest, unsigned long long *__restrict__ partial, int64_t nchunks)
+                                                     T *__restrict__ closest, unsigned long long *__restrict__ partial, int64_t nchunks,
+                                                     int store)
 {
     constexpr int PXL = vt<T>::PXL;
     constexpr bool VAR = MODE == 0;
+    constexpr bool PIPE = kpp_pipelined<T>(NL, FR);
     unsigned long long acc[NL];
 #pragma unroll
     for (int l = 0; l < NL; l++) acc[l] = 0;
@@ -157,21 +207,33 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp(planes_t pl, int F, int64_t
 #pragma unroll
     for (int f = 0; f < (VAR ? FR : 1); f++) vacc[f] = 0;
     const int64_t chunk0 = (int64_t)blockIdx.x * km_chunk<T>();
-    auto tile_body = [&](auto full_t, int64_t base) {
+    // request: all planes of a FULL tile (and its closest-distance vector, MODE 2) into the register set.
+    // tile_body, ROLL 0: the tile requests its own planes (bounds-checked unless FULL);
+    //            ROLL 1: its planes are in x / cl or on their way, and plane f of the full tile at offset `noff` is requested as soon
+    //                    as x[f] has been used (cl: behind its last use, at the end);   ROLL 2: as 1, nothing follows.
+    auto request = [&](T (&x)[FR][PXL], T (&cl)[PXL], uint32_t off) {
+#pragma unroll
+        for (int f = 0; f < FR; f++) load_pxq<T>(pl, F, f, chunk0, off, x[f]);
+        if constexpr (MODE == 2) load_pxf<T, true>(closest, chunk0 + off, n, cl);
+    };
+    auto tile_body = [&](auto full_t, auto roll_c, T (&x)[FR][PXL], T (&cl)[PXL], uint32_t off, uint32_t noff) {
+        const int64_t base = chunk0 + off;
         constexpr bool FULL = decltype(full_t)::value;
-        T x[FR][PXL];
+        constexpr int ROLL = decltype(roll_c)::value;
+        static_assert(ROLL == 0 || FULL, "only full tiles are requested ahead");
+        if constexpr (ROLL == 0) {
 #pragma unroll
-        for (int f = 0; f < FR; f++) {
-            if (f < F) load_pxf<T, FULL>(pl.p[f], base, n, x[f]);
-            else {
+            for (int f = 0; f < FR; f++) {
+                if (f < F) load_pxf<T, FULL>(pl.p[f], base, n, x[f]);
+                else {
 #pragma unroll
-                for (int p = 0; p < PXL; p++) x[f][p] = (T)0;
+                    for (int p = 0; p < PXL; p++) x[f][p] = (T)0;
+                }
             }
-        }
-        T cl[PXL];
 #pragma unroll
-        for (int p = 0; p < PXL; p++) cl[p] = (T)0;
-        if constexpr (MODE == 2) load_pxf<T, FULL>(closest, base, n, cl);
+            for (int p = 0; p < PXL; p++) cl[p] = (T)0;
+            if constexpr (MODE == 2) load_pxf<T, FULL>(closest, base, n, cl);
+        }
         double dot[NL][PXL], dotp[PXL], yy[PXL];
 #pragma unroll
         for (int p = 0; p < PXL; p++) {
@@ -202,6 +264,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp(planes_t pl, int F, int64_t
                     for (int l = 0; l < NL; l++) dot[l][p] = fma(cd[l], y, dot[l][p]);
                 }
             }
+            if constexpr (ROLL == 1) load_pxq<T>(pl, F, f, chunk0, noff, x[f]);   // x[f] is free: the next tile's plane f
         }
         if constexpr (MODE != 0) {
             const double ccp = cc[KPP_MAXL];
@@ -215,7 +278,9 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp(planes_t pl, int F, int64_t
                 }
                 cl[p] = dt;
             }
-            if (FULL || base + PXL <= n) {
+            // store == 0 (the last round): nothing reads the plane again, the folded values only enter this round's potentials
+            if (!store) {
+            } else if (FULL || base + PXL <= n) {
                 // the closest-distance plane is rewritten only where it changed (a new centre takes over ~1 / (r + 1) of the pixels
                 // in round r): less of the write stream that costs a sweep ~10 % of its read rate (profiles/r02_streams.json)
                 if (moved) {
@@ -241,13 +306,27 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp(planes_t pl, int F, int64_t
                 }
             }
         }
+        if constexpr (ROLL == 1 && MODE == 2) load_pxf<T, true>(closest, chunk0 + noff, n, cl);
     };
-    for (int t = 0; t < KM_TILES_PER_CHUNK; t++) {
-        const int64_t tbase = chunk0 + (int64_t)t * km_tile<T>();
-        if (tbase >= n) break;
-        const int64_t base = tbase + (int64_t)threadIdx.x * PXL;
-        if (tbase + km_tile<T>() <= n) tile_body(std::true_type{}, base);
-        else tile_body(std::false_type{}, base);
+    T x[FR][PXL], cl[PXL];
+    auto at = [&](int t) { return (uint32_t)(t * km_tile<T>() + (int)threadIdx.x * PXL); };   // pixel offset in the chunk
+    if constexpr (!PIPE) {
+        for (int t = 0; t < KM_TILES_PER_CHUNK; t++) {
+            const int64_t tbase = chunk0 + (int64_t)t * km_tile<T>();
+            if (tbase >= n) break;
+            if (tbase + km_tile<T>() <= n) tile_body(std::true_type{}, ic<0>(), x, cl, at(t), 0);
+            else tile_body(std::false_type{}, ic<0>(), x, cl, at(t), 0);
+        }
+    } else {
+        // the full tiles of the chunk through the rolling register set, then the ragged tile (if any) by itself
+        const int nfull = km_full_tiles<T>(chunk0, n);
+        if (nfull > 0) {
+            request(x, cl, at(0));
+#pragma clang loop unroll(disable)
+            for (int t = 0; t + 1 < nfull; t++) tile_body(std::true_type{}, ic<1>(), x, cl, at(t), at(t + 1));
+            tile_body(std::true_type{}, ic<2>(), x, cl, at(nfull - 1), 0);
+        }
+        if (nfull < KM_TILES_PER_CHUNK && chunk0 + (int64_t)nfull * km_tile<T>() < n) tile_body(std::false_type{}, ic<0>(), x, cl, at(nfull), 0);
     }
     __shared__ unsigned long long sacc[4][NL];
 #pragma unroll
@@ -405,10 +484,13 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp_sample(planes_t pl, int F, 
 // int64: per-cluster fixed-point sums, per-cluster counts, number of changed labels.
 //
 // One workgroup walks one chunk (16 tiles).  Per tile each lane owns PXL consecutive pixels:
-//   load     all F feature vectors of the lane's pixels are requested back to back (F x 16 B per
-//            lane in flight: a wave keeps F KiB of HBM reads outstanding, which is what hides the
-//            latency at the 3 workgroups per CU the register budget allows) and stay in REGISTERS
-//            for the whole tile — the per-cluster accumulation needs them again after the argmin;
+//   load     the F feature vectors of the lane's pixels (F x 16 B per lane) live in REGISTERS for the
+//            whole tile — the per-cluster accumulation needs them again after the argmin.  Only the
+//            chunk's first full tile is requested back to back; after that the set rolls (see the
+//            note on the pipelined walk at the head of this file): plane f of tile t + 1 is
+//            requested where plane f of tile t is used for the last time (phase B in the update
+//            sweep, phase A in the final E-step), through one 32-bit offset register on scalar plane
+//            bases.  A ragged last tile requests its own planes, bounds-checked, when its turn comes;
 //   phase A  scale/centre, accumulate the k dot products (fma chain over f, as sklearn's gemm);
 //   argmin   strict '<' (lowest index wins), label written as uint8;
 //   phase B  the 2^-40 fixed-point images of the lane's values are added to per-cluster 64-bit LDS
@@ -452,15 +534,26 @@ __global__ __launch_bounds__(KM_THREADS) void km_lloyd(planes_t pl, int F, int k
     for (int j = 0; j < KMAX; j++) cs[j] = csq[j];
     const int64_t chunk0 = (int64_t)blockIdx.x * km_chunk<T>();
     int my_changed = 0;
-    auto tile_body = [&](auto full_t, int64_t base) {
+    constexpr bool PIPE = lloyd_pipelined<T>(KMAX, FR, UPDATE);
+    // request / tile_body(ROLL): as in km_kpp.  x[f] is used for the last time in phase A by the final E-step and in phase B
+    // by the update sweep: that is where plane f of the next tile is requested.
+    auto request = [&](T (&x)[FR][PXL], uint32_t off) {
+#pragma unroll
+        for (int f = 0; f < FR; f++) load_pxq<T>(pl, F, f, chunk0, off, x[f]);
+    };
+    auto tile_body = [&](auto full_t, auto roll_c, T (&x)[FR][PXL], uint32_t off, uint32_t noff) {
+        const int64_t base = chunk0 + off;
         constexpr bool FULL = decltype(full_t)::value;
-        T x[FR][PXL];
+        constexpr int ROLL = decltype(roll_c)::value;
+        static_assert(ROLL == 0 || FULL, "only full tiles are requested ahead");
+        if constexpr (ROLL == 0) {
 #pragma unroll
-        for (int f = 0; f < FR; f++) {
-            if (f < F) load_pxf<T, FULL>(pl.p[f], base, n, x[f]);
-            else {
+            for (int f = 0; f < FR; f++) {
+                if (f < F) load_pxf<T, FULL>(pl.p[f], base, n, x[f]);
+                else {
 #pragma unroll
-                for (int p = 0; p < PXL; p++) x[f][p] = (T)0;
+                    for (int p = 0; p < PXL; p++) x[f][p] = (T)0;
+                }
             }
         }
         T acc[KMAX][PXL];
@@ -482,6 +575,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_lloyd(planes_t pl, int F, int k
 #pragma unroll
                     for (int p = 0; p < PXL; p++) acc[j][p] = tfma<T>(x[f][p], cj[j], acc[j][p]);
             }
+            if constexpr (ROLL == 1 && !UPDATE) load_pxq<T>(pl, F, f, chunk0, noff, x[f]);
         }
         // argmin with strict '<' (lowest index wins ties), _k_means_lloyd.pyx:206-213
         int lab[PXL];
@@ -559,15 +653,29 @@ __global__ __launch_bounds__(KM_THREADS) void km_lloyd(planes_t pl, int F, int k
                             if (valid[p]) atomicAdd(&myS[lab[p] * F + f], q[p]);
                     }
                 }
+                if constexpr (ROLL == 1) load_pxq<T>(pl, F, f, chunk0, noff, x[f]);
             }
         }
     };
-    for (int t = 0; t < KM_TILES_PER_CHUNK; t++) {
-        const int64_t tbase = chunk0 + (int64_t)t * TILE;
-        if (tbase >= n) break;
-        const int64_t base = tbase + (int64_t)threadIdx.x * PXL;
-        if (tbase + TILE <= n) tile_body(std::true_type{}, base);
-        else tile_body(std::false_type{}, base);
+    T x[FR][PXL];
+    auto at = [&](int t) { return (uint32_t)(t * TILE + (int)threadIdx.x * PXL); };   // pixel offset in the chunk
+    if constexpr (!PIPE) {
+        for (int t = 0; t < KM_TILES_PER_CHUNK; t++) {
+            const int64_t tbase = chunk0 + (int64_t)t * TILE;
+            if (tbase >= n) break;
+            if (tbase + TILE <= n) tile_body(std::true_type{}, ic<0>(), x, at(t), 0);
+            else tile_body(std::false_type{}, ic<0>(), x, at(t), 0);
+        }
+    } else {
+        // the full tiles of the chunk through the rolling register set, then the ragged tile (if any) by itself
+        const int nfull = km_full_tiles<T>(chunk0, n);
+        if (nfull > 0) {
+            request(x, at(0));
+#pragma clang loop unroll(disable)
+            for (int t = 0; t + 1 < nfull; t++) tile_body(std::true_type{}, ic<1>(), x, at(t), at(t + 1));
+            tile_body(std::true_type{}, ic<2>(), x, at(nfull - 1), 0);
+        }
+        if (nfull < KM_TILES_PER_CHUNK && chunk0 + (int64_t)nfull * TILE < n) tile_body(std::false_type{}, ic<0>(), x, at(nfull), 0);
     }
     if (UPDATE) {
         __shared__ int changed_w[4];
@@ -641,7 +749,8 @@ __global__ __launch_bounds__(KM_THREADS) void km_var(planes_t pl, int64_t n, con
 template <typename T, int NL, int MODE>
 __global__ __launch_bounds__(KM_THREADS) void km_kpp_blk(planes_t pl, int F, int64_t n, const scaler_t<T> *__restrict__ sp,
                                                          const double *__restrict__ candT, const double *__restrict__ cc, int L,
-                                                         T *__restrict__ closest, unsigned long long *__restrict__ partial, int64_t nchunks)
+                                                         T *__restrict__ closest, unsigned long long *__restrict__ partial, int64_t nchunks,
+                                                         int store)
 {
     constexpr int PXL = vt<T>::PXL;
     unsigned long long acc[NL];
@@ -698,7 +807,9 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp_blk(planes_t pl, int F, int
                 }
                 cl[p] = dt;
             }
-            if (FULL || base + PXL <= n) {
+            // store == 0 (the last round): nothing reads the plane again, the folded values only enter this round's potentials
+            if (!store) {
+            } else if (FULL || base + PXL <= n) {
                 // the closest-distance plane is rewritten only where it changed (a new centre takes over ~1 / (r + 1) of the pixels
                 // in round r): less of the write stream that costs a sweep ~10 % of its read rate (profiles/r02_streams.json)
                 if (moved) {
@@ -1561,7 +1672,7 @@ int launch_lloyd(rsseg_ctx *ctx, bool update, int64_t nchunks, size_t lds, plane
 // mode 0: first centre (L == 1, no per-pixel output); 1: first sampling round; 2: later rounds
 template <typename T>
 void launch_kpp(rsseg_ctx *ctx, int64_t nchunks, planes_t pl, int F, int64_t n, const scaler_t<T> *sp, const double *cand, const double *cc,
-                int L, int mode, T *closest, unsigned long long *partial)
+                int L, int mode, bool last, T *closest, unsigned long long *partial)
 {
     auto go = [&](auto nl_c, auto mode_c) {
         constexpr int NL = decltype(nl_c)::value, MODE = decltype(mode_c)::value;
@@ -1569,9 +1680,11 @@ void launch_kpp(rsseg_ctx *ctx, int64_t nchunks, planes_t pl, int F, int64_t n, 
             constexpr int FR = decltype(fr_c)::value;
             const dim3 grid((unsigned)nchunks), block(KM_THREADS);
             if constexpr (FR != KM_BLOCKED) {
-                hipLaunchKernelGGL((km_kpp<T, NL, FR, MODE>), grid, block, 0, ctx->stream, pl, F, n, sp, cand, cc, L, closest, partial, nchunks);
+                hipLaunchKernelGGL((km_kpp<T, NL, FR, MODE>), grid, block, 0, ctx->stream, pl, F, n, sp, cand, cc, L, closest, partial, nchunks,
+                                   last ? 0 : 1);
             } else {   // feature-blocked kernels; the variance rows of the first pass come from km_var
-                hipLaunchKernelGGL((km_kpp_blk<T, NL, MODE>), grid, block, 0, ctx->stream, pl, F, n, sp, cand, cc, L, closest, partial, nchunks);
+                hipLaunchKernelGGL((km_kpp_blk<T, NL, MODE>), grid, block, 0, ctx->stream, pl, F, n, sp, cand, cc, L, closest, partial, nchunks,
+                                   last ? 0 : 1);
                 if constexpr (MODE == 0)
                     hipLaunchKernelGGL((km_var<T>), dim3((unsigned)nchunks, F), block, 0, ctx->stream, pl, n, sp, partial, nchunks);
             }
@@ -1842,7 +1955,7 @@ template <typename T> struct km_fit {
         // first sweep: the potential of the first centre per chunk (row 0) and the np.var numerators (rows 1..F)
         if (n > 0) {
             prof_scope ps(ctx, "kpp");
-            launch_kpp<T>(ctx, nchunks, pl, F, n, d.sp, d.cand, d.cc, 1, 0, d.closest, (unsigned long long *)d.part);
+            launch_kpp<T>(ctx, nchunks, pl, F, n, d.sp, d.cand, d.cc, 1, 0, false, d.closest, (unsigned long long *)d.part);
         }
         HIPCHK(ctx, hipGetLastError());
         // np.var(X, axis=0) and every rank's total of row 0 in ONE all-reduce: x = [F limb pairs][world limb pairs]
@@ -1874,7 +1987,7 @@ template <typename T> struct km_fit {
             hipLaunchKernelGGL((kc_cands<T>), dim3(1), dim3(KM_THREADS), 0, st, d.lst, (const double *)xbuf, d.cand);
             if (n > 0) {
                 prof_scope ps(ctx, "kpp");
-                launch_kpp<T>(ctx, nchunks, pl, F, n, d.sp, d.cand, d.cc, L, c > 1 ? 2 : 1, d.closest, (unsigned long long *)d.part);
+                launch_kpp<T>(ctx, nchunks, pl, F, n, d.sp, d.cand, d.cc, L, c > 1 ? 2 : 1, c == k - 1, d.closest, (unsigned long long *)d.part);
             }
             HIPCHK(ctx, hipGetLastError());
             // potentials of all L candidates with ONE all-reduce: slot [l][rank] = this rank's chunk-sum total
