@@ -638,6 +638,30 @@ int rsseg_segment_majority_u8(rsseg_ctx *ctx, const int32_t *d_seg, int64_t n, i
  * Profiler name "segment_paint". */
 int rsseg_segment_paint(rsseg_ctx *ctx, const int32_t *d_seg, int64_t n, int64_t n_segments, const void *d_table, int elem_bytes, void *d_out);
 
+/* ---- K25: the object table: what describes a segment (no counterpart in the reference) -------- */
+#define RSSEG_OBJ_GEOMETRY 1
+/* d_table (device, int64[(n_segments + 1)][11 + 4 P], 8-byte aligned).  A pixel i is COUNTED for segment s when d_seg[i] == s,
+ * s >= 1 and its d_mask byte (NULL: all) is non-zero; its effective label is s, every other pixel's is 0.
+ * Columns: 0 n; 1, 2 sum y, sum x; 3, 4, 5 sum y^2, sum x^2, sum y x; 6 ... 9 min y, max y, min x, max x; 10 the perimeter:
+ * the number of (counted pixel, side) pairs whose neighbour across that side lies outside the image or has another
+ * effective label (label 0 and masked pixels included, so holes count).  Plane p: columns 11 + 4 p ... 11 + 4 p + 3 = sum q,
+ * sum q2, min q, max q.  RSSEG_U8: q = v, q2 = v v.  RSSEG_F32: q = llrint(v 2^40) (the column of rsseg_segment_sums),
+ * q2 = llrint((double)v (double)v 2^24): the product is exact in float64 and never a tie, one rounding per term.  The caller
+ * keeps float planes free of NaN, |v| < 2^11 and count * max|v| < 2^23 over the counted pixels, as for rsseg_segment_sums.
+ * A row without a counted pixel (row 0 always) holds 0 in the sums, min y = H, max y = -1, min x = W, max x = -1,
+ * min q = INT64_MAX, max q = INT64_MIN.  Without RSSEG_OBJ_GEOMETRY in flags columns 1 ... 10 hold these empty values in
+ * every row (the neighbours are not read); column 0 is always filled.  Integer sums, minima and maxima: one right answer,
+ * restated in tests/objects_ref.py.
+ * RSSEG_ERR_INVALID, naming the argument, before any launch: a null or misaligned pointer, H or W < 1, H W > 2^31 - 1, P < 0,
+ * a wrong dtype, unknown flag bits; and after the pass a label outside 0 ... n_segments (never used as an index).
+ * RSSEG_ERR_UNSUPPORTED: P > 16, or H W max(H, W)^2 >= 2^63 (the coordinate moments would leave int64; 32768^2 is inside).
+ * Whole raster on one GPU.  Synchronous.  Profiler name "segment_features". */
+int rsseg_segment_features(rsseg_ctx *ctx, const int32_t *d_seg, int H, int W, int64_t n_segments, const void *const *d_planes, int P,
+                           int dtype /* RSSEG_U8 | RSSEG_F32 */, const uint8_t *d_mask, int flags /* RSSEG_OBJ_GEOMETRY */, int64_t *d_table);
+/* host-only: the kernel's tile and the rows of its per-tile table in LDS; a tile that meets more segments commits the surplus
+ * straight to d_table (for tests that place segments across the seams and force that path) */
+void rsseg_segment_features_plan(int P, int *tile_w, int *tile_h, int *lds_slots);
+
 /* ---- K24: class signatures: per-label sums of 1, x and x x^T (no counterpart in the reference) -- */
 /* d_out (device, int64[n_classes][1 + F + F (F + 1) / 2], 8-byte aligned): per label the exact integer moments of F
  * feature planes (RSSEG_F32 or RSSEG_U8, band-planar, n_local pixels) over the counted pixels.  One right answer, restated in

@@ -23,6 +23,7 @@ MASK_AND, MASK_OR, MASK_ANDNOT, MASK_NOT = 0, 1, 2, 3
 VALID_NAN, VALID_INF, VALID_VALUE = 1, 2, 4   # rsseg_valid_mask's flags
 WARP_NEAREST, WARP_BILINEAR, WARP_CUBIC = 0, 1, 2
 WARP_MAX_BANDS = 16
+OBJ_GEOMETRY = 1   # rsseg_segment_features' flag
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int)
 
@@ -173,6 +174,8 @@ SIGNATURES = {
     "rsseg_segment_sums": (_int, [_vp, _vp, _int, _int, _i64, _PP, _int, _int, _vp, _vp]),
     "rsseg_segment_majority_u8": (_int, [_vp, _vp, _i64, _i64, _vp, _int, _int, _vp]),
     "rsseg_segment_paint": (_int, [_vp, _vp, _i64, _i64, _vp, _int, _vp]),
+    "rsseg_segment_features": (_int, [_vp, _vp, _int, _int, _i64, _PP, _int, _int, _vp, _int, _vp]),
+    "rsseg_segment_features_plan": (None, [_int, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int)]),
     "rsseg_class_moments": (_int, [_vp, _PP, _int, _int, _i64, _vp, _int, _int, _int, _vp, C.POINTER(_int), _int, _vp, C.POINTER(_i64)]),
     "rsseg_class_moments_plan": (None, [_int, _int, _int, C.POINTER(_int), C.POINTER(_int)]),
     "rsseg_lbp_uniform_u8":(_int, [_vp, _vp, _int, _int, _int, C.c_double, _vp]),

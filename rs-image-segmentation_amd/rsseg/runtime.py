@@ -822,6 +822,31 @@ class Context:
                                                table.element_size(), C.c_void_p(out.data_ptr())))
         return out
 
+    # ---- K25: the object table (rsseg/objects.py) -------------------------------------------------
+    def segment_features_plan(self, P: int = 0) -> Tuple[int, int, int]:
+        """(tile columns, tile rows, rows of the per-tile LDS table) of rsseg_segment_features."""
+        tw, th, ns = C.c_int(0), C.c_int(0), C.c_int(0)
+        self.lib.rsseg_segment_features_plan(int(P), C.byref(tw), C.byref(th), C.byref(ns))
+        return tw.value, th.value, ns.value
+
+    def segment_features(self, seg, H: int, W: int, n_segments: int, planes: Sequence = (), mask=None, geometry: bool = True):
+        """int64 device table [(n_segments + 1), 11 + 4 P] of rsseg_segment_features: n, the coordinate moments, the bounding
+        box and the perimeter (geometry=False leaves columns 1 ... 10 at their empty values), then per plane sum, sum of squares,
+        min and max (uint8 planes as integers, float32 planes in units of 2^-40 and 2^-24).  At most 16 planes of one dtype."""
+        torch = _torch()
+        P = len(planes)
+        u8 = [self._is_u8(p) for p in planes]
+        if any(u8) and not all(u8):
+            raise ValueError("segment_features: uint8 and float32 planes cannot be mixed in one call")
+        if P and not all(u8) and any(p.dtype != torch.float32 for p in planes):
+            raise ValueError("segment_features: planes must be uint8 or float32")
+        cols = 11 + 4 * P
+        out = self.empty((int(n_segments) + 1) * cols, torch.int64)
+        self._chk(self.lib.rsseg_segment_features(self.h, C.c_void_p(seg.data_ptr()), int(H), int(W), int(n_segments), self._pp(planes) if P else None, P,
+                                                  L.U8 if (P == 0 or all(u8)) else L.F32, None if mask is None else C.c_void_p(mask.data_ptr()),
+                                                  L.OBJ_GEOMETRY if geometry else 0, C.c_void_p(out.data_ptr())))
+        return out.reshape(int(n_segments) + 1, cols)
+
     # ---- K9/K10 --------------------------------------------------------------------------------
     def kmeans_fit_predict(self, planes: Sequence, n_clusters: int, seed: int = 42, max_iter: int = 300, tol: float = 1e-4):
         torch = _torch()

@@ -711,12 +711,74 @@ def run_segment_stage(feature_file_path, class_map, output_dir: str, method: str
     return segments, stats, objects
 
 
+OBJECT_FEATURES_FILE = "object_features.npz"
+
+
+def run_object_features_stage(feature_file_path, segments, output_dir: str, method: str, *, labeled_roi_file: str = "labeled_roi.tif",
+                              valid_mask=None, transform=None, crs=None, ctx: Optional[Context] = None):
+    """Object-based supervised classification from object features (rsseg.objects.classify_objects, K25; no counterpart in the
+    reference): every segment of `segments` (run_segment_stage's map) is described by the mean and the standard deviation of
+    the planes run_segment_stage segments (the first 16 of the feature file's (H, W, F) stack, as float32), the segments that
+    hold pixels of the ROI raster train `method` ('random_forest', 'maximum_likelihood', 'mahalanobis' or 'minimum_distance'),
+    every segment is labelled and painted back.  valid_mask: pixels outside it are not counted and stay 0.
+    Writes, beside the raw map's files that stay as they are: <output_dir>/object_features.npz (table, X, columns),
+    classification_<method>_object_features.npy, <method>_classification_map_object_features.tif (uint8, nodata 0, LZW tiles)
+    and an "object_features" entry in segment_stats.json (n_train, classes, columns).
+    Returns (object map, rsseg.objects.ObjectClassification, that entry)."""
+    import json
+    from . import objects as OB
+    from . import segment as SG
+    from .tiff import read_tiff, write_tiff
+    if method not in OB.FOREST_METHODS and method not in OB.GAUSS_METHODS:
+        raise ValueError(f"run_object_features_stage: method {method!r} is not a supervised classifier")
+    feats = _load_normalised(feature_file_path, output_dir)
+    if feats is None:
+        raise ValueError(f"run_object_features_stage: {feature_file_path} holds no feature stack")
+    shape = (int(feats["height"]), int(feats["width"]))
+    arr, names = _supervised_feature_array(feats, True, shape)
+    if arr is None:
+        raise ValueError(f"run_object_features_stage: {feature_file_path} holds no plane of shape {shape}")
+    if tuple(np.asarray(segments).shape) != shape:
+        raise ValueError(f"run_object_features_stage: the segment map is {tuple(np.asarray(segments).shape)}, the features are {shape}")
+    if not os.path.exists(labeled_roi_file):
+        raise FileNotFoundError(f"标签ROI文件未找到: {labeled_roi_file}")
+    roi = read_tiff(labeled_roi_file)
+    roi = roi[0] if roi.ndim == 3 else roi
+    if roi.shape != shape:
+        raise ValueError(f"标签ROI文件 '{labeled_roi_file}' (形状 {roi.shape}) 尺寸与特征数据 (期望的2D形状 {shape}) 不匹配。")
+    if valid_mask is not None:
+        valid_mask = _check_valid_mask(valid_mask, shape)
+    used = min(arr.shape[-1], SG.MAX_PLANES)
+    planes = [np.ascontiguousarray(arr[..., i]) if arr.dtype == np.uint8 else np.ascontiguousarray(arr[..., i], dtype=np.float32) for i in range(used)]
+    of = OB.object_features(segments, planes, names=names[:used], stats=("mean", "std"), shape=False, mask=valid_mask, ctx=ctx)
+    res = OB.classify_objects(segments, planes, roi, method=method, mask=valid_mask, features=of, ctx=ctx)
+    class_map = res.class_map
+    if valid_mask is not None:   # a segment map made under another mask: its pixels outside this one stay 0 all the same
+        class_map = np.where(np.asarray(valid_mask) != 0, class_map, 0).astype(np.uint8)
+    os.makedirs(output_dir, exist_ok=True)
+    np.savez(os.path.join(output_dir, OBJECT_FEATURES_FILE), table=of.table, X=of.X, columns=np.array(of.columns))
+    np.save(os.path.join(output_dir, f"classification_{method}_object_features.npy"), class_map)
+    write_tiff(os.path.join(output_dir, f"{method}_classification_map_object_features.tif"), class_map, transform=transform, epsg=_epsg_of(crs),
+               geographic=_is_geographic(crs), nodata=0, compress="lzw", tiled=True)
+    entry: Dict[str, object] = {"method": method, "n_train": int(res.train_idx.size), "classes": [int(c) for c in np.unique(res.train_y)],
+                                "columns": list(res.columns), "planes_used": int(used)}
+    spath = os.path.join(output_dir, SEGMENT_STATS_FILE)
+    stats = {}
+    if os.path.exists(spath):
+        with open(spath) as f:
+            stats = json.load(f)
+    stats["object_features"] = entry
+    with open(spath, "w") as f:
+        json.dump(stats, f, indent=1)
+    return class_map, res, entry
+
+
 def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters, ctx, evaluate, raw, confidence, importance,
                      kmeans_model: Optional[str] = None, save_kmeans_model: Optional[str] = None, mask_nodata=None, sieve: int = 0,
                      majority: int = 0, majority_iterations: int = 1, gcps=None, warp_order: int = 1, resampling: str = "nearest",
                      pixel_size: Optional[float] = None, ml_threshold: Optional[float] = None, rule_image: bool = False, segment: int = 0,
                      compactness: float = 10.0, segment_iterations: int = 10, object_based: bool = False, signatures: Optional[str] = None,
-                     fit_on_device: bool = False) -> Dict[str, object]:
+                     fit_on_device: bool = False, object_features: bool = False) -> Dict[str, object]:
     """run_scripts_2_3, and with classify='kmeans' the two model options of the command line: `save_kmeans_model` fits as
     always and also writes the fitted model there (KMeansModel.save; the class map is the same file byte for byte),
     `kmeans_model` applies a saved model and fits nothing (run_kmeans_model_stage).
@@ -732,7 +794,9 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
     valid mask; the object-based map is evaluated into <output_dir>/evaluation_results_objects.
     signatures (SIGNATURES_OF_MAP or the path of an ROI raster): run_signatures_stage on the raw class map, or on the ROI's
     training classes, under the same valid mask.  fit_on_device (classify in GAUSS_METHODS): the model is fitted from moments
-    taken on the GPU (GaussianClassifier.fit_image(..., device=True))."""
+    taken on the GPU (GaussianClassifier.fit_image(..., device=True)).
+    object_features (with segment and a supervised classify): run_object_features_stage on the segments, with ./labeled_roi.tif
+    and under the same valid mask; its map is evaluated into <output_dir>/evaluation_results_object_features."""
     valid_mask = None
     if raw:
         from .preprocess import run_preprocessing_stage
@@ -849,6 +913,14 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
                 odir = os.path.join(output_dir, "evaluation_results_objects")
                 res["metrics_objects"], _ = ev.evaluate_maps(res["class_map_objects"], ev.load_roi_mask(evaluate), odir)
                 res["evaluation_dir_objects"] = odir
+            if object_features:
+                res["class_map_object_features"], res["object_classification"], res["object_features_stats"] = run_object_features_stage(
+                    paths["pkl"], res["segments"], sdir, classify, labeled_roi_file="labeled_roi.tif", valid_mask=valid_mask,
+                    transform=geo["transform"], crs=crs, ctx=ctx)
+                if evaluate:
+                    fdir_ = os.path.join(output_dir, "evaluation_results_object_features")
+                    res["metrics_object_features"], _ = ev.evaluate_maps(res["class_map_object_features"], ev.load_roi_mask(evaluate), fdir_)
+                    res["evaluation_dir_object_features"] = fdir_
     return res
 
 
@@ -892,6 +964,8 @@ def parse_args(ap, argv=None):
         ap.error("--segment takes a grid step in 2..4096")
     if (a.object_based or a.compactness is not None or a.segment_iterations is not None) and not a.segment:
         ap.error("--compactness / --segment-iterations / --object-based need --segment")
+    if a.object_features and not (a.segment and a.classify in ("random_forest", *GAUSS_METHODS)):
+        ap.error("--object-features needs --segment and --classify random_forest, maximum_likelihood, mahalanobis or minimum_distance")
     if a.compactness is not None and not (a.compactness >= 0.0 and a.compactness < float("inf")):
         ap.error("--compactness takes a finite non-negative number")
     if a.segment_iterations is not None and a.segment_iterations < 0:
@@ -957,6 +1031,11 @@ def build_parser():
     ap.add_argument("--object-based", action="store_true",
                     help="with --segment: also write the class map voted per superpixel (classification_<method>_objects.npy, "
                          "<method>_classification_map_objects.tif)")
+    ap.add_argument("--object-features", action="store_true",
+                    help="with --segment and a supervised --classify: also describe every superpixel by the mean and spread of its "
+                         "planes, train the classifier on the superpixels under ./labeled_roi.tif and label every superpixel "
+                         "(rsseg.objects) -> object_features.npz, classification_<method>_object_features.npy, "
+                         "<method>_classification_map_object_features.tif")
     from .preprocess import add_gcp_arguments
     add_gcp_arguments(ap)   # with --raw
     return ap
@@ -970,7 +1049,7 @@ def main(argv=None) -> int:
                            gcps=a.gcps, warp_order=a.warp_order, resampling=a.resampling, pixel_size=a.pixel_size, ml_threshold=a.ml_threshold,
                            rule_image=a.rule_image, segment=a.segment, compactness=10.0 if a.compactness is None else a.compactness,
                            segment_iterations=10 if a.segment_iterations is None else a.segment_iterations, object_based=a.object_based,
-                           signatures=a.signatures, fit_on_device=a.fit_on_device)
+                           signatures=a.signatures, fit_on_device=a.fit_on_device, object_features=a.object_features)
     if a.raw:
         print(f"preprocessed: {res['preprocessed']}")
     for k, v in res["paths"].items():
@@ -1001,6 +1080,14 @@ def main(argv=None) -> int:
             m = res["metrics_objects"]
             print(f"evaluation of the object-based map: OA {m['overall_accuracy'] * 100:.2f}%, kappa {m['kappa_coefficient']:.4f} -> "
                   f"{res['evaluation_dir_objects']}")
+        if "object_features_stats" in res:
+            s = res["object_features_stats"]
+            print(f"object features: {len(s['columns'])} columns, {s['n_train']} training superpixels of classes {s['classes']} -> "
+                  f"{res['segmentation_dir']}")
+        if "metrics_object_features" in res:
+            m = res["metrics_object_features"]
+            print(f"evaluation of the object-features map: OA {m['overall_accuracy'] * 100:.2f}%, kappa {m['kappa_coefficient']:.4f} -> "
+                  f"{res['evaluation_dir_object_features']}")
         return 0 if cm is not None else 1
     return 0
 
