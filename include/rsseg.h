@@ -176,7 +176,11 @@ int rsseg_spectral_indices_evi_u8(rsseg_ctx *ctx, const uint8_t *const *d_bands,
  * d_bands[nb]: normalised band planes; center[nb] (float32 medians) and scale[nb] (float64 IQRs)
  * come from K1 + host interpolation; pass center = NULL for no scaling.
  * Outputs (host): components (n_components x nb, row-major, float32), explained_variance_ratio
- * (n_components), mean (nb), explained_variance (n_components). d_out[n_components]: projected planes. */
+ * (n_components), mean (nb), explained_variance (n_components). d_out[n_components]: projected planes.
+ * Value range: the sums are exact in quanta of 2^-Q, Q = min(38, 48 - ceil(log2(bound^2))) with bound the largest
+ * |scaled value| of the fit (1 for normalised bands, measured otherwise).  Q < -19 (bound above about 1e10) is
+ * refused with RSSEG_ERR_UNSUPPORTED: the band sums share the quantum of the squares, and below it the mean is
+ * rounded more coarsely than scikit-learn's float32 steps round it. */
 int rsseg_pca_fit_transform_f32(rsseg_ctx *ctx, const float *const *d_bands, int nb, int64_t n_local,
                                 const float *center, const double *scale, int n_components,
                                 float *const *d_out, float *components, float *explained_variance_ratio,
@@ -780,6 +784,18 @@ int rsseg_host_kmeans_draws(uint32_t seed, int64_t n, int dtype, int k, int64_t 
  * or a negative value (-2: output buffer too small, -3: corrupt stream). */
 int64_t rsseg_host_lzw_encode(const uint8_t *in, int64_t n, uint8_t *out, int64_t cap);
 int64_t rsseg_host_lzw_decode(const uint8_t *in, int64_t n, uint8_t *out, int64_t cap);
+/* The model step of the PCA entry points (K3) on its own: what they compute on the host between the Gram pass and the
+ * projection.  limbs[2 * 44]: the exact sums over the N fitted pixels in quanta of 2^-Q, entry i as the pair
+ * {limbs[2i], limbs[2i + 1]} with value (limbs[2i] << 32) + limbs[2i + 1]; entries 0..7 are the sums of x_b, entry
+ * 8 + 8b - b(b-1)/2 + (c - b) is the sum of x_b * x_c for b <= c < 8 (entries of bands >= nb are not read).
+ * Steps: sum * 2^-Q as a double; scikit-learn's float32 mean and covariance (g - (N * mu_b) * mu_c) / (N - 1); cyclic Jacobi
+ * in float64; eigenvalues in stable descending order, clamped at 0; sign of each component by its first largest |entry|
+ * (svd_flip); offs[c] = the float32 fma chain of mean_b * components[c][b]; ratios = variance / float32 running total.
+ * Outputs (any may be NULL): mean[nb], cov[nb * nb], components[n_components * nb], explained_variance[n_components],
+ * explained_variance_ratio[n_components], offs[n_components].  RSSEG_ERR_INVALID for nb outside 1..8, n_components
+ * outside 1..nb or N < 2. */
+int rsseg_host_pca_model(const int64_t *limbs, int64_t N, int Q, int nb, int n_components, float *mean, float *cov,
+                         float *components, float *explained_variance, float *explained_variance_ratio, float *offs);
 
 #ifdef __cplusplus
 }

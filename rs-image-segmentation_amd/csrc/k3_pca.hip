@@ -17,6 +17,7 @@
 #define PCA_THREADS 256
 #define PCA_MAXB 8
 #define PCA_NACC (PCA_MAXB + PCA_MAXB * (PCA_MAXB + 1) / 2)
+#define PCA_QMIN (-19)  // the coarsest quantum 2^-Q the fit accepts (pca_core)
 #define PCA_PSTRIDE (2 * PCA_NACC + 2)  // long longs per block in the partial table of k3_gram
 
 struct pca_args {
@@ -516,6 +517,75 @@ static void jacobi_eigh(int n, double A[PCA_MAXB][PCA_MAXB], double V[PCA_MAXB][
     for (int i = 0; i < n; i++) w[i] = A[i][i];
 }
 
+// The model step of pca_core, host only (no HIP call): from the exact sums to mean, covariance, components, explained variance,
+// ratios and the projection offsets.  include/rsseg.h describes the arguments.
+extern "C" int rsseg_host_pca_model(const int64_t *limbs, int64_t N, int Q, int nb, int n_components, float *mean, float *cov, float *components,
+                                    float *explained_variance, float *explained_variance_ratio, float *offs)
+{
+    if (!limbs || nb < 1 || nb > PCA_MAXB || n_components < 1 || n_components > nb || N < 2) return RSSEG_ERR_INVALID;
+    typedef __int128 i128;
+    const double inv = std::ldexp(1.0, -Q);
+    auto val = [&](int i) { return (double)((((i128)limbs[2 * i]) << 32) + (i128)limbs[2 * i + 1]) * inv; };
+    // sklearn's float32 steps on exactly accumulated sums
+    float mu[PCA_MAXB];
+    for (int b = 0; b < nb; b++) {
+        volatile float s = (float)val(b);
+        volatile float m = s / (float)N;
+        mu[b] = m;
+    }
+    double Cd[PCA_MAXB][PCA_MAXB];
+    {
+        int t = PCA_MAXB;
+        for (int b = 0; b < PCA_MAXB; b++)
+            for (int c = b; c < PCA_MAXB; c++, t++) {
+                if (b >= nb || c >= nb) continue;
+                volatile float g = (float)val(t);                // X.T @ X
+                volatile float nm = (float)N * mu[b];            // n_samples * mean (column)
+                volatile float nmm = nm * mu[c];                 //   ... * mean (row)
+                volatile float cc = g - nmm;                     // C -= ...
+                volatile float cv = cc / (float)(N - 1);         // C /= n_samples - 1
+                Cd[b][c] = Cd[c][b] = (double)cv;
+                if (cov) cov[b * nb + c] = cov[c * nb + b] = cv;
+            }
+    }
+    double V[PCA_MAXB][PCA_MAXB], w[PCA_MAXB];
+    jacobi_eigh(nb, Cd, V, w);
+    int order[PCA_MAXB];
+    for (int i = 0; i < nb; i++) order[i] = i;
+    std::stable_sort(order, order + nb, [&](int x, int y) { return w[x] > w[y]; });
+    float ev[PCA_MAXB], total = 0.f;
+    for (int i = 0; i < nb; i++) {
+        float e = (float)w[order[i]];
+        ev[i] = e < 0.f ? 0.f : e;
+    }
+    {
+        volatile float t = 0.f;
+        for (int i = 0; i < nb; i++) t = t + ev[i];
+        total = t;
+    }
+    for (int c = 0; c < n_components; c++) {
+        float row[PCA_MAXB];
+        int am = 0;
+        for (int b = 0; b < nb; b++) {
+            row[b] = (float)V[b][order[c]];
+            if (std::fabs(row[b]) > std::fabs(row[am])) am = b;
+        }
+        const float sg = row[am] < 0.f ? -1.f : 1.f;  // svd_flip(u_based_decision=False)
+        volatile float o = 0.f;
+        for (int b = 0; b < nb; b++) {
+            const float cb = row[b] * sg;
+            o = fmaf(mu[b], cb, o);
+            if (components) components[c * nb + b] = cb;
+        }
+        if (offs) offs[c] = o;
+        if (explained_variance) explained_variance[c] = ev[c];
+        if (explained_variance_ratio) explained_variance_ratio[c] = ev[c] / total;
+    }
+    if (mean)
+        for (int b = 0; b < nb; b++) mean[b] = mu[b];
+    return RSSEG_OK;
+}
+
 struct fuse_req {   // non-null: produce the spectral indices (+ normalised bands, + the quantised texture band) in the projection pass
     float *const *d_idx;
     float *const *d_norm;
@@ -677,10 +747,15 @@ static int pca_core(rsseg_ctx *ctx, const void *const *d_bands, bool u8, int nb,
         double c = a.scaled ? (double)a.center[b] : 0.0, s = a.scaled ? a.scale[b] : 1.0;
         bound = std::max(bound, std::max(std::fabs(vmin[b] - c), std::fabs(vmax[b] - c)) / std::fabs(s) * 1.000001);
     }
+    if (!std::isfinite(bound * bound))   // frexp of an infinity leaves the exponent unspecified
+        return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "pca: scaled band range too large for exact accumulation (bound %.3g)", bound);
     int e2;
     std::frexp(bound * bound, &e2);           // bound^2 < 2^e2
     const int Q = std::min(38, 48 - e2);      // |x*x| * 2^Q < 2^48: 4096 pixels per thread stay below 2^60
-    if (Q < -40) return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "pca: scaled band range too large for exact accumulation (bound %.3g)", bound);
+    // The first-moment sums share this quantum: below 2^-19 a pixel's x_b is rounded so coarsely (to 2^-15.5 of the bound) that
+    // the mean, and with it the covariance, ends up farther from the float64 result than scikit-learn's float32 steps
+    // (tests/test_pca_host.py holds the measured table)
+    if (Q < PCA_QMIN) return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "pca: scaled band range too large for exact accumulation (bound %.3g)", bound);
     a.fx_scale = std::ldexp(1.0, Q);
 
     // ---- Gram / mean over the fitted pixels [fit_off, fit_off + fit_n): a scalar head up to the first 16-byte
@@ -736,13 +811,13 @@ static int pca_core(rsseg_ctx *ctx, const void *const *d_bands, bool u8, int nb,
     RSCHK(run_gram(try_tab));
     if (try_tab && pcount && ((const long long *)ctx->h_pin)[2 * PCA_NACC + 1] != 0) RSCHK(run_gram(false));   // some value was not an integer 0..255
     typedef __int128 i128;
-    long long lim[2 * PCA_NACC + 2];
+    int64_t lim[2 * PCA_NACC + 2];
     {
         const long long *hp = (const long long *)ctx->h_pin;
         for (int i = 0; i < PCA_NACC; i++) {
             const i128 s = pcount ? ((i128)hp[2 * i] << 32) + (i128)hp[2 * i + 1] : (i128)0;
-            lim[2 * i] = (long long)(s >> 32);
-            lim[2 * i + 1] = (long long)(s & 0xffffffffLL);
+            lim[2 * i] = (int64_t)(s >> 32);
+            lim[2 * i + 1] = (int64_t)(s & 0xffffffffLL);
         }
         lim[2 * PCA_NACC] = fit_n;
         lim[2 * PCA_NACC + 1] = pcount ? hp[2 * PCA_NACC] : 0;   // (slot 2 * PCA_NACC + 1 of the table: the try-pass's misses, zero here)
@@ -751,64 +826,20 @@ static int pca_core(rsseg_ctx *ctx, const void *const *d_bands, bool u8, int nb,
     if (lim[2 * PCA_NACC + 1] != 0) return rs_fail(ctx, RSSEG_ERR_INVALID, "pca: Input X contains NaN.");
     const int64_t N = lim[2 * PCA_NACC];
     if (N < 2) return rs_fail(ctx, RSSEG_ERR_INVALID, "pca: needs at least 2 samples");
-    const double inv = std::ldexp(1.0, -Q);
-    auto val = [&](int i) { return (double)((((i128)lim[2 * i]) << 32) + (i128)lim[2 * i + 1]) * inv; };
-    // sklearn's float32 steps on exactly accumulated sums
-    float mu[PCA_MAXB];
-    for (int b = 0; b < nb; b++) {
-        volatile float s = (float)val(b);
-        volatile float m = s / (float)N;
-        mu[b] = m;
-    }
-    double Cd[PCA_MAXB][PCA_MAXB];
-    {
-        int t = PCA_MAXB;
-        for (int b = 0; b < PCA_MAXB; b++)
-            for (int c = b; c < PCA_MAXB; c++, t++) {
-                if (b >= nb || c >= nb) continue;
-                volatile float g = (float)val(t);                // X.T @ X
-                volatile float nm = (float)N * mu[b];            // n_samples * mean (column)
-                volatile float nmm = nm * mu[c];                 //   ... * mean (row)
-                volatile float cc = g - nmm;                     // C -= ...
-                volatile float cv = cc / (float)(N - 1);         // C /= n_samples - 1
-                Cd[b][c] = Cd[c][b] = (double)cv;
-            }
-    }
-    double V[PCA_MAXB][PCA_MAXB], w[PCA_MAXB];
-    jacobi_eigh(nb, Cd, V, w);
-    int order[PCA_MAXB];
-    for (int i = 0; i < nb; i++) order[i] = i;
-    std::stable_sort(order, order + nb, [&](int x, int y) { return w[x] > w[y]; });
-    float ev[PCA_MAXB], total = 0.f;
-    for (int i = 0; i < nb; i++) {
-        float e = (float)w[order[i]];
-        ev[i] = e < 0.f ? 0.f : e;
-    }
-    {
-        volatile float t = 0.f;
-        for (int i = 0; i < nb; i++) t = t + ev[i];
-        total = t;
-    }
+    float mu[PCA_MAXB], m_comp[PCA_MAXB * PCA_MAXB], m_ev[PCA_MAXB], m_ratio[PCA_MAXB], m_offs[PCA_MAXB];
+    // nb, n_components and N were checked above: the model step cannot refuse them
+    (void)rsseg_host_pca_model(lim, N, Q, nb, n_components, mu, nullptr, m_comp, m_ev, m_ratio, m_offs);
     proj_args pr;
     memset(&pr, 0, sizeof(pr));
     pr.nc = n_components;
     for (int c = 0; c < n_components; c++) {
-        float row[PCA_MAXB];
-        int am = 0;
         for (int b = 0; b < nb; b++) {
-            row[b] = (float)V[b][order[c]];
-            if (std::fabs(row[b]) > std::fabs(row[am])) am = b;
-        }
-        const float sg = row[am] < 0.f ? -1.f : 1.f;  // svd_flip(u_based_decision=False)
-        volatile float o = 0.f;
-        for (int b = 0; b < nb; b++) {
-            pr.comp[c][b] = row[b] * sg;
-            o = fmaf(mu[b], pr.comp[c][b], o);
+            pr.comp[c][b] = m_comp[c * nb + b];
             if (components) components[c * nb + b] = pr.comp[c][b];
         }
-        pr.offs[c] = o;
-        if (explained_variance) explained_variance[c] = ev[c];
-        if (explained_variance_ratio) explained_variance_ratio[c] = ev[c] / total;
+        pr.offs[c] = m_offs[c];
+        if (explained_variance) explained_variance[c] = m_ev[c];
+        if (explained_variance_ratio) explained_variance_ratio[c] = m_ratio[c];
         if (d_out) {
             if (!d_out[c] || ((uintptr_t)d_out[c] & 15)) return rs_fail(ctx, RSSEG_ERR_INVALID, "pca: output plane %d null or unaligned", c);
             pr.out[c] = d_out[c];

@@ -192,6 +192,8 @@ SIGNATURES = {
     "rsseg_host_lzw_encode": (_i64, [_vp, _i64, _vp, _i64]),
     "rsseg_host_lzw_decode": (_i64, [_vp, _i64, _vp, _i64]),
     "rsseg_host_kmeans_draws": (_int, [C.c_uint32, _i64, _int, _int, C.POINTER(_i64), C.POINTER(C.c_double)]),
+    "rsseg_host_pca_model": (_int, [C.POINTER(_i64), _i64, _int, _int, _int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                    C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 }
 
 _lib = None
