@@ -693,6 +693,42 @@ int rsseg_class_moments(rsseg_ctx *ctx, const void *const *d_planes, int F, int 
  * outside the limits; *tile_pixels = the pixels a workgroup stages at a time.  For the tests that straddle the seams. */
 void rsseg_class_moments_plan(int F, int n_classes, int dtype, int *path, int *tile_pixels);
 
+/* ---- K26: ISODATA: assign to the nearest centre and take the clusters' moments in one pass (no counterpart in the reference) -- */
+/* One ISODATA iteration's pass over F feature planes (RSSEG_F32 or RSSEG_U8, band-planar, n_local pixels) and k centres.  One
+ * right answer, restated in tests/isodata_ref.py; the kernel gives it bit for bit whatever the workgroup count, tile or path.
+ * Counted: the mask byte is non-zero (d_mask NULL: all).
+ * RSSEG_F32: v_f = the plane value, a NaN read as +0; u_f = v_f * 2^plane_exp[f] (exact, in float64); a counted pixel with any
+ * |u_f| > 1 (+-inf included) is LEFT OUT and counted in *n_left_out.  RSSEG_U8: u_f = v_f; plane_exp must be NULL and Q 0;
+ * no pixel is left out.
+ * Per counted pixel that is not left out, in float64 and one IEEE operation per written operation (no fma):
+ *   z_f = u_f * weight[f];
+ *   for j = 0 .. k - 1:  d_j = +0.0;  for f = 0 .. F - 1:  t = z_f - centers[j * F + f];  d_j = d_j + t * t;
+ *   label = the lowest j with the strictly smallest d_j (j = 0 when no d_j is smaller than d_0);
+ *   *n_changed += (label != the byte that was in d_labels);  d_labels = label;
+ *   row `label` of d_table takes
+ *     column 0          += 1
+ *     column 1 + f      += rint(u_f * 2^Q)
+ *     column 1 + F + f  += rint((u_f * 2^Q) * u_f)
+ *   the product exact (two 24-bit significands) and rounded once, to nearest-even: K24's columns (0, 0), (0, 1 + f), (1 + f, 1 + f).
+ * Every other pixel gets label 255, enters no column and is not counted in *n_changed.
+ * d_table NULL: labels, *n_changed and *n_left_out only (the accumulation is not compiled into that kernel).
+ * Limits: 1 <= F <= RSSEG_MAX_FEATURES and 1 <= k <= RSSEG_MAX_CLUSTERS (above: RSSEG_ERR_UNSUPPORTED); 0 <= Q <= 50,
+ * n_local * 2^Q < 2^62, |plane_exp[f]| <= 300, every weight and centre finite; RSSEG_ERR_INVALID, naming the argument, for
+ * these, a null pointer, a plane not aligned to its element or a table not 8-byte aligned.  n_local == 0 writes zeros.
+ * Planes, labels and mask may have any alignment that holds their element.  The result is this context's own: a communication
+ * hook, if installed, reduces nothing (the integers of the stripes of a sharded raster add).  Synchronous.  Profiler name
+ * "isodata_sweep". */
+int rsseg_isodata_sweep(rsseg_ctx *ctx, const void *const *d_planes, int F, int dtype /* RSSEG_F32 | RSSEG_U8 */, int64_t n_local,
+                        const uint8_t *d_mask /* NULL or n_local bytes, 0 = not counted */,
+                        const int *plane_exp /* host, F; NULL for RSSEG_U8 */, int Q,
+                        const double *weight /* host, F */, int k, const double *centers /* host, k * F, in weighted units */,
+                        uint8_t *d_labels /* device, n_local bytes, read and rewritten in place */,
+                        int64_t *d_table /* device int64[k][1 + 2 F], or NULL: labels only */,
+                        int64_t *n_changed, int64_t *n_left_out /* host */);
+/* host-only: *path = 0 when the workgroup keeps its table in LDS (Path A), 1 when it adds into the global table (Path B), -1
+ * outside the limits; *tile_pixels = the pixels a workgroup takes at a time.  For the tests that straddle the seams. */
+void rsseg_isodata_plan(int F, int k, int dtype, int *path, int *tile_pixels);
+
 /* ---- K13: remaining texture members of the feature dictionary ---------------- */
 /* calculate_lbp_features (indices.py:320-344): skimage.feature.local_binary_pattern(u8, n_points, radius, 'uniform');
  * d_out: the codes 0 .. n_points + 1 as uint8 (the caller divides by their maximum in float64, :342). */

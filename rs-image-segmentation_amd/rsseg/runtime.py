@@ -1049,6 +1049,52 @@ class Context:
                                                C.byref(left)))
         return out.reshape(max(int(n_classes), 1), cols), left.value
 
+    # ---- K26: ISODATA (rsseg/isodata.py) ------------------------------------------------------------
+    def isodata_plan(self, F: int, k: int, u8: bool = False) -> Tuple[int, int]:
+        """(path, tile_pixels) of rsseg_isodata_sweep for F planes and k centres: path 0 keeps the workgroup's table in LDS,
+        1 adds into the global table."""
+        path, tile = C.c_int(0), C.c_int(0)
+        self.lib.rsseg_isodata_plan(int(F), int(k), L.U8 if u8 else L.F32, C.byref(path), C.byref(tile))
+        return path.value, tile.value
+
+    def isodata_sweep(self, planes: Sequence, labels, centers, weight, plane_exp, Q: int, mask=None, want_table: bool = True):
+        """rsseg_isodata_sweep (include/rsseg.h) on flat float32 or uint8 device planes: every counted pixel is assigned to the
+        nearest of the centres (k, F), in weighted units; `labels`, a uint8 device plane, is read and rewritten in place
+        (255: not counted or left out).  -> (int64 device table [k, 1 + 2 F] or None when want_table is False, n_changed,
+        n_left_out).  plane_exp: F ints for float32 planes, None for uint8 planes (whose Q is 0); mask: None or a uint8 plane,
+        0 = not counted."""
+        torch = _torch()
+        F = len(planes)
+        if F == 0:
+            raise ValueError("isodata_sweep: no feature planes")
+        dt, n = planes[0].dtype, planes[0].numel()
+        if any(p.dtype != dt or p.numel() != n for p in planes) or dt not in (torch.float32, torch.uint8):
+            raise ValueError("isodata_sweep: planes must all be float32 or all uint8, of one length")
+        if labels.dtype != torch.uint8 or labels.numel() != n:
+            raise ValueError("isodata_sweep: labels must be a uint8 plane of the planes' length")
+        if mask is not None and (mask.dtype != torch.uint8 or mask.numel() != n):
+            raise ValueError("isodata_sweep: mask must be a uint8 plane of the planes' length")
+        centers = np.ascontiguousarray(centers, dtype=np.float64)
+        weight = np.ascontiguousarray(weight, dtype=np.float64).reshape(-1)
+        if centers.ndim != 2 or centers.shape[0] < 1 or centers.shape[1] != F or weight.size != F:
+            raise ValueError(f"isodata_sweep: centers {centers.shape} and {weight.size} weights do not describe k centres over {F} planes")
+        pe = None
+        if plane_exp is not None:
+            pe = np.ascontiguousarray(plane_exp, dtype=np.int32).reshape(-1)
+            if pe.size != F:
+                raise ValueError(f"isodata_sweep: {pe.size} plane exponents for {F} planes")
+        k, cols = centers.shape[0], 1 + 2 * F
+        table = self.empty(k * cols, torch.int64) if want_table else None
+        changed, left = C.c_int64(0), C.c_int64(0)
+        dp = C.POINTER(C.c_double)
+        self._chk(self.lib.rsseg_isodata_sweep(self.h, self._pp(planes), F, L.F32 if dt == torch.float32 else L.U8, n,
+                                               None if mask is None else C.c_void_p(mask.data_ptr()),
+                                               None if pe is None else pe.ctypes.data_as(C.POINTER(C.c_int)), int(Q),
+                                               weight.ctypes.data_as(dp), k, centers.ctypes.data_as(dp),
+                                               C.c_void_p(labels.data_ptr()) if n else None,
+                                               C.c_void_p(table.data_ptr()) if want_table else None, C.byref(changed), C.byref(left)))
+        return (table.reshape(k, cols) if want_table else None), changed.value, left.value
+
     # ---- K11 -----------------------------------------------------------------------------------
     def forest_load(self, forest: dict):
         f = forest

@@ -773,12 +773,88 @@ def run_object_features_stage(feature_file_path, segments, output_dir: str, meth
     return class_map, res, entry
 
 
+ISODATA_HISTORY_FILE = "isodata_history.json"
+ISODATA_DEFAULTS = dict(init_clusters=None, max_std=0.06, min_dist=0.1, min_size=None, iterations=20, change=0.0)
+
+
+def isodata_planes(feats, feature_keys=None):
+    """The planes run_isodata_stage clusters -> (list of (H, W) planes, all uint8 or all float32, their names): the (H, W, F)
+    stack the Gaussian methods, SLIC and the signatures read (hierarchical_all, else every 2-D plane), or, with feature_keys,
+    those entries of the feature dictionary (2-D planes, 3-D stacks plane by plane)."""
+    shape = (int(feats["height"]), int(feats["width"]))
+    if feature_keys is None:
+        arr, names = _supervised_feature_array(feats, True, shape)
+        if arr is None:
+            return None, []
+        planes = [arr[..., i] for i in range(arr.shape[-1])]
+    else:
+        planes, names = [], []
+        for k in feature_keys:
+            v = feats.get(k)
+            if not isinstance(v, np.ndarray) or v.ndim not in (2, 3) or v.shape[:2] != shape:
+                raise ValueError(f"run_isodata_stage: feature {k!r} is not a plane or a stack of shape {shape}")
+            if v.ndim == 2:
+                planes.append(v)
+                names.append(str(k))
+            else:
+                planes += [v[..., i] for i in range(v.shape[-1])]
+                names += [f"{k}_{i + 1}" for i in range(v.shape[-1])]
+    dt = np.uint8 if all(p.dtype == np.uint8 for p in planes) else np.float32
+    return [np.ascontiguousarray(p, dtype=dt) for p in planes], names
+
+
+def run_isodata_stage(feature_file_path, output_dir="segmentation_outputs", *, n_clusters: int = 7, init_clusters: Optional[int] = None,
+                      max_std: float = 0.06, min_dist: float = 0.1, min_size: Optional[int] = None, iterations: int = 20,
+                      change: float = 0.0, model_path: Optional[str] = None, feature_keys=None, valid_mask=None,
+                      ctx: Optional[Context] = None) -> Optional[np.ndarray]:
+    """ISODATA clustering of the feature stack (rsseg.isodata, K26; no counterpart in the reference): n_clusters is the number
+    aimed at (k_target), the other parameters are rsseg.isodata.isodata's.  model_path: a saved model (IsodataModel.save) is
+    applied and nothing is fitted, so that the cluster ids of this map are those of every other map of the model.
+    valid_mask ((H, W), non-zero = valid): only the valid pixels are clustered; the class map is 0 at the others.
+    Writes <output_dir>/classification_isodata.npy (labels + 1 as uint8, 0 = nodata, the k-means layout),
+    isodata_classification_map.tif with complete metadata, isodata_model.npz and isodata_history.json (the parameters, the
+    per-iteration history, the pixels per cluster, n_left_out).  Returns the class map."""
+    import json
+    from . import isodata as ISO
+    feats = _load_normalised(feature_file_path, output_dir)
+    if feats is None:
+        return None
+    shape = (int(feats["height"]), int(feats["width"]))
+    planes, names = isodata_planes(feats, feature_keys)
+    if planes is None:
+        return None
+    if valid_mask is not None:
+        valid_mask = _check_valid_mask(valid_mask, shape)
+    if model_path:
+        model = ISO.IsodataModel.load(model_path)
+        if model.feature_names is not None and model.feature_names != list(names):
+            raise ValueError(f"IsodataModel: the model was fitted on {model.feature_names}, the feature file offers {list(names)}")
+        labels = model.predict(planes, mask=valid_mask, ctx=ctx)
+        counts = np.bincount(labels.reshape(-1), minlength=256)[:model.n_clusters]
+        record = {"model": os.path.basename(str(model_path)), "fitted": False, "history": [], "n_left_out": int((labels == ISO.NO_LABEL).sum())
+                  - (0 if valid_mask is None else int((np.asarray(valid_mask) == 0).sum()))}
+    else:
+        res = ISO.isodata(planes, k_target=n_clusters, k_init=init_clusters, min_size=min_size, max_std=max_std, min_dist=min_dist,
+                          max_iter=iterations, change=change, mask=valid_mask, feature_names=names, ctx=ctx)
+        model, labels, counts = res.model, res.labels, res.counts
+        record = {"fitted": True, "history": res.history, "n_left_out": int(res.n_left_out)}
+    out = np.where(labels == ISO.NO_LABEL, 0, labels.astype(np.int32) + 1).astype(np.uint8).reshape(shape)
+    np.save(os.path.join(output_dir, "classification_isodata.npy"), out)
+    _save_class_tif(out, feats, output_dir, "isodata")
+    model.save(os.path.join(output_dir, "isodata_model.npz"))
+    with open(os.path.join(output_dir, ISODATA_HISTORY_FILE), "w") as f:
+        json.dump({"k_target": int(n_clusters), "init_clusters": init_clusters, "max_std": max_std, "min_dist": min_dist, "min_size": min_size,
+                   "iterations": int(iterations), "change": change, "n_clusters": int(model.n_clusters), "feature_names": list(names),
+                   "counts": [int(c) for c in counts], **record}, f, indent=1)
+    return out
+
+
 def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters, ctx, evaluate, raw, confidence, importance,
                      kmeans_model: Optional[str] = None, save_kmeans_model: Optional[str] = None, mask_nodata=None, sieve: int = 0,
                      majority: int = 0, majority_iterations: int = 1, gcps=None, warp_order: int = 1, resampling: str = "nearest",
                      pixel_size: Optional[float] = None, ml_threshold: Optional[float] = None, rule_image: bool = False, segment: int = 0,
                      compactness: float = 10.0, segment_iterations: int = 10, object_based: bool = False, signatures: Optional[str] = None,
-                     fit_on_device: bool = False, object_features: bool = False) -> Dict[str, object]:
+                     fit_on_device: bool = False, object_features: bool = False, isodata: Optional[Dict[str, object]] = None) -> Dict[str, object]:
     """run_scripts_2_3, and with classify='kmeans' the two model options of the command line: `save_kmeans_model` fits as
     always and also writes the fitted model there (KMeansModel.save; the class map is the same file byte for byte),
     `kmeans_model` applies a saved model and fits nothing (run_kmeans_model_stage).
@@ -796,7 +872,9 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
     training classes, under the same valid mask.  fit_on_device (classify in GAUSS_METHODS): the model is fitted from moments
     taken on the GPU (GaussianClassifier.fit_image(..., device=True)).
     object_features (with segment and a supervised classify): run_object_features_stage on the segments, with ./labeled_roi.tif
-    and under the same valid mask; its map is evaluated into <output_dir>/evaluation_results_object_features."""
+    and under the same valid mask; its map is evaluated into <output_dir>/evaluation_results_object_features.
+    isodata (classify='isodata'): run_isodata_stage's keyword arguments beside n_clusters (init_clusters, max_std, min_dist, min_size,
+    iterations, change, model_path); the valid mask goes to the sweep as it is."""
     valid_mask = None
     if raw:
         from .preprocess import run_preprocessing_stage
@@ -847,7 +925,10 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
     if valid_mask is not None:
         res["valid_mask_path"] = os.path.join(fdir, "valid_mask.npy")
         np.save(res["valid_mask_path"], valid_mask)
-    if classify and valid_mask is not None:
+    if classify == "isodata":
+        sdir = os.path.join(output_dir, "segmentation_results")
+        res["class_map"] = run_isodata_stage(paths["pkl"], sdir, n_clusters=n_clusters, valid_mask=valid_mask, ctx=ctx, **(isodata or {}))
+    elif classify and valid_mask is not None:
         sdir = os.path.join(output_dir, "segmentation_results")
         if classify in GAUSS_METHODS:
             res["class_map"] = _run_classification(paths["pkl"], classify, sdir, True, n_clusters, None, None, "labeled_roi.tif", False, ctx,
@@ -936,6 +1017,23 @@ def parse_args(ap, argv=None):
         ap.error("--kmeans-model / --save-kmeans-model need --classify kmeans")
     if a.kmeans_model and a.save_kmeans_model:
         ap.error("--kmeans-model applies a saved model and fits nothing: it does not go with --save-kmeans-model")
+    iso_given = [f"--isodata-{k.replace('_', '-')}" for k in ISODATA_DEFAULTS if getattr(a, f"isodata_{k}") is not None] + (
+        ["--isodata-model"] if a.isodata_model else [])
+    if iso_given and a.classify != "isodata":
+        ap.error(f"{' / '.join(iso_given)} need --classify isodata")
+    if a.classify == "isodata":
+        if not 1 <= a.n_clusters <= 64:
+            ap.error("--classify isodata takes --n-clusters in 1..64")
+        if a.isodata_init_clusters is not None and not 1 <= a.isodata_init_clusters <= 64:
+            ap.error("--isodata-init-clusters takes a count in 1..64")
+        if a.isodata_min_size is not None and a.isodata_min_size < 1:
+            ap.error("--isodata-min-size takes a positive pixel count")
+        if a.isodata_iterations is not None and a.isodata_iterations < 1:
+            ap.error("--isodata-iterations takes a positive count")
+        for k in ("max_std", "min_dist", "change"):
+            v = getattr(a, f"isodata_{k}")
+            if v is not None and not (v >= 0.0 and v < float("inf")):
+                ap.error(f"--isodata-{k.replace('_', '-')} takes a finite non-negative number")
     if (a.ml_threshold is not None or a.rule_image) and a.classify not in GAUSS_METHODS:
         ap.error("--ml-threshold / --rule-image need --classify maximum_likelihood, mahalanobis or minimum_distance")
     if a.ml_threshold is not None and not (0.0 < a.ml_threshold < 1.0):
@@ -979,7 +1077,7 @@ def build_parser():
                                  description="feature extraction (scripts/2) and optionally classification (scripts/3) of one GeoTIFF on the GPU")
     ap.add_argument("image")
     ap.add_argument("output_dir")
-    ap.add_argument("--classify", choices=["kmeans", "rule_based", "random_forest", *GAUSS_METHODS])
+    ap.add_argument("--classify", choices=["kmeans", "isodata", "rule_based", "random_forest", *GAUSS_METHODS])
     ap.add_argument("--n-clusters", type=int, default=7)
     ap.add_argument("--no-preprocessing", action="store_true")
     ap.add_argument("--evaluate", metavar="ROI_MASK", help="accuracy assessment (scripts/4) of the class map against this ROI mask (.npy / .tif)")
@@ -1036,6 +1134,19 @@ def build_parser():
                          "planes, train the classifier on the superpixels under ./labeled_roi.tif and label every superpixel "
                          "(rsseg.objects) -> object_features.npz, classification_<method>_object_features.npy, "
                          "<method>_classification_map_object_features.tif")
+    ap.add_argument("--isodata-init-clusters", type=int, default=None, metavar="K",
+                    help="with --classify isodata (--n-clusters is the number aimed at): the initial number of clusters (default --n-clusters)")
+    ap.add_argument("--isodata-max-std", type=float, default=None, metavar="S",
+                    help="with --classify isodata: a cluster wider than S along a plane, in units of the plane's range, may be split (default 0.06)")
+    ap.add_argument("--isodata-min-dist", type=float, default=None, metavar="D",
+                    help="with --classify isodata: two clusters closer than D, in units of a plane's range, may be merged (default 0.1)")
+    ap.add_argument("--isodata-min-size", type=int, default=None, metavar="N",
+                    help="with --classify isodata: a cluster of fewer than N pixels is dropped (default: a thousandth of the valid pixels)")
+    ap.add_argument("--isodata-iterations", type=int, default=None, metavar="N", help="with --classify isodata: at most N iterations (default 20)")
+    ap.add_argument("--isodata-change", type=float, default=None, metavar="FRACTION",
+                    help="with --classify isodata: stop once at most this fraction of the pixels changes cluster (default 0)")
+    ap.add_argument("--isodata-model", metavar="PATH",
+                    help="with --classify isodata: apply this saved model (isodata_model.npz of an earlier run) instead of fitting")
     from .preprocess import add_gcp_arguments
     add_gcp_arguments(ap)   # with --raw
     return ap
@@ -1044,12 +1155,16 @@ def build_parser():
 def main(argv=None) -> int:
     ap = build_parser()
     a = parse_args(ap, argv)
+    iso = None
+    if a.classify == "isodata":
+        iso = {k: (d if getattr(a, f"isodata_{k}") is None else getattr(a, f"isodata_{k}")) for k, d in ISODATA_DEFAULTS.items()}
+        iso["model_path"] = a.isodata_model
     res = _run_scripts_2_3(a.image, a.output_dir, a.classify, not a.no_preprocessing, a.n_clusters, None, a.evaluate, a.raw, a.confidence,
                            a.importance, a.kmeans_model, a.save_kmeans_model, a.mask_nodata, a.sieve, a.majority, a.majority_iterations,
                            gcps=a.gcps, warp_order=a.warp_order, resampling=a.resampling, pixel_size=a.pixel_size, ml_threshold=a.ml_threshold,
                            rule_image=a.rule_image, segment=a.segment, compactness=10.0 if a.compactness is None else a.compactness,
                            segment_iterations=10 if a.segment_iterations is None else a.segment_iterations, object_based=a.object_based,
-                           signatures=a.signatures, fit_on_device=a.fit_on_device, object_features=a.object_features)
+                           signatures=a.signatures, fit_on_device=a.fit_on_device, object_features=a.object_features, isodata=iso)
     if a.raw:
         print(f"preprocessed: {res['preprocessed']}")
     for k, v in res["paths"].items():
