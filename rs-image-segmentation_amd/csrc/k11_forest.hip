@@ -23,7 +23,7 @@
 // leave room for tree nodes: the reference's non-hierarchical forest branch stacks every 2-D plane of the feature
 // dictionary, scripts/3_classification.py:425-437).
 //
-// Two kernels:
+// Two kernels, both written out in this file:
 //   k11_forest_lds   trees are taken in groups of <= 4 consecutive trees whose nodes (contiguous in the node array) fit
 //                    the LDS beside the features; the whole group is copied with 16-byte loads (prefetched into
 //                    registers during the walk of the previous group) and every step is two ds_reads.  Measured
@@ -32,12 +32,14 @@
 //                    tree step.
 //   k11_forest_gen   any forest: the first ntop nodes of each of 4 trees in LDS, deeper nodes by global loads.
 // Algorithmic HBM traffic is 4F B/px in + 8 B/px out; the kernel's bound is VALU issue, reported as node visits / s.
+// The host side of all four entry points (launch plan, dispatch over (row width, threads), plane checks) is in
+// k11_forest.h as well; rsseg_forest_load, below, builds the layout and the group plan.
 #include <algorithm>
 #include <cmath>
 #include <queue>
 
 #include "common.h"
-#include "k11_forest.h"   // node layout, vote rows, the walks: shared with k11_forest_proba.hip
+#include "k11_forest.h"   // node layout, vote rows, the walks, the launch path: shared with k11_forest_proba.hip, k11_forest_perm.hip
 
 template <int NC>
 __device__ __forceinline__ void rf_finish(const double (&acc)[NC], int n_trees, int n_classes, const long long *__restrict__ classes,
@@ -54,6 +56,10 @@ __device__ __forceinline__ void rf_finish(const double (&acc)[NC], int n_trees, 
     out[i] = classes[best];
 }
 
+// k11_forest_lds keeps its LDS-group body WRITTEN OUT, as the parent had it: as a policy on a shared __forceinline__ body it computed
+// the same values, but two of its 18 instantiations took more scratch memory than the parent's.  The three LDS-group kernels (here, k11_forest_proba.hip,
+// k11_forest_perm.hip) share the walks, the vote rows, RF_PRE / RF_PUT and the launch path of k11_forest.h; a change to the
+// steps of one body is made in the other two as well.
 template <int NC, int RF_TH>
 __global__ __launch_bounds__(RF_TH) void k11_forest_lds(rf_planes pl, int F, int64_t n, const rf_node *__restrict__ nodes,
                                                         const rf_tree *__restrict__ trees, const rf_group *__restrict__ groups, int n_groups,
@@ -61,35 +67,37 @@ __global__ __launch_bounds__(RF_TH) void k11_forest_lds(rf_planes pl, int F, int
                                                         const double *__restrict__ leafval,
                                                         int n_classes, const long long *__restrict__ classes, long long *__restrict__ out)
 {
-    constexpr int RF_LT = RF_TH / RF_PX;
+    // One pixel per thread (the PX of the first versions is gone from the header and the other kernels), spelled here as
+    // loops of PX = 1 pixel and LT threads: the compiler folds them away, but with this spelling the two widest
+    // instantiations keep the parent's 104 B of scratch memory; written flat, as in k11_forest_out_lds, they take 108.
+    constexpr int PX = 1, LT = RF_TH, NCH = PX * RF_C;
     extern __shared__ __align__(16) char smem[];
     const int FP = F | 1;                                                      // odd row length: the fills below hit 64 distinct banks
     float *feat = reinterpret_cast<float *>(smem);                             // [RF_TH pixels][FP]
     uint4 *top = reinterpret_cast<uint4 *>(feat + (size_t)FP * RF_TH);         // the current group's nodes, two per uint4
-    const int64_t i0 = (int64_t)blockIdx.x * RF_TH + threadIdx.x;             // pixel p of the thread: i0 + p * RF_LT
+    const int64_t i0 = (int64_t)blockIdx.x * RF_TH + threadIdx.x;             // pixel p of the thread: i0 + p * LT
     int my_nan = 0;
     for (int f = 0; f < F; f++)
 #pragma unroll
-        for (int p = 0; p < RF_PX; p++) {
-            const int64_t i = i0 + p * RF_LT;
+        for (int p = 0; p < PX; p++) {
+            const int64_t i = i0 + p * LT;
             const float v = i < n ? pl.p[f][i] : 0.f;
             my_nan |= v != v;
-            feat[(p * RF_LT + threadIdx.x) * FP + f] = v;
+            feat[(p * LT + threadIdx.x) * FP + f] = v;
         }
     {
         const rf_group g0 = groups[0];
         const uint4 *src = reinterpret_cast<const uint4 *>(nodes + g0.node_base);
-        for (int j = threadIdx.x; j < (g0.n_nodes + 1) / 2; j += RF_LT) top[j] = src[j];
+        for (int j = threadIdx.x; j < (g0.n_nodes + 1) / 2; j += LT) top[j] = src[j];
         // a fixed-point leaf behind the node area for the unused chains of a group with fewer than RF_C trees
         if (threadIdx.x == 0) top[cap2] = make_uint4(RF_NAN_BITS, RF_LEAF | RF_MISS, RF_NAN_BITS, RF_LEAF | RF_MISS);
     }
     const bool any_nan = __syncthreads_or(my_nan) != 0;  // workgroup-uniform; also the barrier behind the fills above
     const unsigned feat_tid = (unsigned)(uintptr_t)(lds_cfloat *)feat + threadIdx.x * (unsigned)FP * 4u;
-    const unsigned px_stride = (unsigned)RF_LT * (unsigned)FP * 4u;
     const unsigned top_addr = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const uint4 *)top;
-    double acc[RF_PX][NC];
+    double acc[PX][NC];
 #pragma unroll
-    for (int p = 0; p < RF_PX; p++)
+    for (int p = 0; p < PX; p++)
 #pragma unroll
         for (int c = 0; c < NC; c++) acc[p][c] = 0.0;
     for (int g = 0; g < n_groups; g++) {
@@ -103,10 +111,8 @@ __global__ __launch_bounds__(RF_TH) void k11_forest_lds(rf_planes pl, int F, int
         const int npiece = more ? (gn.n_nodes + 1) / 2 : 0;
         const uint4 *psrc = reinterpret_cast<const uint4 *>(nodes + gn.node_base);
         const int plast = (gn.n_nodes + 1) / 2 - 1;
-#define RF_PRE(r) const uint4 pre##r = psrc[(int)threadIdx.x + r * RF_LT < plast ? (int)threadIdx.x + r * RF_LT : plast];
         RF_PRE(0) RF_PRE(1) RF_PRE(2) RF_PRE(3) RF_PRE(4) RF_PRE(5)
-#undef RF_PRE
-        rf_node nd[RF_NCH];
+        rf_node nd[NCH];
         unsigned base[RF_C];
 #pragma unroll
         for (int c = 0; c < RF_C; c++) {
@@ -114,36 +120,34 @@ __global__ __launch_bounds__(RF_TH) void k11_forest_lds(rf_planes pl, int F, int
             base[c] = c < gr.count ? top_addr + (unsigned)(tr.node_off - gr.node_base) * 8u : top_addr + (unsigned)cap2 * 16u;
             lds_cnode *p = RF_LDS_PTR(lds_cnode, base[c]);
 #pragma unroll
-            for (int px = 0; px < RF_PX; px++) {   // lanes without a pixel walk their zero features (no special case in the loop)
+            for (int px = 0; px < PX; px++) {   // lanes without a pixel walk their zero features (no special case in the loop)
                 nd[px * RF_C + c].thr = p->thr;
                 nd[px * RF_C + c].bits = p->bits;
             }
         }
-        if (any_nan) rf_walk_lds<true>(nd, feat_tid, px_stride, base, two_rounds != 0);
-        else rf_walk_lds<false>(nd, feat_tid, px_stride, base, two_rounds != 0);
+        if (any_nan) rf_walk_lds<true>(nd, feat_tid, base, two_rounds != 0);
+        else rf_walk_lds<false>(nd, feat_tid, base, two_rounds != 0);
         // refill first (frees the prefetch registers: holding them AND the vote rows spilled 96 bytes per lane to scratch
         // memory, 800 B/px of extra HBM writes), then request the vote rows of all chains at once; the second barrier and
         // the next group's set-up cover most of the gather latency, and the rows are added in tree order behind it
         constexpr bool PIPE = NC <= 8;
-        double rows[PIPE ? RF_NCH : 1][NC];
+        double rows[PIPE ? NCH : 1][NC];
         if (PIPE) {
 #pragma unroll
-            for (int q = 0; q < RF_NCH; q++) rf_row_load<NC>(nd[q], leafval, rows[PIPE ? q : 0]);
+            for (int q = 0; q < NCH; q++) rf_row_load<NC>(nd[q], leafval, rows[PIPE ? q : 0]);
         } else {
 #pragma unroll
-            for (int q = 0; q < RF_NCH; q++)
-                if (q % RF_C < gr.count && i0 + (q / RF_C) * RF_LT < n) rf_vote<NC>(nd[q], leafval, acc[q / RF_C]);
+            for (int q = 0; q < NCH; q++)
+                if (q % RF_C < gr.count && i0 + (q / RF_C) * LT < n) rf_vote<NC>(nd[q], leafval, acc[q / RF_C]);
         }
         if (more) {
             __syncthreads();  // every wave is done with the current group
-#define RF_PUT(r) if ((int)threadIdx.x + r * RF_LT < npiece) top[threadIdx.x + r * RF_LT] = pre##r;
             RF_PUT(0) RF_PUT(1) RF_PUT(2) RF_PUT(3) RF_PUT(4) RF_PUT(5)
-#undef RF_PUT
         }
         if (more) __syncthreads();
         if (PIPE) {
 #pragma unroll
-            for (int q = 0; q < RF_NCH; q++)
+            for (int q = 0; q < NCH; q++)
                 if (q % RF_C < gr.count) {
 #pragma unroll
                     for (int c = 0; c < NC; c++) acc[q / RF_C][c] += rows[PIPE ? q : 0][c];
@@ -151,10 +155,13 @@ __global__ __launch_bounds__(RF_TH) void k11_forest_lds(rf_planes pl, int F, int
         }
     }
 #pragma unroll
-    for (int px = 0; px < RF_PX; px++)
-        if (i0 + px * RF_LT < n) rf_finish<NC>(acc[px], n_trees, n_classes, classes, out, i0 + px * RF_LT);
+    for (int px = 0; px < PX; px++)
+        if (i0 + px * LT < n) rf_finish<NC>(acc[px], n_trees, n_classes, classes, out, i0 + px * LT);
 }
 
+// the general kernel, written out like the LDS-group one above: a body shared with the other two outputs did not keep
+// their speed, and a shared body of one user is no sharing; a change to its steps is made in the other
+// two files as well
 template <int NC, int RF_TH>
 __global__ __launch_bounds__(RF_TH) void k11_forest_gen(rf_planes pl, int F, int64_t n, const rf_node *__restrict__ nodes,
                                                         const rf_tree *__restrict__ trees, int n_trees, int ntop,
@@ -261,7 +268,7 @@ extern "C" int rsseg_forest_load(rsseg_ctx *ctx, int n_trees, const int64_t *tre
     const int64_t nn = tree_off[n_trees];
     if (nn < n_trees || nn > 0x7ffffff0) return rs_fail(ctx, RSSEG_ERR_INVALID, "forest_load: bad node count %lld", (long long)nn);
     std::vector<rf_node> nodes((size_t)nn);
-    const int NCP = n_classes <= 4 ? 4 : (n_classes <= 8 ? 8 : (n_classes <= 16 ? 16 : (n_classes <= 32 ? 32 : 64)));  // row length of the vote table
+    const int NCP = rf_row_width(n_classes);  // row length of the vote table
     std::vector<double> leaf((size_t)n_classes * NCP, 0.0);
     for (int c = 0; c < n_classes; c++) leaf[(size_t)c * NCP + c] = 1.0;
     std::vector<rf_tree> trees(n_trees);
@@ -392,73 +399,15 @@ extern "C" int rsseg_forest_load(rsseg_ctx *ctx, int n_trees, const int64_t *tre
 extern "C" int rsseg_forest_predict(rsseg_ctx *ctx, const float *const *d_planes, int F, int64_t n, int64_t *d_out)
 {
     if (!ctx) return RSSEG_ERR_INVALID;
-    forest_dev &fd = ctx->forest;
-    if (!fd.d_nodes) return rs_fail(ctx, RSSEG_ERR_INVALID, "forest_predict: no forest loaded");
-    if (!d_planes || !d_out || n < 0) return rs_fail(ctx, RSSEG_ERR_INVALID, "forest_predict: bad arguments");
-    if (F != fd.n_features)
-        return rs_fail(ctx, RSSEG_ERR_INVALID, "forest_predict: X has %d features, but the forest is expecting %d features as input", F, fd.n_features);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     rf_planes pl;
-    memset(&pl, 0, sizeof(pl));
-    for (int f = 0; f < F; f++) {
-        if (!d_planes[f]) return rs_fail(ctx, RSSEG_ERR_INVALID, "forest_predict: plane %d is null", f);
-        pl.p[f] = d_planes[f];
-    }
+    RSCHK(rf_check_planes(ctx, "forest_predict", d_planes, d_out && n >= 0, F, pl));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     if (n == 0) return RSSEG_OK;
-    const long long *d_classes = (const long long *)fd.d_treeoff;
-    const rf_tree *d_trees = (const rf_tree *)((const char *)fd.d_treeoff + fd.n_classes * sizeof(long long));
-    const int TH = rf_threads(F, fd.n_classes);
-    const unsigned grid = (unsigned)ceil_div64(n, TH);
-    int rc;
-    if (fd.n_groups > 0) {
-        // every group of trees fits the LDS: features TH * (F | 1) * 4 B + cap nodes + the dummy leaf
-        const int cap = rf_lds_cap(F, TH);
-        const size_t lds = (size_t)(F | 1) * TH * 4 + (size_t)cap * sizeof(rf_node) + 16;
-        auto launch = [&](auto kern) -> int {
-            RSCHK(set_max_dyn_lds(ctx, (const void *)kern, lds));
-            prof_scope ps(ctx, "forest");
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(TH / RF_PX), lds, ctx->stream, pl, F, n, (const rf_node *)fd.d_nodes, d_trees,
-                               (const rf_group *)fd.d_groups, fd.n_groups, cap / 2, fd.max_depth >= 10 ? 1 : 0, fd.n_trees, (const double *)fd.d_leafval, fd.n_classes, d_classes,
-                               (long long *)d_out);
-            return RSSEG_OK;
-        };
-        if (TH == 1024) {
-            if (fd.n_classes <= 4) rc = launch(k11_forest_lds<4, 1024>);
-            else if (fd.n_classes <= 8) rc = launch(k11_forest_lds<8, 1024>);
-            else if (fd.n_classes <= 16) rc = launch(k11_forest_lds<16, 1024>);
-            else rc = launch(k11_forest_lds<32, 1024>);
-        } else {
-            if (fd.n_classes <= 4) rc = launch(k11_forest_lds<4, 512>);
-            else if (fd.n_classes <= 8) rc = launch(k11_forest_lds<8, 512>);
-            else if (fd.n_classes <= 16) rc = launch(k11_forest_lds<16, 512>);
-            else if (fd.n_classes <= 32) rc = launch(k11_forest_lds<32, 512>);
-            else rc = launch(k11_forest_lds<64, 512>);
-        }
-    } else {
-        // a tree larger than the LDS area: the first ntop (breadth-first) nodes of RF_C trees in LDS, in steps of 256
-        int ntop = 3 * TH;
-        while (ntop > 256 && (size_t)F * TH * 4 + (size_t)RF_C * ntop * sizeof(rf_node) > 158 * 1024) ntop -= 256;
-        const size_t lds = (size_t)F * TH * 4 + (size_t)RF_C * ntop * sizeof(rf_node);
-        auto launch = [&](auto kern) -> int {
-            RSCHK(set_max_dyn_lds(ctx, (const void *)kern, lds));
-            prof_scope ps(ctx, "forest");
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(TH), lds, ctx->stream, pl, F, n, (const rf_node *)fd.d_nodes, d_trees, fd.n_trees, ntop,
-                               (const double *)fd.d_leafval, fd.n_classes, d_classes, (long long *)d_out);
-            return RSSEG_OK;
-        };
-        if (TH == 1024) {
-            if (fd.n_classes <= 4) rc = launch(k11_forest_gen<4, 1024>);
-            else if (fd.n_classes <= 8) rc = launch(k11_forest_gen<8, 1024>);
-            else if (fd.n_classes <= 16) rc = launch(k11_forest_gen<16, 1024>);
-            else rc = launch(k11_forest_gen<32, 1024>);
-        } else {
-            if (fd.n_classes <= 4) rc = launch(k11_forest_gen<4, 512>);
-            else if (fd.n_classes <= 8) rc = launch(k11_forest_gen<8, 512>);
-            else if (fd.n_classes <= 16) rc = launch(k11_forest_gen<16, 512>);
-            else if (fd.n_classes <= 32) rc = launch(k11_forest_gen<32, 512>);
-            else rc = launch(k11_forest_gen<64, 512>);
-        }
-    }
+    const rf_plan p = rf_launch_plan(ctx->forest, F);
+    auto launch = [&](auto kern) { return rf_launch(ctx, p, "forest", 1, kern, pl, F, n, rf_dev_classes(ctx->forest), (long long *)d_out); };
+    int rc = RSSEG_ERR_INVALID;
+    if (p.lds_groups) { RF_DISPATCH(rc, p, launch, k11_forest_lds) }
+    else { RF_DISPATCH(rc, p, launch, k11_forest_gen) }
     if (rc != RSSEG_OK) return rc;
     HIPCHK(ctx, hipGetLastError());
     return stream_sync(ctx);

@@ -8,9 +8,9 @@
 // label_index: what rsseg_forest_predict turns into classes[...] (float64 sums of the leaf rows in tree order, divided by
 // the tree count, first maximum on ties); y[i] = -1 (a label the forest does not know) is never correct.
 //
-// The walk, the node layout and the vote table are those of k11_forest.hip (k11_forest.h); the two kernels below are
-// k11_forest_lds and k11_forest_gen with another staging and another finish, kept apart so that the existing kernels stay
-// as they are.  Jobs sit on blockIdx.y: a workgroup is (a block of RF_TH samples, one job).
+// The node layout, the vote table, the walks and the launch path are those of k11_forest.h; the two kernels below are
+// k11_forest_lds and k11_forest_gen with another staging and another finish, written out (DESIGN.md section 5 says why they
+// are not one body).  Jobs sit on blockIdx.y: a workgroup is (a block of RF_TH samples, one job).
 //   staging   the sample's own features, except feature f, which comes from row src[s * n + i] of the same plane.  The
 //             NaN-aware walk is chosen from the values staged, AFTER the substitution: a NaN brought in from a row of
 //             another workgroup turns it on, a NaN that the substitution replaced does not.  A source index outside
@@ -25,8 +25,6 @@
 // substituted value, a gather), 8 B per workgroup out.
 #include "common.h"
 #include "k11_forest.h"
-
-static_assert(RF_PX == 1, "one sample per thread: the substitution and the count below are per lane");
 
 struct rf_perm_args {
     const int32_t *y;                 // [n] class index, -1: unknown label
@@ -46,28 +44,6 @@ __device__ __forceinline__ float rf_perm_value(const rf_planes &pl, const rf_per
         else v = pl.p[job.feature][s];
     }
     return v;
-}
-
-// rf_vote in pieces of 8 doubles.  The accumulators of the widest rows take half the registers a lane may have (NC = 32 at
-// 1024 threads: 64 of 128; NC = 64 at 512: 128 of 256), and a whole row loaded beside them goes to scratch memory; the
-// compiler barrier keeps the pieces apart.  One addition per class and tree, in tree order, as rf_vote: the same sums.
-template <int NC>
-__device__ __forceinline__ void rf_vote_pieces(const rf_node nd, const double *__restrict__ leafval, double (&acc)[NC])
-{
-    const double2 *v = reinterpret_cast<const double2 *>(leafval + (size_t)(__float_as_uint(nd.thr) & RF_PAY_MASK) * NC);
-    constexpr int P = NC / 2 < 4 ? NC / 2 : 4;   // double2 per piece
-#pragma unroll
-    for (int c0 = 0; c0 < NC / 2; c0 += P) {
-        double2 t[P];
-#pragma unroll
-        for (int k = 0; k < P; k++) t[k] = v[c0 + k];
-#pragma unroll
-        for (int k = 0; k < P; k++) {
-            acc[2 * (c0 + k)] += t[k].x;
-            acc[2 * (c0 + k) + 1] += t[k].y;
-        }
-        if (NC > 16) asm volatile("" ::: "memory");
-    }
 }
 
 template <int NC, int RF_TH>
@@ -97,6 +73,10 @@ __device__ __forceinline__ void rf_perm_finish(const double (&acc)[NC], int n_tr
     }
 }
 
+// k11_forest_perm_lds keeps its LDS-group body WRITTEN OUT, as the parent had it: as a policy on a shared __forceinline__ body it computed
+// the same values, but was over the speed bar in two of three sessions.  The three LDS-group kernels (here, k11_forest_proba.hip,
+// k11_forest_perm.hip) share the walks, the vote rows, RF_PRE / RF_PUT and the launch path of k11_forest.h; a change to the
+// steps of one body is made in the other two as well.
 template <int NC, int RF_TH>
 __global__ __launch_bounds__(RF_TH) void k11_forest_perm_lds(rf_planes pl, int F, int64_t n, const rf_node *__restrict__ nodes,
                                                              const rf_tree *__restrict__ trees, const rf_group *__restrict__ groups, int n_groups,
@@ -124,24 +104,21 @@ __global__ __launch_bounds__(RF_TH) void k11_forest_perm_lds(rf_planes pl, int F
     }
     const bool any_nan = __syncthreads_or(my_nan) != 0;   // of the values staged for THIS job
     const unsigned feat_tid = (unsigned)(uintptr_t)(lds_cfloat *)feat + threadIdx.x * (unsigned)FP * 4u;
-    const unsigned px_stride = (unsigned)RF_TH * (unsigned)FP * 4u;
     const unsigned top_addr = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const uint4 *)top;
     double acc[NC];
 #pragma unroll
     for (int c = 0; c < NC; c++) acc[c] = 0.0;
     for (int g = 0; g < n_groups; g++) {
         const rf_group gr = groups[g];
-        // the next group's nodes in six named registers, as in k11_forest_lds (an array went to scratch memory there)
+        // the next group's nodes in the six named registers of k11_forest.h (RF_PRE / RF_PUT)
         static_assert(RF_NPRE == 6, "the prefetch registers below are spelled out for six pieces per thread");
         const bool more = g + 1 < n_groups;
         const rf_group gn = groups[more ? g + 1 : g];
         const int npiece = more ? (gn.n_nodes + 1) / 2 : 0;
         const uint4 *psrc = reinterpret_cast<const uint4 *>(nodes + gn.node_base);
         const int plast = (gn.n_nodes + 1) / 2 - 1;
-#define RF_PRE(r) const uint4 pre##r = psrc[(int)threadIdx.x + r * RF_TH < plast ? (int)threadIdx.x + r * RF_TH : plast];
         RF_PRE(0) RF_PRE(1) RF_PRE(2) RF_PRE(3) RF_PRE(4) RF_PRE(5)
-#undef RF_PRE
-        rf_node nd[RF_NCH];
+        rf_node nd[RF_C];
         unsigned base[RF_C];
 #pragma unroll
         for (int c = 0; c < RF_C; c++) {
@@ -151,29 +128,27 @@ __global__ __launch_bounds__(RF_TH) void k11_forest_perm_lds(rf_planes pl, int F
             nd[c].thr = p->thr;
             nd[c].bits = p->bits;
         }
-        if (any_nan) rf_walk_lds<true>(nd, feat_tid, px_stride, base, two_rounds != 0);
-        else rf_walk_lds<false>(nd, feat_tid, px_stride, base, two_rounds != 0);
+        if (any_nan) rf_walk_lds<true>(nd, feat_tid, base, two_rounds != 0);
+        else rf_walk_lds<false>(nd, feat_tid, base, two_rounds != 0);
         // refill first, then the vote rows of all chains at once, added in tree order behind the barrier (k11_forest_lds)
         constexpr bool PIPE = NC <= 8;
-        double rows[PIPE ? RF_NCH : 1][NC];
+        double rows[PIPE ? RF_C : 1][NC];
         if (PIPE) {
 #pragma unroll
-            for (int q = 0; q < RF_NCH; q++) rf_row_load<NC>(nd[q], leafval, rows[PIPE ? q : 0]);
+            for (int q = 0; q < RF_C; q++) rf_row_load<NC>(nd[q], leafval, rows[PIPE ? q : 0]);
         } else {
 #pragma unroll
-            for (int q = 0; q < RF_NCH; q++)
+            for (int q = 0; q < RF_C; q++)
                 if (q < gr.count && i0 < n) rf_vote_pieces<NC>(nd[q], leafval, acc);
         }
         if (more) {
             __syncthreads();  // every wave is done with the current group
-#define RF_PUT(r) if ((int)threadIdx.x + r * RF_TH < npiece) top[threadIdx.x + r * RF_TH] = pre##r;
             RF_PUT(0) RF_PUT(1) RF_PUT(2) RF_PUT(3) RF_PUT(4) RF_PUT(5)
-#undef RF_PUT
         }
         if (more) __syncthreads();
         if (PIPE) {
 #pragma unroll
-            for (int q = 0; q < RF_NCH; q++)
+            for (int q = 0; q < RF_C; q++)
                 if (q < gr.count) {   // lanes without a sample add the rows of their zero features and count nothing
 #pragma unroll
                     for (int c = 0; c < NC; c++) acc[c] += rows[PIPE ? q : 0][c];
@@ -183,6 +158,8 @@ __global__ __launch_bounds__(RF_TH) void k11_forest_perm_lds(rf_planes pl, int F
     rf_perm_finish<NC, RF_TH>(acc, n_trees, n_classes, a, n, i0, reinterpret_cast<int *>(smem));
 }
 
+// the general kernel, written out like the LDS-group one above (as a policy on a shared body it did not keep the parent's
+// speed: DESIGN.md section 5); a change to its steps is made in the other two files as well
 template <int NC, int RF_TH>
 __global__ __launch_bounds__(RF_TH) void k11_forest_perm_gen(rf_planes pl, int F, int64_t n, const rf_node *__restrict__ nodes,
                                                              const rf_tree *__restrict__ trees, int n_trees, int ntop,
@@ -287,57 +264,16 @@ __global__ __launch_bounds__(RF_TH) void k11_forest_perm_gen(rf_planes pl, int F
     rf_perm_finish<NC, RF_TH>(acc, n_trees, n_classes, a, n, i, reinterpret_cast<int *>(smem));
 }
 
-// jobs [j0, j0 + nj) of the call in one launch: grid (blocks of TH samples, jobs); the kernel, the launch geometry and the
-// LDS sizes are those rsseg_forest_predict chooses for the loaded forest
+// jobs [j0, j0 + nj) of the call in one launch: grid (blocks of TH samples, jobs), by the plan and the dispatch of k11_forest.h
 static int rf_launch_perm(rsseg_ctx *ctx, const rf_planes &pl, int F, int64_t n, rf_perm_args a, int j0, int nj)
 {
-    forest_dev &fd = ctx->forest;
-    const rf_tree *d_trees = (const rf_tree *)((const char *)fd.d_treeoff + fd.n_classes * sizeof(long long));
-    const int TH = rf_threads(F, fd.n_classes);
-    const dim3 grid((unsigned)ceil_div64(n, TH), (unsigned)nj);
-    const int NCP = fd.n_classes <= 4 ? 4 : (fd.n_classes <= 8 ? 8 : (fd.n_classes <= 16 ? 16 : (fd.n_classes <= 32 ? 32 : 64)));
+    const rf_plan p = rf_launch_plan(ctx->forest, F);
     a.jobs += j0;
     a.counts += j0;
+    auto launch = [&](auto kern) { return rf_launch(ctx, p, "forest_perm", (unsigned)nj, kern, pl, F, n, a); };
     int rc = RSSEG_ERR_INVALID;
-#define RF_DISPATCH(KERN)                                                       \
-    if (TH == 1024) {                                                           \
-        if (NCP == 4) rc = launch(KERN<4, 1024>);                               \
-        else if (NCP == 8) rc = launch(KERN<8, 1024>);                          \
-        else if (NCP == 16) rc = launch(KERN<16, 1024>);                        \
-        else rc = launch(KERN<32, 1024>);                                       \
-    } else {                                                                    \
-        if (NCP == 4) rc = launch(KERN<4, 512>);                                \
-        else if (NCP == 8) rc = launch(KERN<8, 512>);                           \
-        else if (NCP == 16) rc = launch(KERN<16, 512>);                         \
-        else if (NCP == 32) rc = launch(KERN<32, 512>);                         \
-        else rc = launch(KERN<64, 512>);                                        \
-    }
-    if (fd.n_groups > 0) {
-        const int cap = rf_lds_cap(F, TH);
-        const size_t lds = (size_t)(F | 1) * TH * 4 + (size_t)cap * sizeof(rf_node) + 16;
-        auto launch = [&](auto kern) -> int {
-            RSCHK(set_max_dyn_lds(ctx, (const void *)kern, lds));
-            prof_scope ps(ctx, "forest_perm");
-            hipLaunchKernelGGL(kern, grid, dim3(TH), lds, ctx->stream, pl, F, n, (const rf_node *)fd.d_nodes, d_trees,
-                               (const rf_group *)fd.d_groups, fd.n_groups, cap / 2, fd.max_depth >= 10 ? 1 : 0, fd.n_trees,
-                               (const double *)fd.d_leafval, fd.n_classes, a);
-            return RSSEG_OK;
-        };
-        RF_DISPATCH(k11_forest_perm_lds)
-    } else {
-        int ntop = 3 * TH;
-        while (ntop > 256 && (size_t)F * TH * 4 + (size_t)RF_C * ntop * sizeof(rf_node) > 158 * 1024) ntop -= 256;
-        const size_t lds = (size_t)F * TH * 4 + (size_t)RF_C * ntop * sizeof(rf_node);
-        auto launch = [&](auto kern) -> int {
-            RSCHK(set_max_dyn_lds(ctx, (const void *)kern, lds));
-            prof_scope ps(ctx, "forest_perm");
-            hipLaunchKernelGGL(kern, grid, dim3(TH), lds, ctx->stream, pl, F, n, (const rf_node *)fd.d_nodes, d_trees, fd.n_trees, ntop,
-                               (const double *)fd.d_leafval, fd.n_classes, a);
-            return RSSEG_OK;
-        };
-        RF_DISPATCH(k11_forest_perm_gen)
-    }
-#undef RF_DISPATCH
+    if (p.lds_groups) { RF_DISPATCH(rc, p, launch, k11_forest_perm_lds) }
+    else { RF_DISPATCH(rc, p, launch, k11_forest_perm_gen) }
     if (rc != RSSEG_OK) return rc;
     HIPCHK(ctx, hipGetLastError());
     return RSSEG_OK;
@@ -350,17 +286,8 @@ extern "C" int rsseg_forest_permutation_counts(rsseg_ctx *ctx, const float *cons
 {
     if (!ctx) return RSSEG_ERR_INVALID;
     const char *who = "forest_permutation_counts";
-    forest_dev &fd = ctx->forest;
-    if (!fd.d_nodes) return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: no forest loaded", who);
-    if (!d_planes || n < 0 || n_jobs < 0 || n_src < 0) return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: bad arguments", who);
-    if (F != fd.n_features)
-        return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: X has %d features, but the forest is expecting %d features as input", who, F, fd.n_features);
     rf_planes pl;
-    memset(&pl, 0, sizeof(pl));
-    for (int f = 0; f < F; f++) {
-        if (!d_planes[f]) return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: plane %d is null", who, f);
-        pl.p[f] = d_planes[f];
-    }
+    RSCHK(rf_check_planes(ctx, who, d_planes, n >= 0 && n_jobs >= 0 && n_src >= 0, F, pl));
     if (!d_y) return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: the labels are null", who);
     if (!jobs) return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: the jobs are null", who);
     if (!counts) return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: the counts are null", who);

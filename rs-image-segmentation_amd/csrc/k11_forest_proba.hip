@@ -4,8 +4,8 @@
 // order in float64, divided by the tree count) and ForestClassifier._compute_oob_predictions (_forest.py:558-622: the
 // same sum over the trees whose bootstrap never drew the sample, divided by max(number of such trees, 1)).
 //
-// The walk, the node layout and the vote table are those of k11_forest.hip (k11_forest.h); the two kernels below are
-// k11_forest_lds and k11_forest_gen with another finish, kept apart so that the label-only kernels stay as they are:
+// The node layout, the vote table, the walks and the launch path are those of k11_forest.h; the two kernels below are
+// k11_forest_lds and k11_forest_gen with another finish, written out (DESIGN.md section 5 says why they are not one body):
 //   OOB = false   proba[c][i] = acc[c] / n_trees (class-planar: for a class the lanes of a wave store consecutive
 //                 doubles), conf[i] = the largest of them, labels[i] = classes[first maximum]; any output may be null
 //   OOB = true    a tree's row is added, and the sample's count incremented, only where counts[tree][i] == 0; every chain
@@ -15,8 +15,6 @@
 // HBM traffic: 4F B/px in, 8 * n_classes + 8 + 8 B/px out (proba, confidence, label); OOB adds 4 * n_trees B/sample in.
 #include "common.h"
 #include "k11_forest.h"
-
-static_assert(RF_PX == 1, "one pixel per thread: the out-of-bag flags below are per chain of one pixel");
 
 struct rf_outputs {
     double *proba;         // [n_classes][n]; the out-of-bag decision function when OOB
@@ -49,6 +47,10 @@ __device__ __forceinline__ void rf_finish_out(const double (&acc)[NC], int n_tre
     }
 }
 
+// k11_forest_out_lds keeps its LDS-group body WRITTEN OUT, as the parent had it: as a policy on a shared __forceinline__ body it computed
+// the same values, but missed the speed bar in two sessions.  The three LDS-group kernels (here, k11_forest_proba.hip,
+// k11_forest_perm.hip) share the walks, the vote rows, RF_PRE / RF_PUT and the launch path of k11_forest.h; a change to the
+// steps of one body is made in the other two as well.
 template <int NC, int RF_TH, bool OOB>
 __global__ __launch_bounds__(RF_TH) void k11_forest_out_lds(rf_planes pl, int F, int64_t n, const rf_node *__restrict__ nodes,
                                                             const rf_tree *__restrict__ trees, const rf_group *__restrict__ groups, int n_groups,
@@ -75,7 +77,6 @@ __global__ __launch_bounds__(RF_TH) void k11_forest_out_lds(rf_planes pl, int F,
     }
     const bool any_nan = __syncthreads_or(my_nan) != 0;
     const unsigned feat_tid = (unsigned)(uintptr_t)(lds_cfloat *)feat + threadIdx.x * (unsigned)FP * 4u;
-    const unsigned px_stride = (unsigned)RF_TH * (unsigned)FP * 4u;
     const unsigned top_addr = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const uint4 *)top;
     double acc[NC];
 #pragma unroll
@@ -83,16 +84,14 @@ __global__ __launch_bounds__(RF_TH) void k11_forest_out_lds(rf_planes pl, int F,
     int n_oob = 0;
     for (int g = 0; g < n_groups; g++) {
         const rf_group gr = groups[g];
-        // the next group's nodes in six named registers, as in k11_forest_lds (an array went to scratch memory there)
+        // the next group's nodes in the six named registers of k11_forest.h (RF_PRE / RF_PUT)
         static_assert(RF_NPRE == 6, "the prefetch registers below are spelled out for six pieces per thread");
         const bool more = g + 1 < n_groups;
         const rf_group gn = groups[more ? g + 1 : g];
         const int npiece = more ? (gn.n_nodes + 1) / 2 : 0;
         const uint4 *psrc = reinterpret_cast<const uint4 *>(nodes + gn.node_base);
         const int plast = (gn.n_nodes + 1) / 2 - 1;
-#define RF_PRE(r) const uint4 pre##r = psrc[(int)threadIdx.x + r * RF_TH < plast ? (int)threadIdx.x + r * RF_TH : plast];
         RF_PRE(0) RF_PRE(1) RF_PRE(2) RF_PRE(3) RF_PRE(4) RF_PRE(5)
-#undef RF_PRE
         // out-of-bag: the sample's bootstrap counts for the trees of the group (a row of counts per tree: coalesced)
         bool use[RF_C];
 #pragma unroll
@@ -104,7 +103,7 @@ __global__ __launch_bounds__(RF_TH) void k11_forest_out_lds(rf_planes pl, int F,
                 n_oob += use[c] ? 1 : 0;
             }
         }
-        rf_node nd[RF_NCH];
+        rf_node nd[RF_C];
         unsigned base[RF_C];
 #pragma unroll
         for (int c = 0; c < RF_C; c++) {
@@ -114,29 +113,27 @@ __global__ __launch_bounds__(RF_TH) void k11_forest_out_lds(rf_planes pl, int F,
             nd[c].thr = p->thr;
             nd[c].bits = p->bits;
         }
-        if (any_nan) rf_walk_lds<true>(nd, feat_tid, px_stride, base, two_rounds != 0);
-        else rf_walk_lds<false>(nd, feat_tid, px_stride, base, two_rounds != 0);
+        if (any_nan) rf_walk_lds<true>(nd, feat_tid, base, two_rounds != 0);
+        else rf_walk_lds<false>(nd, feat_tid, base, two_rounds != 0);
         // refill first, then the vote rows of all chains at once, added in tree order behind the barrier (k11_forest_lds)
         constexpr bool PIPE = NC <= 8;
-        double rows[PIPE ? RF_NCH : 1][NC];
+        double rows[PIPE ? RF_C : 1][NC];
         if (PIPE) {
 #pragma unroll
-            for (int q = 0; q < RF_NCH; q++) rf_row_load<NC>(nd[q], leafval, rows[PIPE ? q : 0]);
+            for (int q = 0; q < RF_C; q++) rf_row_load<NC>(nd[q], leafval, rows[PIPE ? q : 0]);
         } else {
 #pragma unroll
-            for (int q = 0; q < RF_NCH; q++)
+            for (int q = 0; q < RF_C; q++)
                 if (use[q]) rf_vote<NC>(nd[q], leafval, acc);
         }
         if (more) {
             __syncthreads();  // every wave is done with the current group
-#define RF_PUT(r) if ((int)threadIdx.x + r * RF_TH < npiece) top[threadIdx.x + r * RF_TH] = pre##r;
             RF_PUT(0) RF_PUT(1) RF_PUT(2) RF_PUT(3) RF_PUT(4) RF_PUT(5)
-#undef RF_PUT
         }
         if (more) __syncthreads();
         if (PIPE) {
 #pragma unroll
-            for (int q = 0; q < RF_NCH; q++)
+            for (int q = 0; q < RF_C; q++)
                 if (OOB ? use[q] : q < gr.count) {   // lanes without a pixel add the rows of their zero features and store nothing
 #pragma unroll
                     for (int c = 0; c < NC; c++) acc[c] += rows[PIPE ? q : 0][c];
@@ -146,6 +143,8 @@ __global__ __launch_bounds__(RF_TH) void k11_forest_out_lds(rf_planes pl, int F,
     if (i0 < n) rf_finish_out<NC, OOB>(acc, n_trees, n_oob, n_classes, classes, o, n, i0);
 }
 
+// the general kernel, written out like the LDS-group one above (as a policy on a shared body it did not keep the parent's
+// speed: DESIGN.md section 5); a change to its steps is made in the other two files as well
 template <int NC, int RF_TH, bool OOB>
 __global__ __launch_bounds__(RF_TH) void k11_forest_out_gen(rf_planes pl, int F, int64_t n, const rf_node *__restrict__ nodes,
                                                             const rf_tree *__restrict__ trees, int n_trees, int ntop,
@@ -247,77 +246,18 @@ __global__ __launch_bounds__(RF_TH) void k11_forest_out_gen(rf_planes pl, int F,
     if (i < n) rf_finish_out<NC, OOB>(acc, n_trees, n_oob, n_classes, classes, o, n, i);
 }
 
-// One launch of the loaded forest over n pixels into `o`: the LDS-group kernel when rsseg_forest_load found a plan, the
-// general kernel otherwise; launch geometry and LDS sizes are those of rsseg_forest_predict.
+// One launch of the loaded forest over n pixels into `o`, by the plan and the dispatch of k11_forest.h
 template <bool OOB>
 static int rf_launch_out(rsseg_ctx *ctx, const rf_planes &pl, int F, int64_t n, const rf_outputs &o, const char *prof_name)
 {
-    forest_dev &fd = ctx->forest;
-    const long long *d_classes = (const long long *)fd.d_treeoff;
-    const rf_tree *d_trees = (const rf_tree *)((const char *)fd.d_treeoff + fd.n_classes * sizeof(long long));
-    const int TH = rf_threads(F, fd.n_classes);
-    const unsigned grid = (unsigned)ceil_div64(n, TH);
-    const int NCP = fd.n_classes <= 4 ? 4 : (fd.n_classes <= 8 ? 8 : (fd.n_classes <= 16 ? 16 : (fd.n_classes <= 32 ? 32 : 64)));
+    const rf_plan p = rf_launch_plan(ctx->forest, F);
+    auto launch = [&](auto kern) { return rf_launch(ctx, p, prof_name, 1, kern, pl, F, n, rf_dev_classes(ctx->forest), o); };
     int rc = RSSEG_ERR_INVALID;
-    // the (row width, threads) pairs rsseg_forest_predict has: 1024 threads up to 32 classes, 512 for every width
-#define RF_DISPATCH(KERN)                                                            \
-    if (TH == 1024) {                                                                \
-        if (NCP == 4) rc = launch(KERN<4, 1024, OOB>);                               \
-        else if (NCP == 8) rc = launch(KERN<8, 1024, OOB>);                          \
-        else if (NCP == 16) rc = launch(KERN<16, 1024, OOB>);                        \
-        else rc = launch(KERN<32, 1024, OOB>);                                       \
-    } else {                                                                         \
-        if (NCP == 4) rc = launch(KERN<4, 512, OOB>);                                \
-        else if (NCP == 8) rc = launch(KERN<8, 512, OOB>);                           \
-        else if (NCP == 16) rc = launch(KERN<16, 512, OOB>);                         \
-        else if (NCP == 32) rc = launch(KERN<32, 512, OOB>);                         \
-        else rc = launch(KERN<64, 512, OOB>);                                        \
-    }
-    if (fd.n_groups > 0) {
-        const int cap = rf_lds_cap(F, TH);
-        const size_t lds = (size_t)(F | 1) * TH * 4 + (size_t)cap * sizeof(rf_node) + 16;
-        auto launch = [&](auto kern) -> int {
-            RSCHK(set_max_dyn_lds(ctx, (const void *)kern, lds));
-            prof_scope ps(ctx, prof_name);
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(TH), lds, ctx->stream, pl, F, n, (const rf_node *)fd.d_nodes, d_trees,
-                               (const rf_group *)fd.d_groups, fd.n_groups, cap / 2, fd.max_depth >= 10 ? 1 : 0, fd.n_trees,
-                               (const double *)fd.d_leafval, fd.n_classes, d_classes, o);
-            return RSSEG_OK;
-        };
-        RF_DISPATCH(k11_forest_out_lds)
-    } else {
-        int ntop = 3 * TH;
-        while (ntop > 256 && (size_t)F * TH * 4 + (size_t)RF_C * ntop * sizeof(rf_node) > 158 * 1024) ntop -= 256;
-        const size_t lds = (size_t)F * TH * 4 + (size_t)RF_C * ntop * sizeof(rf_node);
-        auto launch = [&](auto kern) -> int {
-            RSCHK(set_max_dyn_lds(ctx, (const void *)kern, lds));
-            prof_scope ps(ctx, prof_name);
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(TH), lds, ctx->stream, pl, F, n, (const rf_node *)fd.d_nodes, d_trees, fd.n_trees, ntop,
-                               (const double *)fd.d_leafval, fd.n_classes, d_classes, o);
-            return RSSEG_OK;
-        };
-        RF_DISPATCH(k11_forest_out_gen)
-    }
-#undef RF_DISPATCH
+    if (p.lds_groups) { RF_DISPATCH(rc, p, launch, k11_forest_out_lds, OOB) }
+    else { RF_DISPATCH(rc, p, launch, k11_forest_out_gen, OOB) }
     if (rc != RSSEG_OK) return rc;
     HIPCHK(ctx, hipGetLastError());
     return stream_sync(ctx);
-}
-
-// the checks both entry points share; fills `pl`
-static int rf_check_planes(rsseg_ctx *ctx, const char *who, const float *const *d_planes, int F, int64_t n, rf_planes &pl)
-{
-    forest_dev &fd = ctx->forest;
-    if (!fd.d_nodes) return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: no forest loaded", who);
-    if (!d_planes || n < 0) return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: bad arguments", who);
-    if (F != fd.n_features)
-        return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: X has %d features, but the forest is expecting %d features as input", who, F, fd.n_features);
-    memset(&pl, 0, sizeof(pl));
-    for (int f = 0; f < F; f++) {
-        if (!d_planes[f]) return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: plane %d is null", who, f);
-        pl.p[f] = d_planes[f];
-    }
-    return RSSEG_OK;
 }
 
 extern "C" int rsseg_forest_predict_proba(rsseg_ctx *ctx, const float *const *d_planes, int F, int64_t n, double *d_proba, double *d_conf,
@@ -325,7 +265,7 @@ extern "C" int rsseg_forest_predict_proba(rsseg_ctx *ctx, const float *const *d_
 {
     if (!ctx) return RSSEG_ERR_INVALID;
     rf_planes pl;
-    RSCHK(rf_check_planes(ctx, "forest_predict_proba", d_planes, F, n, pl));
+    RSCHK(rf_check_planes(ctx, "forest_predict_proba", d_planes, n >= 0, F, pl));
     if (!d_proba && !d_conf && !d_labels) return rs_fail(ctx, RSSEG_ERR_INVALID, "forest_predict_proba: every output is null");
     if (n == 0) return RSSEG_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -343,7 +283,7 @@ extern "C" int rsseg_forest_oob(rsseg_ctx *ctx, const float *const *d_planes, in
 {
     if (!ctx) return RSSEG_ERR_INVALID;
     rf_planes pl;
-    RSCHK(rf_check_planes(ctx, "forest_oob", d_planes, F, n, pl));
+    RSCHK(rf_check_planes(ctx, "forest_oob", d_planes, n >= 0, F, pl));
     if (!d_counts) return rs_fail(ctx, RSSEG_ERR_INVALID, "forest_oob: the bootstrap counts are null");
     if (!d_oob || !d_n_oob) return rs_fail(ctx, RSSEG_ERR_INVALID, "forest_oob: an output is null");
     if (n == 0) return RSSEG_OK;
