@@ -772,9 +772,9 @@ def rule_based_classification(features: dict) -> np.ndarray:
 # --------------------------------------------------------------------------------------------
 # KMeans   (modules/features/extract.py:508-581 -> oracle.c)
 # --------------------------------------------------------------------------------------------
-def kmeans_random_draws(n: int, k: int, dtype) -> Tuple[int, np.ndarray]:
-    """The two things sklearn asks RandomState(42) for (sklearn/cluster/_kmeans.py:225, 243)."""
-    rs = np.random.RandomState(42)
+def kmeans_random_draws(n: int, k: int, dtype, seed: int = 42) -> Tuple[int, np.ndarray]:
+    """The two things sklearn asks RandomState(seed) for (sklearn/cluster/_kmeans.py:225, 243); the reference passes 42."""
+    rs = np.random.RandomState(seed)
     w = np.ones(n, dtype=dtype)
     center_id = int(rs.choice(n, p=w / w.sum()))
     L = 2 + int(np.log(k))
@@ -782,14 +782,14 @@ def kmeans_random_draws(n: int, k: int, dtype) -> Tuple[int, np.ndarray]:
     return center_id, u
 
 
-def kmeans_fit_planes(planes: Sequence[np.ndarray], n_clusters: int, max_iter=300, tol=1e-4):
+def kmeans_fit_planes(planes: Sequence[np.ndarray], n_clusters: int, max_iter=300, tol=1e-4, seed: int = 42):
     """planes: list of equally shaped arrays, all float32 or all float64 (one per feature column)."""
     dt = np.result_type(*[p.dtype for p in planes])
     if dt not in (np.float32, np.float64):
         dt = np.dtype(np.float64)
     P = [np.ascontiguousarray(p.reshape(-1), dtype=dt) for p in planes]
     n, F = P[0].size, len(P)
-    cid, u = kmeans_random_draws(n, n_clusters, dt)
+    cid, u = kmeans_random_draws(n, n_clusters, dt, seed)
     ctype = ctypes.c_float if dt == np.float32 else ctypes.c_double
     arr = (ctypes.POINTER(ctype) * F)(*[p.ctypes.data_as(ctypes.POINTER(ctype)) for p in P])
     labels = np.zeros(n, np.int32)

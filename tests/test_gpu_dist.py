@@ -353,16 +353,33 @@ def test_many_stripes_in_threads_equal_single_gpu(ctx, oracle, H, W, world):
 
 @pytest.mark.parametrize("F,k,dt,splits", [(40, 5, np.float64, (0, 7001, 7001, 20011)),      # feature-blocked kernels; rank 1 holds NO pixels
                                             (15, 8, np.float32, (0, 16384 * 3 + 5, 16384 * 3 + 9, 70001)),   # a 4-pixel rank
-                                            (2, 11, np.float32, (0, 30, 64, 97))])           # duplicate-heavy (seed 22 of the relocation test): clusters run empty
+                                            (2, 11, np.float32, (0, 30, 64, 97)),            # duplicate-heavy (seed 22 of the relocation test): clusters run empty
+                                            # relocation cases of tests/kmeans_fit_cases.py, three chunks: an empty rank between two that
+                                            # both hold taken pixels; four ranks that each hold one or two of the five taken pixels
+                                            (33, 32, np.float64, (0, 100, 100, 16901)),
+                                            (9, 16, np.float32, (0, 40, 62, 64, 33797))])
 def test_kmeans_entry_point_sharded_over_thread_ranks(ctx, oracle, F, k, dt, splits):
     """rsseg_kmeans_fit_predict itself on consecutive slices of the pixel list, one context per slice (threads of this
     process): the device-resident state, the stream-ordered collectives between the control kernels, a rank without
     pixels, a rank smaller than one chunk, the feature-blocked kernels (F = 40) and the empty-cluster hand-over to the
-    host path, against the single-context run and the oracle: seeds, iteration count, relocations and labels."""
+    host path, against the single-context run and the oracle: seeds, iteration count, relocations and labels; the centres
+    of every rank against the single-context run's, bit for bit.  The two relocation cases put the pixels that the empty
+    clusters take on several ranks: the farthest pixel is found by a MAX and a MIN across ranks (relocate) and its row comes
+    from the one rank that holds it (fetch_row)."""
+    import kmeans_fit_cases as K
     from rsseg.runtime import Context
     rng = np.random.default_rng(F * 100 + k)
     n = splits[-1]
-    if F == 2:   # the data of test_kmeans_empty_cluster_relocation[22]: 97 points, 2 features, 11 clusters, 2 relocations
+    reloc_case = n == K.large_n(dt)
+    if reloc_case:
+        t = "f32" if dt == np.float32 else "f64"
+        d = dict(K.RELOC_KD)[k]
+        planes, _ = K.protos(K.RELOC_SEEDS_LARGE[(F, k, d, t)], n, F, d, dt)
+        X = np.stack(planes, axis=1)
+        far = K.restate_relocation(oracle, planes, k)["far"]
+        owners = np.searchsorted(np.asarray(splits[1:]), far, side="right")
+        assert len(set(owners.tolist())) == sum(b > a for a, b in zip(splits, splits[1:])), owners   # every rank with pixels gives some
+    elif F == 2:   # the data of test_kmeans_empty_cluster_relocation[22]: 97 points, 2 features, 11 clusters, 2 relocations
         rng = np.random.default_rng(22)
         n_, F_, k_ = int(rng.integers(20, 120)), int(rng.integers(1, 4)), int(rng.integers(6, 14))
         assert (n_, F_, k_) == (n, F, k)
@@ -373,10 +390,12 @@ def test_kmeans_entry_point_sharded_over_thread_ranks(ctx, oracle, F, k, dt, spl
         X = (cent[rng.integers(0, k + 2, n)] + rng.normal(0, 0.07, (n, F))).astype(dt)
     planes = [np.ascontiguousarray(X[:, f]) for f in range(F)]
     want, info = oracle.kmeans_fit_planes(planes, k)
-    if F == 2:
+    if F == 2 or reloc_case:
         assert info["relocated"] > 0
     labels, meta = ctx.kmeans_fit_predict([ctx.to_device(p) for p in planes], k)
     assert np.array_equal(labels.cpu().numpy(), want) and meta["n_iter"] == info["n_iter"]
+    if reloc_case:
+        K.assert_fit_equal(meta, labels.cpu().numpy(), info, want, dt, (F, k, "single context"))
     world = len(splits) - 1
     tw = _ThreadWorld(world)
     out = [None] * world
@@ -387,15 +406,16 @@ def test_kmeans_entry_point_sharded_over_thread_ranks(ctx, oracle, F, k, dt, spl
         a, b = splits[r], splits[r + 1]
         d = [c.to_device(p[a:b].copy()) for p in planes]
         lab, m = c.kmeans_fit_predict(d, k)
-        out[r] = (lab.cpu().numpy(), m["n_iter"], m["relocated"], m["init_indices"].copy())
+        out[r] = (lab.cpu().numpy(), m["n_iter"], m["relocated"], m["init_indices"].copy(), m["centers"].copy())
         c.close()
 
     tw.run(rank_main)
     for r in range(world):
-        lab, n_iter, reloc, seeds = out[r]
+        lab, n_iter, reloc, seeds, centres = out[r]
         assert n_iter == info["n_iter"] and reloc == info["relocated"], r
         assert np.array_equal(seeds, info["init_indices"]), r
         assert np.array_equal(lab, want[splits[r]:splits[r + 1]]), r
+        assert centres.shape == meta["centers"].shape and np.array_equal(K.bits(centres), K.bits(meta["centers"])), r
 
 
 def test_full_size_eight_stripes_in_threads_equal_single_gpu(ctx):

@@ -9,6 +9,9 @@ beyond n is not inside a larger buffer of the test's own."""
 import numpy as np
 import pytest
 
+# the data, the exact-size device planes and the comparison itself are shared with the other k-means fit tests
+from kmeans_fit_cases import blobs, check_fit
+
 pytestmark = pytest.mark.gpu
 
 THREADS, TILES_PER_CHUNK = 256, 16
@@ -20,39 +23,8 @@ def seam_sizes(dt):
     return [1, tile - 1, tile, tile + 1, 2 * tile, 2 * tile + 3, 15 * tile + 7, chunk - 1, chunk, chunk + 1, 2 * chunk + tile + 5]
 
 
-def blobs(seed, n, F, k, dt, sigma):
-    rng = np.random.default_rng(seed)
-    cen = rng.random((max(k, 2), F)) * 4
-    X = cen[rng.integers(0, cen.shape[0], n)] + rng.normal(0, sigma, (n, F))
-    return [np.ascontiguousarray(X[:, f]).astype(dt) for f in range(F)]
-
-
-def exact_planes(planes):
-    """one device allocation of exactly n elements per plane"""
-    import torch
-    out = []
-    for p in planes:
-        t = torch.empty(p.size, dtype=torch.float32 if p.dtype == np.float32 else torch.float64, device="cuda")
-        t.copy_(torch.from_numpy(p))
-        out.append(t)
-    return out
-
-
 def check(ctx, oracle, planes, k, tag, max_iter=300):
-    want, info = oracle.kmeans_fit_planes(planes, k, max_iter=max_iter)
-    labels, meta = ctx.kmeans_fit_predict(exact_planes(planes), k, max_iter=max_iter)
-    assert [int(x) for x in meta["init_indices"]] == [int(x) for x in info["init_indices"]], tag
-    for key in ("scale", "min", "mean"):
-        assert np.array_equal(meta[key].view(np.uint64), info[key].view(np.uint64)), (tag, key)
-    assert int(meta["n_iter"]) == int(info["n_iter"]), (tag, meta["n_iter"], info["n_iter"])
-    got = labels.cpu().numpy()
-    assert got.shape == want.shape and np.array_equal(got, want), (tag, int((got != want).sum()))
-    # the oracle reports the centres of the centred space; the library adds the mean back in the planes' type, as
-    # scikit-learn does (best_centers += X_mean): one rounded addition per value, repeated here on the oracle's numbers
-    dt = planes[0].dtype
-    want_centers = (info["centers"].astype(dt) + info["mean"].astype(dt)[None, :]).astype(np.float64)
-    assert np.array_equal(meta["centers"].view(np.uint64), want_centers.view(np.uint64)), tag
-    return info
+    return check_fit(ctx, oracle, planes, k, tag, max_iter=max_iter)
 
 
 @pytest.mark.parametrize("k", [2, 8])

@@ -586,10 +586,13 @@ def test_kmeans_float64_planes_with_more_than_32_clusters(ctx, oracle, n, F, k):
     assert planes[0].dtype == np.float64 and meta["n_iter"] == info["n_iter"]
     assert np.array_equal(meta["init_indices"], info["init_indices"])
     assert np.array_equal(host(labels), want)
+    from kmeans_fit_cases import assert_fit_equal
+    assert_fit_equal(meta, host(labels), info, want, np.float64, (n, F, k))   # centres, scaler and tol too, bit for bit
     p32 = [p.astype(np.float32) for p in planes]
     want32, info32 = oracle.kmeans_fit_planes(p32, k)
     labels32, meta32 = ctx.kmeans_fit_predict([dev(ctx, p) for p in p32], k)
     assert meta32["n_iter"] == info32["n_iter"] and np.array_equal(host(labels32), want32)
+    assert_fit_equal(meta32, host(labels32), info32, want32, np.float32, (n, F, k, "f32"))
 
 
 def test_kmeans_both_lloyd_forms_give_the_same_fit(ctx, oracle):
@@ -1074,6 +1077,9 @@ def test_kmeans_empty_cluster_relocation(ctx, oracle, seed):
     assert meta["relocated"] == info["relocated"]
     assert meta["n_iter"] == info["n_iter"]
     assert np.array_equal(host(labels), want)
+    # the fit ends in the iteration that relocates, so the labels do not show which pixels were taken: the centres do
+    from kmeans_fit_cases import assert_fit_equal
+    assert_fit_equal(meta, host(labels), info, want, np.float32, seed)
     from sklearn.cluster import KMeans
     from sklearn.preprocessing import MinMaxScaler
     from threadpoolctl import threadpool_limits
@@ -1101,6 +1107,8 @@ def test_kmeans_many_clusters_and_features(ctx, oracle, k, F, dt):
     assert np.array_equal(meta["init_indices"], info["init_indices"])
     assert meta["n_iter"] == info["n_iter"]
     assert np.array_equal(host(labels), want)
+    from kmeans_fit_cases import assert_fit_equal
+    assert_fit_equal(meta, host(labels), info, want, dt, (k, F))   # centres, scaler and tol too, bit for bit
 
 
 # ------------------------------------------------------------------------------------------------ full size
