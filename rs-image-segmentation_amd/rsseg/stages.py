@@ -12,14 +12,16 @@ mirrors in modules/ do.  Plotting (scripts/2:131, 267-385; scripts/3:491) is out
 """
 from __future__ import annotations
 
+import json
 import os
 import pickle
+from dataclasses import dataclass, replace
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import pipeline as P
-from .runtime import Context, default_context
+from .runtime import Context, RssegUnsupported, default_context
 
 
 def run_feature_extraction_stage(bands_data: Sequence[np.ndarray], preprocessing: bool = True, texture_band_index: int = 3,
@@ -148,6 +150,8 @@ def run_kmeans_stage(hierarchical_all: np.ndarray, n_clusters: int = 7, ctx: Opt
 
 
 def _check_valid_mask(valid_mask, shape):
+    if valid_mask is None:
+        return None
     m = np.asarray(valid_mask)
     if m.shape != tuple(shape):
         raise ValueError(f"valid_mask: shape {m.shape}, the raster is {tuple(shape)}")
@@ -156,6 +160,39 @@ def _check_valid_mask(valid_mask, shape):
 
 RF_MODEL_FILE = "random_forest_model.joblib"   # scripts/3_classification.py:459
 GAUSS_METHODS = ("maximum_likelihood", "mahalanobis", "minimum_distance")   # rsseg.gaussian.STAGE_METHODS
+
+
+@dataclass(frozen=True)
+class ClassifyRequest:
+    """What one run of the classification stage is asked for: the arguments of run_classification_stage and of its three
+    siblings, with run_classification_stage's defaults.  A branch of _classify reads its own fields and ignores the others."""
+    method: str = "rule_based"
+    n_clusters: int = 7
+    use_hierarchical_all: bool = True
+    classifier: object = None
+    feature_keys: Optional[Sequence[str]] = None
+    labeled_roi_file: str = "labeled_roi.tif"
+    strict_reference: bool = False
+    valid_mask: object = None                  # (H, W), non-zero = valid: class 0 at the other pixels
+    confidence: bool = False                   # forest: ClassifyProducts.proba and .confidence
+    importance_mask: object = None             # forest: an (H, W) label mask -> .importance and .feature_names
+    save_kmeans_model: Optional[str] = None    # kmeans: .kmeans_model, the model of the fit that made the labels, saved there
+    ml_threshold: Optional[float] = None       # GAUSS_METHODS
+    rule_image: bool = False                   # GAUSS_METHODS: .dist2 and .margin
+    fit_on_device: bool = False                # GAUSS_METHODS
+
+
+@dataclass
+class ClassifyProducts:
+    """What a branch of _classify made beside the class map; None: not made.  _run_classification writes what is there."""
+    kmeans_model: object = None
+    proba: Optional[np.ndarray] = None         # (H, W, C)
+    confidence: Optional[np.ndarray] = None    # (H, W)
+    gauss_model: object = None
+    dist2: Optional[np.ndarray] = None
+    margin: Optional[np.ndarray] = None
+    importance: Optional[Dict[str, object]] = None
+    feature_names: Optional[Sequence[str]] = None
 
 
 def run_classification_stage(feature_file_path, method='rule_based', output_dir="segmentation_outputs", use_hierarchical_all=True, *,
@@ -192,8 +229,9 @@ def run_classification_stage(feature_file_path, method='rule_based', output_dir=
     reference's error paths, which print and return).  run_forest_confidence_stage is the 'random_forest' branch with the
     class probabilities and the confidence map written beside the class map, run_masked_classification_stage the same
     dispatch on the valid pixels of a scene with nodata."""
-    return _run_classification(feature_file_path, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys,
-                               labeled_roi_file, strict_reference, ctx, False)
+    req = ClassifyRequest(method=method, n_clusters=n_clusters, use_hierarchical_all=use_hierarchical_all, classifier=classifier,
+                          feature_keys=feature_keys, labeled_roi_file=labeled_roi_file, strict_reference=strict_reference)
+    return _run_classification(feature_file_path, output_dir, req, ctx)
 
 
 def run_masked_classification_stage(feature_file_path, method='rule_based', output_dir="segmentation_outputs", use_hierarchical_all=True, *,
@@ -207,8 +245,10 @@ def run_masked_classification_stage(feature_file_path, method='rule_based', outp
     run_forest_confidence_stage as well, with probability rows of 0 and confidence 0 at the masked pixels.  (A function of its
     own, like run_forest_confidence_stage: the signatures of run_classification_stage and run_forest_confidence_stage are the
     reference's plus a fixed set of keyword-only additions.)"""
-    return _run_classification(feature_file_path, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys,
-                               labeled_roi_file, strict_reference, ctx, bool(confidence), valid_mask=valid_mask)
+    req = ClassifyRequest(method=method, n_clusters=n_clusters, use_hierarchical_all=use_hierarchical_all, classifier=classifier,
+                          feature_keys=feature_keys, labeled_roi_file=labeled_roi_file, strict_reference=strict_reference,
+                          valid_mask=valid_mask, confidence=bool(confidence))
+    return _run_classification(feature_file_path, output_dir, req, ctx)
 
 
 IMPORTANCE_FILE = "rf_permutation_importance.json"
@@ -225,8 +265,9 @@ def run_forest_importance_stage(feature_file_path, roi_mask, output_dir="segment
     and random_state (42) — rsseg.forest_importance.permutation_importance_image, equal to scikit-learn's
     permutation_importance.  The ranking is printed as train_random_forest_classifier prints its importances.  Returns the
     label map."""
-    return _run_classification(feature_file_path, "random_forest", output_dir, use_hierarchical_all, 7, classifier, None,
-                               labeled_roi_file, False, ctx, confidence, np.asarray(roi_mask))
+    req = ClassifyRequest(method="random_forest", use_hierarchical_all=use_hierarchical_all, classifier=classifier,
+                          labeled_roi_file=labeled_roi_file, confidence=confidence, importance_mask=np.asarray(roi_mask))
+    return _run_classification(feature_file_path, output_dir, req, ctx)
 
 
 def run_forest_confidence_stage(feature_file_path, output_dir="segmentation_outputs", use_hierarchical_all=True, *, classifier=None,
@@ -237,8 +278,9 @@ def run_forest_confidence_stage(feature_file_path, output_dir="segmentation_outp
     metadata, <output_dir>/random_forest_confidence_map.tif (float64, LZW tiles).  Returns the label map.  (A function of
     its own: the signature of run_classification_stage is the reference's plus a fixed set of keyword-only additions.)
     On a scene with nodata: run_masked_classification_stage(..., 'random_forest', valid_mask=..., confidence=True)."""
-    return _run_classification(feature_file_path, "random_forest", output_dir, use_hierarchical_all, 7, classifier, None,
-                               labeled_roi_file, False, ctx, True)
+    req = ClassifyRequest(method="random_forest", use_hierarchical_all=use_hierarchical_all, classifier=classifier,
+                          labeled_roi_file=labeled_roi_file, confidence=True)
+    return _run_classification(feature_file_path, output_dir, req, ctx)
 
 
 KMEANS_SUMMARY_FILE = "kmeans_model_summary.json"
@@ -278,12 +320,11 @@ def run_kmeans_model_stage(feature_file_path, model_path, output_dir="segmentati
     np.save(os.path.join(output_dir, "classification_kmeans.npy"), out)
     _save_class_tif(out, feats, output_dir, "kmeans")
     np.save(os.path.join(output_dir, "kmeans_distance.npy"), dist.cpu().numpy().reshape(shape))
-    import json
     inertia = summary["inertia"]
-    with open(os.path.join(output_dir, KMEANS_SUMMARY_FILE), "w") as f:
-        json.dump({"model": os.path.basename(str(model_path)), "n_clusters": model.n_clusters, "n_features": model.n_features_in_,
-                   "counts": summary["counts"].tolist(), "inertia": inertia if np.isfinite(inertia) else None,
-                   "overflow": bool(summary["overflow"]), **extra}, f, indent=1)
+    _write_json(os.path.join(output_dir, KMEANS_SUMMARY_FILE),
+                {"model": os.path.basename(str(model_path)), "n_clusters": model.n_clusters, "n_features": model.n_features_in_,
+                 "counts": summary["counts"].tolist(), "inertia": inertia if np.isfinite(inertia) else None,
+                 "overflow": bool(summary["overflow"]), **extra})
     return out
 
 
@@ -338,175 +379,175 @@ def _load_normalised(feature_file_path, output_dir):
     return feats
 
 
-def _run_classification(feature_file_path, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys,
-                        labeled_roi_file, strict_reference, ctx, confidence, importance_mask=None,
-                        save_kmeans_model=None, valid_mask=None, ml_threshold=None, rule_image=False,
-                        fit_on_device=False) -> Optional[np.ndarray]:
+def _run_classification(feature_file_path, output_dir, req: ClassifyRequest, ctx: Optional[Context]) -> Optional[np.ndarray]:
+    """The classification stage behind run_classification_stage and its siblings: load, _classify, write the map and its products."""
     feats = _load_normalised(feature_file_path, output_dir)
     if feats is None:
         return None
-    if valid_mask is not None:
-        valid_mask = _check_valid_mask(valid_mask, (feats["height"], feats["width"]))
+    if req.valid_mask is not None:
+        req = replace(req, valid_mask=_check_valid_mask(req.valid_mask, (feats["height"], feats["width"])))
     from . import runtime as _rt
     prev_ctx = _rt._default_ctx
     if ctx is not None:   # the mirrors run on the process-wide context: lend them this one for the duration of the call
         _rt._default_ctx = ctx
     try:
-        extras = None
-        if (confidence or importance_mask is not None) and method in ("random_forest", "rf", "supervised"):
-            extras = {"want_confidence": bool(confidence), "importance_mask": importance_mask}
-        if save_kmeans_model and method == "kmeans":
-            extras = {"want_kmeans_model": True}
-        if method in GAUSS_METHODS:
-            extras = {"ml_threshold": ml_threshold, "want_rule_image": bool(rule_image)}
-            if fit_on_device:
-                extras["fit_on_device"] = True
-        out = _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys, labeled_roi_file,
-                        strict_reference, extras, valid_mask)
+        out, made = _classify(feats, output_dir, req)
     finally:
         _rt._default_ctx = prev_ctx
     if out is None:
         return None
+    method = req.method
     np.save(os.path.join(output_dir, f"classification_{method}.npy"), out)
     _save_class_tif(out, feats, output_dir, method)
-    if extras and "kmeans_model" in extras:
-        print(f"KMeans模型保存至: {extras['kmeans_model'].save(save_kmeans_model)}")
-    if extras and "proba" in extras:
-        np.save(os.path.join(output_dir, "rf_class_probabilities.npy"), extras["proba"])
-        np.save(os.path.join(output_dir, "rf_confidence.npy"), extras["confidence"])
+    if made.kmeans_model is not None:
+        print(f"KMeans模型保存至: {made.kmeans_model.save(req.save_kmeans_model)}")
+    if made.proba is not None:
+        np.save(os.path.join(output_dir, "rf_class_probabilities.npy"), made.proba)
+        np.save(os.path.join(output_dir, "rf_confidence.npy"), made.confidence)
         if all(feats.get(k) is not None for k in ("transform", "crs", "width", "height")):
             from .tiff import write_tiff
-            write_tiff(os.path.join(output_dir, f"{method}_confidence_map.tif"), extras["confidence"], transform=feats["transform"],
+            write_tiff(os.path.join(output_dir, f"{method}_confidence_map.tif"), made.confidence, transform=feats["transform"],
                        epsg=_epsg_of(feats["crs"]), geographic=_is_geographic(feats["crs"]), compress="lzw", tiled=True)
-    if extras and "gauss_model" in extras:
-        print(f"{method} 模型保存至: {extras['gauss_model'].save(os.path.join(output_dir, f'{method}_model.npz'))}")
-    if extras and "dist2" in extras:
-        np.save(os.path.join(output_dir, f"{method}_dist2.npy"), extras["dist2"])
-        np.save(os.path.join(output_dir, f"{method}_margin.npy"), extras["margin"])
-    if extras and "importance" in extras:
-        _save_importance(os.path.join(output_dir, IMPORTANCE_FILE), extras["importance"], extras["feature_names"])
+    if made.gauss_model is not None:
+        print(f"{method} 模型保存至: {made.gauss_model.save(os.path.join(output_dir, f'{method}_model.npz'))}")
+    if made.dist2 is not None:
+        np.save(os.path.join(output_dir, f"{method}_dist2.npy"), made.dist2)
+        np.save(os.path.join(output_dir, f"{method}_margin.npy"), made.margin)
+    if made.importance is not None:
+        _save_importance(os.path.join(output_dir, IMPORTANCE_FILE), made.importance, made.feature_names)
     return out
 
 
 def _save_importance(path: str, imp, names) -> None:
-    import json
-    with open(path, "w") as f:
-        json.dump({"feature_names": list(names), "importances_mean": imp["importances_mean"].tolist(),
-                   "importances_std": imp["importances_std"].tolist(), "importances": imp["importances"].tolist(),
-                   "baseline_score": imp["baseline_score"], "n_samples": imp["n_samples"], "n_repeats": IMPORTANCE_REPEATS,
-                   "random_state": IMPORTANCE_SEED}, f, indent=1)
+    _write_json(path, {"feature_names": list(names), "importances_mean": imp["importances_mean"].tolist(),
+                       "importances_std": imp["importances_std"].tolist(), "importances": imp["importances"].tolist(),
+                       "baseline_score": imp["baseline_score"], "n_samples": imp["n_samples"], "n_repeats": IMPORTANCE_REPEATS,
+                       "random_state": IMPORTANCE_SEED})
     mean = imp["importances_mean"]
     print(f"随机森林置换特征重要性 ({imp['n_samples']} 个标注像素, 基准准确率 {imp['baseline_score']:.4f}):")
     for i in np.argsort(mean)[::-1]:
         print(f"    特征 '{names[i]}': {mean[i]:.4f}")
 
 
-def _classify(feats, method, output_dir, use_hierarchical_all, n_clusters, classifier, feature_keys, labeled_roi_file, strict_reference,
-              extras=None, valid_mask=None):
-    """The dispatch of scripts/3_classification.py:335-488 on a normalised feature dictionary -> label map or None.
-    valid_mask: None, or an (H, W) array, non-zero = valid (run_classification_stage): class 0 at the other pixels.
-    extras: None, or a dict of requests the forest branch answers in place: 'want_confidence' -> 'proba' (H, W, C) and
-    'confidence' (H, W); 'importance_mask' (an (H, W) label mask) -> 'importance' and 'feature_names'; the kmeans branch
-    answers 'want_kmeans_model' -> 'kmeans_model' (the KMeansModel of the fit that made the labels)."""
-    from modules.features.extract import (prepare_training_samples, rule_based_classification, supervised_classification_predict,
-                                          train_random_forest_classifier, unsupervised_kmeans_classification)
+def _classify(feats, output_dir, req: ClassifyRequest) -> Tuple[Optional[np.ndarray], ClassifyProducts]:
+    """The dispatch of scripts/3_classification.py:335-488 on a normalised feature dictionary -> (label map or None, what the
+    branch made beside it).  req.valid_mask is None or an (H, W) array already checked against the features' shape."""
+    branch = _BRANCHES.get(req.method)
+    if branch is None:
+        print(f"错误: 不支持的分割方法 '{req.method}'")
+        return None, ClassifyProducts()
+    return branch(feats, output_dir, req)
+
+
+def _classify_rules(feats, output_dir, req):
+    from modules.features.extract import rule_based_classification
+    rules = {}
+    for k in ("ndvi", "ndwi", "mndwi", "ndbi"):
+        v = feats.get(k)
+        if v is None:
+            v = feats.get(f"all_extracted_features_dict_{k}")
+        if v is not None:
+            rules[k] = v
+    rules["height"], rules["width"] = feats["height"], feats["width"]
+    out = rule_based_classification(rules)
+    if req.valid_mask is not None and out is not None:
+        out = np.where(req.valid_mask != 0, out, 0).astype(out.dtype)
+    return out, ClassifyProducts()
+
+
+def _classify_kmeans(feats, output_dir, req):
+    from modules.features.extract import unsupervised_kmeans_classification
+    keys = _kmeans_keys(feats, req.feature_keys, req.strict_reference)
+    if req.save_kmeans_model:   # the same call on the same planes, its model kept
+        from .kmeans_model import KMeansModel
+        model, labels = KMeansModel.fit_features(feats, req.n_clusters, keys, mask=req.valid_mask)
+        return (labels + 1).astype(np.uint8), ClassifyProducts(kmeans_model=model)
+    if req.valid_mask is not None:   # labels -1 at the masked pixels: class 0
+        from modules.features.extract import _select_planes
+        from .masked import kmeans_fit_predict_masked
+        planes, _ = _select_planes(feats, keys)
+        labels, _ = kmeans_fit_predict_masked([np.asarray(p) for p in planes], req.valid_mask, int(req.n_clusters))
+        return (labels.reshape(feats["height"], feats["width"]) + 1).astype(np.uint8), ClassifyProducts()
+    return (unsupervised_kmeans_classification(feats, req.n_clusters, keys) + 1).astype(np.uint8), ClassifyProducts()   # scripts/3:394
+
+
+def _classify_gaussian(feats, output_dir, req):
+    from modules.features.extract import prepare_training_samples
     shape = (feats["height"], feats["width"])
-    if method == "rule_based":
-        rules = {}
-        for k in ("ndvi", "ndwi", "mndwi", "ndbi"):
-            v = feats.get(k)
-            if v is None:
-                v = feats.get(f"all_extracted_features_dict_{k}")
-            if v is not None:
-                rules[k] = v
-        rules["height"], rules["width"] = shape
-        out = rule_based_classification(rules)
-        if valid_mask is not None and out is not None:
-            out = np.where(valid_mask != 0, out, 0).astype(out.dtype)
-        return out
-    if method == "kmeans":
-        keys = _kmeans_keys(feats, feature_keys, strict_reference)
-        if extras is not None and extras.get("want_kmeans_model"):   # the same call on the same planes, its model kept
-            from .kmeans_model import KMeansModel
-            extras["kmeans_model"], labels = KMeansModel.fit_features(feats, n_clusters, keys, mask=valid_mask)
-            return (labels + 1).astype(np.uint8)
-        if valid_mask is not None:   # labels -1 at the masked pixels: class 0
-            from modules.features.extract import _select_planes
-            from .masked import kmeans_fit_predict_masked
-            planes, _ = _select_planes(feats, keys)
-            labels, _ = kmeans_fit_predict_masked([np.asarray(p) for p in planes], valid_mask, int(n_clusters))
-            return (labels.reshape(shape) + 1).astype(np.uint8)
-        return (unsupervised_kmeans_classification(feats, n_clusters, keys) + 1).astype(np.uint8)   # scripts/3:394
-    if method in GAUSS_METHODS:
-        arr, names = _supervised_feature_array(feats, use_hierarchical_all, shape)
-        if arr is None:
-            return None
-        if not os.path.exists(labeled_roi_file):
-            print(f"错误: 监督分类所需的标签ROI文件 '{labeled_roi_file}' 未找到。")
-            return None
-        from .gaussian import STAGE_METHODS, GaussianClassifier
-        extras = {} if extras is None else extras
-        if extras.get("fit_on_device"):   # the classes' moments from the raster on the GPU (K24): no host sample matrix
-            from .tiff import read_tiff
-            roi = read_tiff(labeled_roi_file)[0]
-            if roi.shape != shape:
-                raise ValueError(f"标签ROI文件 '{labeled_roi_file}' (形状 {roi.shape}) 尺寸与特征数据 (期望的2D形状 {shape}) 不匹配。")
-            clf = GaussianClassifier(STAGE_METHODS[method], threshold=extras.get("ml_threshold")).fit_image(arr, roi, device=True)
+    roi_file = req.labeled_roi_file
+    arr, names = _supervised_feature_array(feats, req.use_hierarchical_all, shape)
+    if arr is None:
+        return None, ClassifyProducts()
+    if not os.path.exists(roi_file):
+        print(f"错误: 监督分类所需的标签ROI文件 '{roi_file}' 未找到。")
+        return None, ClassifyProducts()
+    from .gaussian import STAGE_METHODS, GaussianClassifier
+    if req.fit_on_device:   # the classes' moments from the raster on the GPU (K24): no host sample matrix
+        from .tiff import read_tiff
+        roi = read_tiff(roi_file)[0]
+        if roi.shape != shape:
+            raise ValueError(f"标签ROI文件 '{roi_file}' (形状 {roi.shape}) 尺寸与特征数据 (期望的2D形状 {shape}) 不匹配。")
+        clf = GaussianClassifier(STAGE_METHODS[req.method], threshold=req.ml_threshold).fit_image(arr, roi, device=True)
+    else:
+        X, y = prepare_training_samples(arr, roi_file)
+        clf = GaussianClassifier(STAGE_METHODS[req.method], threshold=req.ml_threshold).fit(X, y)
+    rule = bool(req.rule_image)
+    res = clf.predict_image(arr, mask=req.valid_mask, want_dist2=rule, want_margin=rule)
+    if rule:
+        return res[0], ClassifyProducts(gauss_model=clf, dist2=res[1], margin=res[2])
+    return res, ClassifyProducts(gauss_model=clf)
+
+
+def _classify_forest(feats, output_dir, req):
+    from modules.features.extract import prepare_training_samples, supervised_classification_predict, train_random_forest_classifier
+    classifier, roi_file, valid_mask, made = req.classifier, req.labeled_roi_file, req.valid_mask, ClassifyProducts()
+    arr, names = _supervised_feature_array(feats, req.use_hierarchical_all, (feats["height"], feats["width"]))
+    if arr is None:
+        return None, made
+    model_path = os.path.join(output_dir, RF_MODEL_FILE)
+    try:
+        import joblib
+        if classifier is None and os.path.exists(model_path):
+            print(f"加载已训练的随机森林模型: {model_path}")
+            classifier = joblib.load(model_path)
+        nf = getattr(classifier, "n_features_in_", None)
+        if classifier is not None and nf is not None and nf != arr.shape[-1]:
+            print(f"警告: 加载的分类器需要 {nf} 个特征，但准备的数据有 {arr.shape[-1]} 个。正在重新训练模型。")
+            classifier = None
+        if classifier is None:      # scripts/3:450-475: fit on the host from the label raster, cache the model
+            if not os.path.exists(roi_file):
+                print(f"错误: 监督分类所需的标签ROI文件 '{roi_file}' 未找到 (也没有可用的模型 '{model_path}')。")
+                return None, made
+            X, y = prepare_training_samples(arr, roi_file)
+            classifier = train_random_forest_classifier(X, y, feature_names_for_training=names)
+            joblib.dump(classifier, model_path)
+            print(f"随机森林模型训练并保存至: {model_path}")
+        if valid_mask is not None:
+            from .masked import forest_predict_masked
+            out = forest_predict_masked(classifier, arr, valid_mask, 0)
         else:
-            X, y = prepare_training_samples(arr, labeled_roi_file)
-            clf = GaussianClassifier(STAGE_METHODS[method], threshold=extras.get("ml_threshold")).fit(X, y)
-        rule = bool(extras.get("want_rule_image"))
-        res = clf.predict_image(arr, mask=valid_mask, want_dist2=rule, want_margin=rule)
-        extras["gauss_model"] = clf
-        if rule:
-            res, extras["dist2"], extras["margin"] = res
-        return res
-    if method in ("random_forest", "rf", "supervised"):
-        arr, names = _supervised_feature_array(feats, use_hierarchical_all, shape)
-        if arr is None:
-            return None
-        model_path = os.path.join(output_dir, RF_MODEL_FILE)
-        try:
-            import joblib
-            if classifier is None and os.path.exists(model_path):
-                print(f"加载已训练的随机森林模型: {model_path}")
-                classifier = joblib.load(model_path)
-            nf = getattr(classifier, "n_features_in_", None)
-            if classifier is not None and nf is not None and nf != arr.shape[-1]:
-                print(f"警告: 加载的分类器需要 {nf} 个特征，但准备的数据有 {arr.shape[-1]} 个。正在重新训练模型。")
-                classifier = None
-            if classifier is None:      # scripts/3:450-475: fit on the host from the label raster, cache the model
-                if not os.path.exists(labeled_roi_file):
-                    print(f"错误: 监督分类所需的标签ROI文件 '{labeled_roi_file}' 未找到 (也没有可用的模型 '{model_path}')。")
-                    return None
-                X, y = prepare_training_samples(arr, labeled_roi_file)
-                classifier = train_random_forest_classifier(X, y, feature_names_for_training=names)
-                joblib.dump(classifier, model_path)
-                print(f"随机森林模型训练并保存至: {model_path}")
+            out = supervised_classification_predict(arr, classifier)
+        if req.confidence:   # the same pixels as the label map saw: NaN -> 0 (extract.py:690-719)
+            from .forest import image_proba_and_confidence
             if valid_mask is not None:
-                from .masked import forest_predict_masked
-                out = forest_predict_masked(classifier, arr, valid_mask, 0)
+                made.proba, made.confidence = image_proba_and_confidence(classifier, arr, mask=valid_mask)
             else:
-                out = supervised_classification_predict(arr, classifier)
-            if extras is not None and extras.get("want_confidence"):   # the same pixels as the label map saw: NaN -> 0 (extract.py:690-719)
-                from .forest import image_proba_and_confidence
-                if valid_mask is not None:
-                    extras["proba"], extras["confidence"] = image_proba_and_confidence(classifier, arr, mask=valid_mask)
-                else:
-                    extras["proba"], extras["confidence"] = image_proba_and_confidence(classifier, np.nan_to_num(arr, nan=0.0))
-            if extras is not None and extras.get("importance_mask") is not None:
-                from .forest_importance import permutation_importance_image
-                extras["importance"] = permutation_importance_image(classifier, arr, extras["importance_mask"],
-                                                                    n_repeats=IMPORTANCE_REPEATS, random_state=IMPORTANCE_SEED)
-                extras["feature_names"] = names
-            return out
-        except _rt_unsupported():
-            raise
-        except Exception as e:  # noqa: BLE001 — scripts/3:482-486 prints and returns
-            print(f"随机森林分类过程中发生错误: {e}")
-            return None
-    print(f"错误: 不支持的分割方法 '{method}'")
-    return None
+                made.proba, made.confidence = image_proba_and_confidence(classifier, np.nan_to_num(arr, nan=0.0))
+        if req.importance_mask is not None:
+            from .forest_importance import permutation_importance_image
+            made.importance = permutation_importance_image(classifier, arr, req.importance_mask,
+                                                           n_repeats=IMPORTANCE_REPEATS, random_state=IMPORTANCE_SEED)
+            made.feature_names = names
+        return out, made
+    except RssegUnsupported:
+        raise
+    except Exception as e:  # noqa: BLE001 — scripts/3:482-486 prints and returns
+        print(f"随机森林分类过程中发生错误: {e}")
+        return None, ClassifyProducts()
+
+
+_BRANCHES = {"rule_based": _classify_rules, "kmeans": _classify_kmeans, **dict.fromkeys(GAUSS_METHODS, _classify_gaussian),
+             **dict.fromkeys(("random_forest", "rf", "supervised"), _classify_forest)}
 
 
 def _supervised_feature_array(feats, use_hierarchical_all, shape):
@@ -529,9 +570,28 @@ def _supervised_feature_array(feats, use_hierarchical_all, shape):
     return arr, names
 
 
-def _rt_unsupported():
-    from .runtime import RssegUnsupported
-    return RssegUnsupported
+def _supervised_stack(feature_file_path, output_dir, who):
+    """The feature file's (H, W, F) stack as the supervised classifiers read it -> ((H, W), stack, feature names); a file without one
+    is refused in the name of the stage `who`.  output_dir exists afterwards (_load_normalised makes it)."""
+    feats = _load_normalised(feature_file_path, output_dir)
+    if feats is None:
+        raise ValueError(f"{who}: {feature_file_path} holds no feature stack")
+    shape = (int(feats["height"]), int(feats["width"]))
+    arr, names = _supervised_feature_array(feats, True, shape)
+    if arr is None:
+        raise ValueError(f"{who}: {feature_file_path} holds no plane of shape {shape}")
+    return shape, arr, names
+
+
+def _write_class_tif(path, class_map, transform, crs) -> None:
+    """A class map beside the raw one: uint8, nodata 0, LZW tiles; georeferenced when transform and crs are given."""
+    from .tiff import write_tiff
+    write_tiff(path, class_map, transform=transform, epsg=_epsg_of(crs), geographic=_is_geographic(crs), nodata=0, compress="lzw", tiled=True)
+
+
+def _write_json(path, obj) -> None:
+    with open(path, "w") as f:
+        json.dump(obj, f, indent=1)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -553,7 +613,9 @@ def run_scripts_2_3(image_path: str, output_dir: str, classify: Optional[str] = 
     importance: with classify='random_forest', a ROI mask (.npy / .tif, read as `evaluate` reads its mask): the permutation
     importance of the forest's features over its labelled pixels, written as segmentation_results/rf_permutation_importance.json
     (run_forest_importance_stage)."""
-    return _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters, ctx, evaluate, raw, confidence, importance)
+    opts = RunOptions(classify=classify, preprocessing=preprocessing, n_clusters=n_clusters, evaluate=evaluate, raw=raw, confidence=confidence,
+                      importance=importance)
+    return _run_scripts_2_3(image_path, output_dir, opts, ctx)
 
 
 MASK_NODATA_FROM_TAG = "tag"   # --mask-nodata without a value
@@ -593,9 +655,7 @@ def run_postclass_stage(class_map, output_dir: str, method: str, min_area: int =
     <method>_classification_map_clean.tif (uint8, nodata 0, LZW tiles; georeferenced when transform and crs are given) and
     postclass_stats.json (the parameters, clean_class_map's statistics, pixels per class before and after).
     Returns (clean map, that dictionary)."""
-    import json
     from . import postclass as PC
-    from .tiff import write_tiff
     raw = PC.check_class_map(class_map)
     if _is_device_tensor(raw):
         raw = raw.cpu().numpy()
@@ -603,14 +663,12 @@ def run_postclass_stage(class_map, output_dir: str, method: str, min_area: int =
                                    ctx=ctx, return_stats=True)
     os.makedirs(output_dir, exist_ok=True)
     np.save(os.path.join(output_dir, f"classification_{method}_clean.npy"), clean)
-    write_tiff(os.path.join(output_dir, f"{method}_classification_map_clean.tif"), clean, transform=transform, epsg=_epsg_of(crs),
-               geographic=_is_geographic(crs), nodata=0, compress="lzw", tiled=True)
+    _write_class_tif(os.path.join(output_dir, f"{method}_classification_map_clean.tif"), clean, transform, crs)
     stats: Dict[str, object] = {"method": method, "min_area": int(min_area), "window": int(window or 3),
                                 "majority_iterations": int(majority_iterations if window else 0), "nodata": int(nodata), **st,
                                 "class_counts_before": {str(k): v for k, v in PC.class_counts(raw).items()},
                                 "class_counts_after": {str(k): v for k, v in PC.class_counts(clean).items()}}
-    with open(os.path.join(output_dir, POSTCLASS_STATS_FILE), "w") as f:
-        json.dump(stats, f, indent=1)
+    _write_json(os.path.join(output_dir, POSTCLASS_STATS_FILE), stats)
     return clean, stats
 
 
@@ -633,15 +691,8 @@ def run_signatures_stage(feature_file_path, label_map, output_dir: str, method: 
     scenes merge) and separability_<method>.json (separability_report: Jeffries-Matusita and transformed divergence, the least
     separable pair, per class the count, mean and standard deviation; a class whose covariance is singular is named under
     "error" in place of the matrices).  Returns (ClassMoments, that dictionary)."""
-    import json
     from . import signatures as SIG
-    feats = _load_normalised(feature_file_path, output_dir)
-    if feats is None:
-        raise ValueError(f"run_signatures_stage: {feature_file_path} holds no feature stack")
-    shape = (int(feats["height"]), int(feats["width"]))
-    arr, names = _supervised_feature_array(feats, True, shape)
-    if arr is None:
-        raise ValueError(f"run_signatures_stage: {feature_file_path} holds no plane of shape {shape}")
+    shape, arr, names = _supervised_stack(feature_file_path, output_dir, "run_signatures_stage")
     lab = label_map.cpu().numpy() if _is_device_tensor(label_map) else np.asarray(label_map)
     if lab.shape != shape:
         raise ValueError(f"run_signatures_stage: the label raster is {lab.shape}, the features are {shape}")
@@ -650,10 +701,8 @@ def run_signatures_stage(feature_file_path, label_map, output_dir: str, method: 
         if np.any(l64 != np.floor(l64)) or np.any(l64 < 0) or np.any(l64 > 255):
             raise ValueError("run_signatures_stage: the labels must be integers in 0..255")
         lab = l64.astype(np.uint8)
-    if valid_mask is not None:
-        valid_mask = _check_valid_mask(valid_mask, shape)
+    valid_mask = _check_valid_mask(valid_mask, shape)
     mom = SIG.class_moments(np.asarray(arr, np.float32) if arr.dtype != np.uint8 else arr, lab, ignore=ignore, mask=valid_mask, ctx=ctx)
-    os.makedirs(output_dir, exist_ok=True)
     mom.save(os.path.join(output_dir, f"signatures_{method}.npz"))
     try:
         report = SIG.separability_report(mom)
@@ -661,8 +710,7 @@ def run_signatures_stage(feature_file_path, label_map, output_dir: str, method: 
         report = SIG.separability_report(mom, kinds=())
         report["error"] = str(e)
     report = {"method": method, "feature_names": list(names), **report}
-    with open(os.path.join(output_dir, f"separability_{method}.json"), "w") as f:
-        json.dump(report, f, indent=1)
+    _write_json(os.path.join(output_dir, f"separability_{method}.json"), report)
     return mom, report
 
 
@@ -677,16 +725,8 @@ def run_segment_stage(feature_file_path, class_map, output_dir: str, method: str
     (the parameters, n_segments, n_iter, n_regrown, the smallest / median / largest area) and, with object_based,
     classification_<method>_objects.npy and <method>_classification_map_objects.tif (uint8, nodata 0, LZW tiles).
     Returns (segments, that dictionary, object map or None)."""
-    import json
     from . import segment as SG
-    from .tiff import write_tiff
-    feats = _load_normalised(feature_file_path, output_dir)
-    if feats is None:
-        raise ValueError(f"run_segment_stage: {feature_file_path} holds no feature stack")
-    shape = (int(feats["height"]), int(feats["width"]))
-    arr, names = _supervised_feature_array(feats, True, shape)
-    if arr is None:
-        raise ValueError(f"run_segment_stage: {feature_file_path} holds no plane of shape {shape}")
+    _, arr, names = _supervised_stack(feature_file_path, output_dir, "run_segment_stage")
     used = min(arr.shape[-1], SG.MAX_PLANES)
     if used < arr.shape[-1]:
         print(f"segments: the feature stack has {arr.shape[-1]} planes, the first {used} are segmented ({', '.join(names[:used])})")
@@ -697,17 +737,14 @@ def run_segment_stage(feature_file_path, class_map, output_dir: str, method: str
                                 "masked_pixels": int((segments == 0).sum()),
                                 "area_min": int(area.min()) if area.size else 0, "area_median": float(np.median(area)) if area.size else 0.0,
                                 "area_max": int(area.max()) if area.size else 0, "object_based": bool(object_based)}
-    os.makedirs(output_dir, exist_ok=True)
     np.save(os.path.join(output_dir, "segments.npy"), segments)
     objects = None
     if object_based:
         objects = SG.object_classify(segments, class_map, nodata=nodata, ctx=ctx)
         np.save(os.path.join(output_dir, f"classification_{method}_objects.npy"), objects)
-        write_tiff(os.path.join(output_dir, f"{method}_classification_map_objects.tif"), objects, transform=transform, epsg=_epsg_of(crs),
-                   geographic=_is_geographic(crs), nodata=0, compress="lzw", tiled=True)
+        _write_class_tif(os.path.join(output_dir, f"{method}_classification_map_objects.tif"), objects, transform, crs)
         stats["pixels_changed_by_objects"] = int((objects != np.asarray(class_map)).sum())
-    with open(os.path.join(output_dir, SEGMENT_STATS_FILE), "w") as f:
-        json.dump(stats, f, indent=1)
+    _write_json(os.path.join(output_dir, SEGMENT_STATS_FILE), stats)
     return segments, stats, objects
 
 
@@ -725,19 +762,12 @@ def run_object_features_stage(feature_file_path, segments, output_dir: str, meth
     classification_<method>_object_features.npy, <method>_classification_map_object_features.tif (uint8, nodata 0, LZW tiles)
     and an "object_features" entry in segment_stats.json (n_train, classes, columns).
     Returns (object map, rsseg.objects.ObjectClassification, that entry)."""
-    import json
     from . import objects as OB
     from . import segment as SG
-    from .tiff import read_tiff, write_tiff
+    from .tiff import read_tiff
     if method not in OB.FOREST_METHODS and method not in OB.GAUSS_METHODS:
         raise ValueError(f"run_object_features_stage: method {method!r} is not a supervised classifier")
-    feats = _load_normalised(feature_file_path, output_dir)
-    if feats is None:
-        raise ValueError(f"run_object_features_stage: {feature_file_path} holds no feature stack")
-    shape = (int(feats["height"]), int(feats["width"]))
-    arr, names = _supervised_feature_array(feats, True, shape)
-    if arr is None:
-        raise ValueError(f"run_object_features_stage: {feature_file_path} holds no plane of shape {shape}")
+    shape, arr, names = _supervised_stack(feature_file_path, output_dir, "run_object_features_stage")
     if tuple(np.asarray(segments).shape) != shape:
         raise ValueError(f"run_object_features_stage: the segment map is {tuple(np.asarray(segments).shape)}, the features are {shape}")
     if not os.path.exists(labeled_roi_file):
@@ -746,8 +776,7 @@ def run_object_features_stage(feature_file_path, segments, output_dir: str, meth
     roi = roi[0] if roi.ndim == 3 else roi
     if roi.shape != shape:
         raise ValueError(f"标签ROI文件 '{labeled_roi_file}' (形状 {roi.shape}) 尺寸与特征数据 (期望的2D形状 {shape}) 不匹配。")
-    if valid_mask is not None:
-        valid_mask = _check_valid_mask(valid_mask, shape)
+    valid_mask = _check_valid_mask(valid_mask, shape)
     used = min(arr.shape[-1], SG.MAX_PLANES)
     planes = [np.ascontiguousarray(arr[..., i]) if arr.dtype == np.uint8 else np.ascontiguousarray(arr[..., i], dtype=np.float32) for i in range(used)]
     of = OB.object_features(segments, planes, names=names[:used], stats=("mean", "std"), shape=False, mask=valid_mask, ctx=ctx)
@@ -755,11 +784,9 @@ def run_object_features_stage(feature_file_path, segments, output_dir: str, meth
     class_map = res.class_map
     if valid_mask is not None:   # a segment map made under another mask: its pixels outside this one stay 0 all the same
         class_map = np.where(np.asarray(valid_mask) != 0, class_map, 0).astype(np.uint8)
-    os.makedirs(output_dir, exist_ok=True)
     np.savez(os.path.join(output_dir, OBJECT_FEATURES_FILE), table=of.table, X=of.X, columns=np.array(of.columns))
     np.save(os.path.join(output_dir, f"classification_{method}_object_features.npy"), class_map)
-    write_tiff(os.path.join(output_dir, f"{method}_classification_map_object_features.tif"), class_map, transform=transform, epsg=_epsg_of(crs),
-               geographic=_is_geographic(crs), nodata=0, compress="lzw", tiled=True)
+    _write_class_tif(os.path.join(output_dir, f"{method}_classification_map_object_features.tif"), class_map, transform, crs)
     entry: Dict[str, object] = {"method": method, "n_train": int(res.train_idx.size), "classes": [int(c) for c in np.unique(res.train_y)],
                                 "columns": list(res.columns), "planes_used": int(used)}
     spath = os.path.join(output_dir, SEGMENT_STATS_FILE)
@@ -768,8 +795,7 @@ def run_object_features_stage(feature_file_path, segments, output_dir: str, meth
         with open(spath) as f:
             stats = json.load(f)
     stats["object_features"] = entry
-    with open(spath, "w") as f:
-        json.dump(stats, f, indent=1)
+    _write_json(spath, stats)
     return class_map, res, entry
 
 
@@ -814,7 +840,6 @@ def run_isodata_stage(feature_file_path, output_dir="segmentation_outputs", *, n
     Writes <output_dir>/classification_isodata.npy (labels + 1 as uint8, 0 = nodata, the k-means layout),
     isodata_classification_map.tif with complete metadata, isodata_model.npz and isodata_history.json (the parameters, the
     per-iteration history, the pixels per cluster, n_left_out).  Returns the class map."""
-    import json
     from . import isodata as ISO
     feats = _load_normalised(feature_file_path, output_dir)
     if feats is None:
@@ -823,8 +848,7 @@ def run_isodata_stage(feature_file_path, output_dir="segmentation_outputs", *, n
     planes, names = isodata_planes(feats, feature_keys)
     if planes is None:
         return None
-    if valid_mask is not None:
-        valid_mask = _check_valid_mask(valid_mask, shape)
+    valid_mask = _check_valid_mask(valid_mask, shape)
     if model_path:
         model = ISO.IsodataModel.load(model_path)
         if model.feature_names is not None and model.feature_names != list(names):
@@ -842,66 +866,101 @@ def run_isodata_stage(feature_file_path, output_dir="segmentation_outputs", *, n
     np.save(os.path.join(output_dir, "classification_isodata.npy"), out)
     _save_class_tif(out, feats, output_dir, "isodata")
     model.save(os.path.join(output_dir, "isodata_model.npz"))
-    with open(os.path.join(output_dir, ISODATA_HISTORY_FILE), "w") as f:
-        json.dump({"k_target": int(n_clusters), "init_clusters": init_clusters, "max_std": max_std, "min_dist": min_dist, "min_size": min_size,
-                   "iterations": int(iterations), "change": change, "n_clusters": int(model.n_clusters), "feature_names": list(names),
-                   "counts": [int(c) for c in counts], **record}, f, indent=1)
+    _write_json(os.path.join(output_dir, ISODATA_HISTORY_FILE),
+                {"k_target": int(n_clusters), "init_clusters": init_clusters, "max_std": max_std, "min_dist": min_dist, "min_size": min_size,
+                 "iterations": int(iterations), "change": change, "n_clusters": int(model.n_clusters), "feature_names": list(names),
+                 "counts": [int(c) for c in counts], **record})
     return out
 
 
-def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters, ctx, evaluate, raw, confidence, importance,
-                     kmeans_model: Optional[str] = None, save_kmeans_model: Optional[str] = None, mask_nodata=None, sieve: int = 0,
-                     majority: int = 0, majority_iterations: int = 1, gcps=None, warp_order: int = 1, resampling: str = "nearest",
-                     pixel_size: Optional[float] = None, ml_threshold: Optional[float] = None, rule_image: bool = False, segment: int = 0,
-                     compactness: float = 10.0, segment_iterations: int = 10, object_based: bool = False, signatures: Optional[str] = None,
-                     fit_on_device: bool = False, object_features: bool = False, isodata: Optional[Dict[str, object]] = None) -> Dict[str, object]:
-    """run_scripts_2_3, and with classify='kmeans' the two model options of the command line: `save_kmeans_model` fits as
-    always and also writes the fitted model there (KMeansModel.save; the class map is the same file byte for byte),
-    `kmeans_model` applies a saved model and fits nothing (run_kmeans_model_stage).
-    mask_nodata (None, MASK_NODATA_FROM_TAG or a value; resolve_mask_nodata): the classifier sees only the pixels where every
-    band holds data; the mask is also written as <output_dir>/feature_outputs/valid_mask.npy and the class map is 0 elsewhere.
+@dataclass(frozen=True)
+class RunOptions:
+    """What one run of the driver is asked for beside the image, the output directory and the context: run_scripts_2_3's arguments
+    (described there) and the further options of the command line, with the defaults of a call that names none of them.
     gcps (with raw; beyond the reference): stage 1 rectifies the DN planes first (rsseg.georect, K21) and the feature stage goes
     on from the warped planes with the new shape and georeferencing.  With mask_nodata the warp's validity mask is AND-ed into
     the nodata mask of the warped DN planes (a bare --mask-nodata on a file without a GDAL_NODATA tag masks by the warp alone);
     without it the collar outside the source is classified as data, as it would be after a cv2.warpAffine.
-    ml_threshold, rule_image (classify in GAUSS_METHODS): the chi-square quantile beyond which a pixel stays unclassified, and
-    the rule images <method>_dist2.npy / <method>_margin.npy beside the class map.
-    segment (a grid step), compactness, segment_iterations, object_based: run_segment_stage on the feature file, under the same
-    valid mask; the object-based map is evaluated into <output_dir>/evaluation_results_objects.
-    signatures (SIGNATURES_OF_MAP or the path of an ROI raster): run_signatures_stage on the raw class map, or on the ROI's
-    training classes, under the same valid mask.  fit_on_device (classify in GAUSS_METHODS): the model is fitted from moments
-    taken on the GPU (GaussianClassifier.fit_image(..., device=True)).
-    object_features (with segment and a supervised classify): run_object_features_stage on the segments, with ./labeled_roi.tif
-    and under the same valid mask; its map is evaluated into <output_dir>/evaluation_results_object_features.
-    isodata (classify='isodata'): run_isodata_stage's keyword arguments beside n_clusters (init_clusters, max_std, min_dist, min_size,
-    iterations, change, model_path); the valid mask goes to the sweep as it is."""
+    segment, signatures and object_features run under the same valid mask as the classifier; the object-based map and the
+    object-features map are evaluated into <output_dir>/evaluation_results_objects and evaluation_results_object_features."""
+    classify: Optional[str] = None
+    preprocessing: bool = True
+    n_clusters: int = 7
+    evaluate: Optional[str] = None
+    raw: bool = False
+    confidence: bool = False
+    importance: Optional[str] = None
+    kmeans_model: Optional[str] = None   # classify='kmeans': apply this saved model and fit nothing (run_kmeans_model_stage)
+    save_kmeans_model: Optional[str] = None   # classify='kmeans': fit as always and also write the model there (KMeansModel.save; the same class map)
+    # None, MASK_NODATA_FROM_TAG or a value (resolve_mask_nodata): the classifier sees only the pixels where every band holds data;
+    # the mask is also written as <output_dir>/feature_outputs/valid_mask.npy and the class map is 0 elsewhere
+    mask_nodata: object = None
+    sieve: int = 0
+    majority: int = 0
+    majority_iterations: int = 1
+    gcps: Optional[str] = None
+    warp_order: int = 1
+    resampling: str = "nearest"
+    pixel_size: Optional[float] = None
+    ml_threshold: Optional[float] = None   # classify in GAUSS_METHODS: the chi-square quantile beyond which a pixel stays unclassified
+    rule_image: bool = False   # classify in GAUSS_METHODS: the rule images <method>_dist2.npy / <method>_margin.npy beside the class map
+    segment: int = 0   # a grid step: run_segment_stage on the feature file, with the three options that follow
+    compactness: float = 10.0
+    segment_iterations: int = 10
+    object_based: bool = False
+    signatures: Optional[str] = None   # SIGNATURES_OF_MAP or an ROI raster's path: run_signatures_stage on the raw class map, or on the ROI's training classes
+    fit_on_device: bool = False   # classify in GAUSS_METHODS: the model is fitted from moments taken on the GPU (fit_image(..., device=True))
+    object_features: bool = False   # with segment and a supervised classify: run_object_features_stage on the segments, with ./labeled_roi.tif
+    # classify='isodata': run_isodata_stage's keyword arguments beside n_clusters (init_clusters, max_std, min_dist, min_size, iterations,
+    # change, model_path); the valid mask goes to the sweep as it is
+    isodata: Optional[Dict[str, object]] = None
+
+
+def request_from_options(o: RunOptions, method: str, valid_mask, load_roi) -> ClassifyRequest:
+    """The request of the driver's classification step: every option goes to the method it belongs to and to no other.  The
+    --importance ROI is read here, by load_roi (ClassificationEvaluator._load) and so before the classification starts, for
+    'random_forest' without a valid mask only: a masked run ignores `importance` (the command line refuses the combination)."""
+    forest, gauss = method == "random_forest", method in GAUSS_METHODS
+    importance_mask = np.asarray(load_roi(o.importance)) if forest and o.importance and valid_mask is None else None
+    return ClassifyRequest(method=method, n_clusters=o.n_clusters, valid_mask=valid_mask, confidence=forest and bool(o.confidence),
+                           importance_mask=importance_mask, save_kmeans_model=o.save_kmeans_model if method == "kmeans" else None,
+                           ml_threshold=o.ml_threshold if gauss else None, rule_image=gauss and bool(o.rule_image),
+                           fit_on_device=gauss and bool(o.fit_on_device))
+
+
+def _evaluate_into(ev, class_map, roi_path, out_dir):   # -> (metrics, cluster mapping)
+    return ev.evaluate_maps(class_map, ev.load_roi_mask(roi_path), out_dir)
+
+
+def _run_scripts_2_3(image_path, output_dir, o: RunOptions, ctx: Optional[Context]) -> Dict[str, object]:
+    """run_scripts_2_3 with every option of the command line (RunOptions)."""
     valid_mask = None
-    if raw:
+    if o.raw:
         from .preprocess import run_preprocessing_stage
         pdir = os.path.join(output_dir, "preprocessed")
         stem = os.path.splitext(os.path.basename(image_path))[0]
         ppath = os.path.join(pdir, f"{stem}_preprocessed.tif")
-        if gcps is None:
+        if o.gcps is None:
             ppath, dev, (h, w), geo = run_preprocessing_stage(image_path, ppath, pdir, ctx=ctx, return_device=True)
         else:
             nodata = None
-            if mask_nodata is not None:
+            if o.mask_nodata is not None:
                 from .tiff import read_tiff_georef
                 tag = read_tiff_georef(image_path)["nodata"]
-                nodata = None if mask_nodata == MASK_NODATA_FROM_TAG and tag is None else resolve_mask_nodata(mask_nodata, tag)
-            ppath, dev, (h, w), geo, wmask = run_preprocessing_stage(image_path, ppath, pdir, ctx=ctx, return_device=True, gcps=gcps,
-                                                                     warp_order=warp_order, resampling=resampling, pixel_size=pixel_size,
+                nodata = None if o.mask_nodata == MASK_NODATA_FROM_TAG and tag is None else resolve_mask_nodata(o.mask_nodata, tag)
+            ppath, dev, (h, w), geo, wmask = run_preprocessing_stage(image_path, ppath, pdir, ctx=ctx, return_device=True, gcps=o.gcps,
+                                                                     warp_order=o.warp_order, resampling=o.resampling, pixel_size=o.pixel_size,
                                                                      nodata=nodata)
-            if mask_nodata is not None:
+            if o.mask_nodata is not None:
                 valid_mask = wmask.cpu().numpy().reshape(h, w)
                 print(f"valid pixels: {int(valid_mask.sum())} of {valid_mask.size} (warp mask"
                       + ("" if nodata is None else f" and nodata {nodata:g}") + ")")
-        fd, hier = _feature_extraction_on_device(ctx or default_context(), dev, h, w, preprocessing)
+        fd, hier = _feature_extraction_on_device(ctx or default_context(), dev, h, w, o.preprocessing)
     else:
         from .tiff import read_tiff, read_tiff_georef
         arr = read_tiff(image_path)
         geo = read_tiff_georef(image_path)
-        nodata = resolve_mask_nodata(mask_nodata, geo["nodata"])
+        nodata = resolve_mask_nodata(o.mask_nodata, geo["nodata"])
         if nodata is not None:
             valid_mask, n_valid = nodata_valid_mask(ctx or default_context(), arr, nodata)
             print(f"valid pixels: {n_valid} of {valid_mask.size} (nodata {nodata:g})")
@@ -915,93 +974,57 @@ def _run_scripts_2_3(image_path, output_dir, classify, preprocessing, n_clusters
                 b[b == geo["nodata"]] = np.nan
             bands.append(b)
         h, w = arr.shape[1:]
-        fd, hier = run_feature_extraction_stage(bands, preprocessing=preprocessing, ctx=ctx)
+        fd, hier = run_feature_extraction_stage(bands, preprocessing=o.preprocessing, ctx=ctx)
     crs = None if geo["epsg"] is None else f"EPSG:{geo['epsg']}"
     fdir = os.path.join(output_dir, "feature_outputs")
     paths = save_feature_outputs(fdir, fd, hier, h, w, geo["transform"], crs)
     res: Dict[str, object] = {"paths": paths, "shape": (h, w)}
-    if raw:
+    if o.raw:
         res["preprocessed"] = ppath
     if valid_mask is not None:
         res["valid_mask_path"] = os.path.join(fdir, "valid_mask.npy")
         np.save(res["valid_mask_path"], valid_mask)
+    if not o.classify:
+        return res
+    from .evaluate import ClassificationEvaluator
+    classify, evaluate = o.classify, o.evaluate
+    sdir = os.path.join(output_dir, "segmentation_results")
     if classify == "isodata":
-        sdir = os.path.join(output_dir, "segmentation_results")
-        res["class_map"] = run_isodata_stage(paths["pkl"], sdir, n_clusters=n_clusters, valid_mask=valid_mask, ctx=ctx, **(isodata or {}))
-    elif classify and valid_mask is not None:
-        sdir = os.path.join(output_dir, "segmentation_results")
-        if classify in GAUSS_METHODS:
-            res["class_map"] = _run_classification(paths["pkl"], classify, sdir, True, n_clusters, None, None, "labeled_roi.tif", False, ctx,
-                                                   False, valid_mask=valid_mask, ml_threshold=ml_threshold, rule_image=rule_image,
-                                                   fit_on_device=fit_on_device)
-        elif confidence and classify == "random_forest":
-            res["class_map"] = run_masked_classification_stage(paths["pkl"], classify, sdir, True, valid_mask=valid_mask, confidence=True, ctx=ctx)
-        elif kmeans_model and classify == "kmeans":
-            res["class_map"] = run_kmeans_model_stage(paths["pkl"], kmeans_model, sdir, ctx=ctx, valid_mask=valid_mask)
-        elif save_kmeans_model and classify == "kmeans":
-            res["class_map"] = _run_classification(paths["pkl"], classify, sdir, True, n_clusters, None, None, "labeled_roi.tif", False, ctx,
-                                                   False, save_kmeans_model=save_kmeans_model, valid_mask=valid_mask)
-        else:
-            res["class_map"] = run_masked_classification_stage(paths["pkl"], classify, sdir, True, valid_mask=valid_mask, n_clusters=n_clusters,
-                                                               ctx=ctx)
-    elif classify:
-        sdir = os.path.join(output_dir, "segmentation_results")
-        if classify in GAUSS_METHODS:
-            res["class_map"] = _run_classification(paths["pkl"], classify, sdir, True, n_clusters, None, None, "labeled_roi.tif", False, ctx,
-                                                   False, ml_threshold=ml_threshold, rule_image=rule_image, fit_on_device=fit_on_device)
-        elif importance and classify == "random_forest":
-            from .evaluate import ClassificationEvaluator
-            res["class_map"] = run_forest_importance_stage(paths["pkl"], ClassificationEvaluator._load(importance), sdir, True,
-                                                           confidence=confidence, ctx=ctx)
-        elif confidence and classify == "random_forest":
-            res["class_map"] = run_forest_confidence_stage(paths["pkl"], sdir, True, ctx=ctx)
-        elif kmeans_model and classify == "kmeans":
-            res["class_map"] = run_kmeans_model_stage(paths["pkl"], kmeans_model, sdir, ctx=ctx)
-        elif save_kmeans_model and classify == "kmeans":
-            res["class_map"] = _run_classification(paths["pkl"], classify, sdir, True, n_clusters, None, None, "labeled_roi.tif", False, ctx,
-                                                   False, save_kmeans_model=save_kmeans_model)
-        else:
-            res["class_map"] = run_classification_stage(paths["pkl"], classify, sdir, True, n_clusters=n_clusters, ctx=ctx)
-    if classify:
-        res["segmentation_dir"] = sdir
-        if evaluate and res["class_map"] is not None:
-            from .evaluate import ClassificationEvaluator
-            ev = ClassificationEvaluator(ctx)
-            edir = os.path.join(output_dir, "evaluation_results")
-            res["metrics"], res["cluster_mapping"] = ev.evaluate_maps(res["class_map"], ev.load_roi_mask(evaluate), edir)
-            res["evaluation_dir"] = edir
-        if (sieve or majority) and res["class_map"] is not None:
-            # sieve / majority: the cleaned map beside the raw one (whose files and evaluation stay byte for byte what they are)
-            res["class_map_clean"], res["postclass_stats"] = run_postclass_stage(res["class_map"], sdir, classify, sieve, majority, majority_iterations,
-                                                                                 transform=geo["transform"], crs=crs, ctx=ctx)
+        cm = run_isodata_stage(paths["pkl"], sdir, n_clusters=o.n_clusters, valid_mask=valid_mask, ctx=ctx, **(o.isodata or {}))
+    elif classify == "kmeans" and o.kmeans_model:
+        cm = run_kmeans_model_stage(paths["pkl"], o.kmeans_model, sdir, ctx=ctx, valid_mask=valid_mask)
+    else:
+        cm = _run_classification(paths["pkl"], sdir, request_from_options(o, classify, valid_mask, ClassificationEvaluator._load), ctx)
+    res["class_map"], res["segmentation_dir"] = cm, sdir
+    if cm is None:   # the classifier printed why it made no map: nothing follows
+        return res
+    georef = dict(transform=geo["transform"], crs=crs, ctx=ctx)
+    if evaluate:
+        ev = ClassificationEvaluator(ctx)
+        res["evaluation_dir"] = edir = os.path.join(output_dir, "evaluation_results")
+        res["metrics"], res["cluster_mapping"] = _evaluate_into(ev, cm, evaluate, edir)
+    if o.sieve or o.majority:
+        # sieve / majority: the cleaned map beside the raw one (whose files and evaluation stay byte for byte what they are)
+        res["class_map_clean"], res["postclass_stats"] = run_postclass_stage(cm, sdir, classify, o.sieve, o.majority, o.majority_iterations, **georef)
+        if evaluate:
+            res["evaluation_dir_clean"] = cdir = os.path.join(output_dir, "evaluation_results_clean")
+            res["metrics_clean"], _ = _evaluate_into(ev, res["class_map_clean"], evaluate, cdir)
+    if o.signatures:
+        sig_labels = cm if o.signatures == SIGNATURES_OF_MAP else ClassificationEvaluator._load(o.signatures)
+        res["signatures"], res["separability"] = run_signatures_stage(paths["pkl"], sig_labels, sdir, classify, valid_mask=valid_mask, ctx=ctx)
+    if o.segment:
+        # superpixels, and the class map voted per superpixel, beside the raw map (whose files stay byte for byte what they are)
+        res["segments"], res["segment_stats"], res["class_map_objects"] = run_segment_stage(
+            paths["pkl"], cm, sdir, classify, o.segment, o.compactness, o.segment_iterations, o.object_based, valid_mask=valid_mask, **georef)
+        if evaluate and o.object_based:
+            res["evaluation_dir_objects"] = odir = os.path.join(output_dir, "evaluation_results_objects")
+            res["metrics_objects"], _ = _evaluate_into(ev, res["class_map_objects"], evaluate, odir)
+        if o.object_features:
+            res["class_map_object_features"], res["object_classification"], res["object_features_stats"] = run_object_features_stage(
+                paths["pkl"], res["segments"], sdir, classify, labeled_roi_file="labeled_roi.tif", valid_mask=valid_mask, **georef)
             if evaluate:
-                cdir = os.path.join(output_dir, "evaluation_results_clean")
-                res["metrics_clean"], _ = ev.evaluate_maps(res["class_map_clean"], ev.load_roi_mask(evaluate), cdir)
-                res["evaluation_dir_clean"] = cdir
-        if signatures and res["class_map"] is not None:
-            if signatures == SIGNATURES_OF_MAP:
-                sig_labels = res["class_map"]
-            else:
-                from .evaluate import ClassificationEvaluator
-                sig_labels = ClassificationEvaluator._load(signatures)
-            res["signatures"], res["separability"] = run_signatures_stage(paths["pkl"], sig_labels, sdir, classify, valid_mask=valid_mask, ctx=ctx)
-        if segment and res["class_map"] is not None:
-            # superpixels, and the class map voted per superpixel, beside the raw map (whose files stay byte for byte what they are)
-            res["segments"], res["segment_stats"], res["class_map_objects"] = run_segment_stage(
-                paths["pkl"], res["class_map"], sdir, classify, segment, compactness, segment_iterations, object_based, valid_mask=valid_mask,
-                transform=geo["transform"], crs=crs, ctx=ctx)
-            if evaluate and object_based:
-                odir = os.path.join(output_dir, "evaluation_results_objects")
-                res["metrics_objects"], _ = ev.evaluate_maps(res["class_map_objects"], ev.load_roi_mask(evaluate), odir)
-                res["evaluation_dir_objects"] = odir
-            if object_features:
-                res["class_map_object_features"], res["object_classification"], res["object_features_stats"] = run_object_features_stage(
-                    paths["pkl"], res["segments"], sdir, classify, labeled_roi_file="labeled_roi.tif", valid_mask=valid_mask,
-                    transform=geo["transform"], crs=crs, ctx=ctx)
-                if evaluate:
-                    fdir_ = os.path.join(output_dir, "evaluation_results_object_features")
-                    res["metrics_object_features"], _ = ev.evaluate_maps(res["class_map_object_features"], ev.load_roi_mask(evaluate), fdir_)
-                    res["evaluation_dir_object_features"] = fdir_
+                res["evaluation_dir_object_features"] = fdir_ = os.path.join(output_dir, "evaluation_results_object_features")
+                res["metrics_object_features"], _ = _evaluate_into(ev, res["class_map_object_features"], evaluate, fdir_)
     return res
 
 
@@ -1152,61 +1175,67 @@ def build_parser():
     return ap
 
 
-def main(argv=None) -> int:
-    ap = build_parser()
-    a = parse_args(ap, argv)
+def options_from_args(a) -> RunOptions:
+    """The parsed command line (parse_args) as RunOptions.  The defaults the parser leaves at None, so that parse_args can tell
+    a given option from one left out (--compactness, --segment-iterations, --isodata-*), are filled in here."""
     iso = None
     if a.classify == "isodata":
         iso = {k: (d if getattr(a, f"isodata_{k}") is None else getattr(a, f"isodata_{k}")) for k, d in ISODATA_DEFAULTS.items()}
         iso["model_path"] = a.isodata_model
-    res = _run_scripts_2_3(a.image, a.output_dir, a.classify, not a.no_preprocessing, a.n_clusters, None, a.evaluate, a.raw, a.confidence,
-                           a.importance, a.kmeans_model, a.save_kmeans_model, a.mask_nodata, a.sieve, a.majority, a.majority_iterations,
-                           gcps=a.gcps, warp_order=a.warp_order, resampling=a.resampling, pixel_size=a.pixel_size, ml_threshold=a.ml_threshold,
-                           rule_image=a.rule_image, segment=a.segment, compactness=10.0 if a.compactness is None else a.compactness,
-                           segment_iterations=10 if a.segment_iterations is None else a.segment_iterations, object_based=a.object_based,
-                           signatures=a.signatures, fit_on_device=a.fit_on_device, object_features=a.object_features, isodata=iso)
+    return RunOptions(classify=a.classify, preprocessing=not a.no_preprocessing, n_clusters=a.n_clusters, evaluate=a.evaluate, raw=a.raw,
+                      confidence=a.confidence, importance=a.importance, kmeans_model=a.kmeans_model, save_kmeans_model=a.save_kmeans_model,
+                      mask_nodata=a.mask_nodata, sieve=a.sieve, majority=a.majority, majority_iterations=a.majority_iterations, gcps=a.gcps,
+                      warp_order=a.warp_order, resampling=a.resampling, pixel_size=a.pixel_size, ml_threshold=a.ml_threshold,
+                      rule_image=a.rule_image, segment=a.segment, compactness=10.0 if a.compactness is None else a.compactness,
+                      segment_iterations=10 if a.segment_iterations is None else a.segment_iterations, object_based=a.object_based,
+                      signatures=a.signatures, fit_on_device=a.fit_on_device, object_features=a.object_features, isodata=iso)
+
+
+def _print_report(res, a) -> None:
+    """What the command line prints of _run_scripts_2_3's result."""
+    sdir = res.get("segmentation_dir")
+
+    def accuracy(of, key):
+        if f"metrics{key}" in res:
+            m = res[f"metrics{key}"]
+            print(f"evaluation{of}: OA {m['overall_accuracy'] * 100:.2f}%, kappa {m['kappa_coefficient']:.4f} -> {res[f'evaluation_dir{key}']}")
+
     if a.raw:
         print(f"preprocessed: {res['preprocessed']}")
     for k, v in res["paths"].items():
         print(f"{k}: {v}")
-    if a.classify:
-        cm = res.get("class_map")
-        print(f"class map: {None if cm is None else (cm.shape, np.unique(cm).tolist())} -> {res['segmentation_dir']}")
-        if "metrics" in res:
-            m = res["metrics"]
-            print(f"evaluation: OA {m['overall_accuracy'] * 100:.2f}%, kappa {m['kappa_coefficient']:.4f} -> {res['evaluation_dir']}")
-        if "postclass_stats" in res:
-            s = res["postclass_stats"]
-            print(f"cleaned map: {s['removed']} pixels sieved out, {s['filled']} filled, {s['left_as_nodata']} left as nodata, "
-                  f"majority passes changed {s['changed']} -> {res['segmentation_dir']}")
-        if "metrics_clean" in res:
-            m = res["metrics_clean"]
-            print(f"evaluation of the cleaned map: OA {m['overall_accuracy'] * 100:.2f}%, kappa {m['kappa_coefficient']:.4f} -> {res['evaluation_dir_clean']}")
-        if "segment_stats" in res:
-            s = res["segment_stats"]
-            print(f"segments: {s['n_segments']} superpixels of {s['area_min']} .. {s['area_max']} pixels after {s['n_iter']} iterations, "
-                  f"{s['n_regrown']} pixels regrown -> {res['segmentation_dir']}")
-        if "separability" in res:
-            s = res["separability"]
-            worst = (s.get("jm") or {}).get("least_separable")
-            print(f"signatures: {len(s['classes'])} classes"
-                  + (f", least separable {worst['classes']} (JM {worst['value']:.4f})" if worst else "") + f" -> {res['segmentation_dir']}")
-        if "metrics_objects" in res:
-            m = res["metrics_objects"]
-            print(f"evaluation of the object-based map: OA {m['overall_accuracy'] * 100:.2f}%, kappa {m['kappa_coefficient']:.4f} -> "
-                  f"{res['evaluation_dir_objects']}")
-        if "object_features_stats" in res:
-            s = res["object_features_stats"]
-            print(f"object features: {len(s['columns'])} columns, {s['n_train']} training superpixels of classes {s['classes']} -> "
-                  f"{res['segmentation_dir']}")
-        if "metrics_object_features" in res:
-            m = res["metrics_object_features"]
-            print(f"evaluation of the object-features map: OA {m['overall_accuracy'] * 100:.2f}%, kappa {m['kappa_coefficient']:.4f} -> "
-                  f"{res['evaluation_dir_object_features']}")
-        return 0 if cm is not None else 1
-    return 0
+    if not a.classify:
+        return
+    cm = res.get("class_map")
+    print(f"class map: {None if cm is None else (cm.shape, np.unique(cm).tolist())} -> {sdir}")
+    accuracy("", "")
+    if "postclass_stats" in res:
+        s = res["postclass_stats"]
+        print(f"cleaned map: {s['removed']} pixels sieved out, {s['filled']} filled, {s['left_as_nodata']} left as nodata, "
+              f"majority passes changed {s['changed']} -> {sdir}")
+    accuracy(" of the cleaned map", "_clean")
+    if "segment_stats" in res:
+        s = res["segment_stats"]
+        print(f"segments: {s['n_segments']} superpixels of {s['area_min']} .. {s['area_max']} pixels after {s['n_iter']} iterations, "
+              f"{s['n_regrown']} pixels regrown -> {sdir}")
+    if "separability" in res:
+        s = res["separability"]
+        worst = (s.get("jm") or {}).get("least_separable")
+        print(f"signatures: {len(s['classes'])} classes"
+              + (f", least separable {worst['classes']} (JM {worst['value']:.4f})" if worst else "") + f" -> {sdir}")
+    accuracy(" of the object-based map", "_objects")
+    if "object_features_stats" in res:
+        s = res["object_features_stats"]
+        print(f"object features: {len(s['columns'])} columns, {s['n_train']} training superpixels of classes {s['classes']} -> {sdir}")
+    accuracy(" of the object-features map", "_object_features")
+
+
+def main(argv=None) -> int:
+    a = parse_args(build_parser(), argv)
+    res = _run_scripts_2_3(a.image, a.output_dir, options_from_args(a), None)
+    _print_report(res, a)
+    return 1 if a.classify and res.get("class_map") is None else 0
 
 
 if __name__ == "__main__":
-    import sys
-    sys.exit(main())
+    raise SystemExit(main())

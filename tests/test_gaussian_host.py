@@ -293,6 +293,6 @@ def test_stage_argument_errors(capsys):
 
 def test_unknown_method_still_prints_the_old_message(capsys):
     from rsseg import stages as S
-    out = S._classify({"height": 4, "width": 4}, "quadratic", "unused", True, 7, None, None, "labeled_roi.tif", False)
+    out, _ = S._classify({"height": 4, "width": 4}, "unused", S.ClassifyRequest(method="quadratic"))
     assert out is None
     assert "错误: 不支持的分割方法 'quadratic'" in capsys.readouterr().out
