@@ -2,7 +2,9 @@
 """Per-kernel comparison of two source trees' gfx950 code, without a GPU: every file is compiled to assembly with the
 Makefile's flags (hipcc --cuda-device-only -S) in both trees; per kernel the registers, LDS and scratch bytes of the
 code-object metadata, the waves per SIMD they allow, and whether the instruction sequences (comments, labels' directives and
-blank lines dropped) are equal.  A file that only the new tree has is listed by itself (`new_file`, no parent figures): its
+blank lines dropped) are equal.  Kernels are matched by their demangled name without the parameter list, so a kernel that gained a
+parameter is still compared with its parent; a kernel (an instantiation) that only the new tree has is listed by itself like
+the kernels of a new file (`new_kernel`).  A file that only the new tree has is listed by itself (`new_file`, no parent figures): its
 kernels are within the rules when they use no scratch.
 
   python profiles/code_object_diff.py <parent csrc dir> <new csrc dir> out.json k5_window.hip k13_texture.hip ..."""
@@ -35,10 +37,23 @@ def demangle(names):
     return dict(zip(names, p.stdout.split("\n")))
 
 
+def short(demangled):
+    return demangled.split("(")[0].replace("void ", "")
+
+
+def by_name(kn):
+    """mangled -> figures becomes demangled name without parameters -> figures"""
+    names = demangle(sorted(kn))
+    out = {short(names[m]): v for m, v in kn.items()}
+    assert len(out) == len(kn), "two kernels share a name"
+    return out
+
+
 def kernels(text):
     res = {}
     for m in re.finditer(r"^(\w+):\s*; @\1\n(.*?)^\s*\.end_amdhsa_kernel", text, re.S | re.M):
-        ins = [ln.split(";")[0].strip() for ln in m.group(2).split("\n")]
+        # a local label carries the number of its function in the file (.LBB12_3), which moves when a kernel is added before it
+        ins = [re.sub(r"\.L(\w+?)\d+_(\d+)", r".L\1_\2", ln.split(";")[0].strip()) for ln in m.group(2).split("\n")]
         res[m.group(1)] = {"ins": [i for i in ins if i and not i.startswith(".")]}
     for m in re.finditer(r"- \.agpr_count:.*?\.name:\s+(\w+).*?\.wavefront_size", text, re.S):
         blk, name = m.group(0), m.group(1)
@@ -82,13 +97,23 @@ def main():
                     table.append(row)
                     print("new  " + ("" if row["within_the_rules"] else "RULE ") + json.dumps(row))
                 continue
-            kp, kn = kernels(jobs[("parent", f)].result()), kernels(jobs[("new", f)].result())
-            assert set(kp) == set(kn), (f, set(kp) ^ set(kn))
-            names = demangle(sorted(kp))
+            kp, kn = by_name(kernels(jobs[("parent", f)].result())), by_name(kernels(jobs[("new", f)].result()))
+            assert set(kp) <= set(kn), (f, set(kp) - set(kn))
+            for name in sorted(set(kn) - set(kp)):      # an instantiation the parent does not have: the rule is no scratch
+                b = kn[name]
+                row = {"file": f, "kernel": name, "new_kernel": True}
+                for k in ("vgprs", "agprs", "sgprs", "lds", "scratch"):
+                    row[k] = [None, b[k]]
+                row["waves_per_simd"] = [None, waves_per_simd(b)]
+                row["instructions"] = [None, len(b["ins"])]
+                row["identical"] = None
+                row["within_the_rules"] = b["scratch"] == 0
+                table.append(row)
+                print("new  " + ("" if row["within_the_rules"] else "RULE ") + json.dumps(row))
             for name in sorted(kp):
                 a, b = kp[name], kn[name]
-                row = {"file": f, "kernel": names[name].split("(")[0].replace("void ", "")}
-                for k in ("vgprs", "sgprs", "lds", "scratch"):
+                row = {"file": f, "kernel": name}
+                for k in ("vgprs", "agprs", "sgprs", "lds", "scratch"):
                     row[k] = [a[k], b[k]]
                 row["waves_per_simd"] = [waves_per_simd(a), waves_per_simd(b)]
                 row["instructions"] = [len(a["ins"]), len(b["ins"])]

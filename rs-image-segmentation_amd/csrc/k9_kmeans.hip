@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_minmax(planes_t pl, int64_t n, 
 
 // ------------------------------------------------------------------------------------------------
 // mean pass: exact sums of fixed(xs) (the np.var numerators ride on the first k-means++ pass, km_kpp MODE 0).
-// grid (nblk, F); partial[f][blk] int64
+// grid (nblk, F); partial[f][blk] int64.  Serves 33 ... 64 planes; up to 32 planes take km_moment_chunk below.
 // ------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(KM_THREADS) void km_moment(planes_t pl, int64_t n, const scaler_t<T> *__restrict__ sp,
@@ -143,6 +144,67 @@ __global__ __launch_bounds__(KM_THREADS) void km_moment(planes_t pl, int64_t n, 
     if (threadIdx.x == 0) partial[(size_t)f * gridDim.x + blockIdx.x] = wg_sum(sacc);
 }
 
+// The mean pass on the chunk walk of the sweeps (F <= 32 planes; grid: nchunks): a lane reads all F planes of its pixels through the
+// rolling register set, as km_kpp MODE 0 does for the same bytes, instead of one plane per workgroup row as a stream of its own.
+// partial[f][chunk] int64; the sums are exact integers, so the column sums (km_reduce_cols) are the same bits in either form.
+template <typename T, int FR>
+__global__ __launch_bounds__(KM_THREADS) void km_moment_chunk(planes_t pl, int F, int64_t n, const scaler_t<T> *__restrict__ sp,
+                                                              long long *__restrict__ partial, int64_t nchunks)
+{
+    constexpr int PXL = vt<T>::PXL;
+    long long acc[FR];
+#pragma unroll
+    for (int f = 0; f < FR; f++) acc[f] = 0;
+    const int64_t chunk0 = (int64_t)blockIdx.x * km_chunk<T>();
+    // tile_body(ROLL): as in km_kpp
+    auto tile_body = [&](auto full_t, auto roll_c, T (&x)[FR][PXL], uint32_t off, uint32_t noff) {
+        const int64_t base = chunk0 + off;
+        constexpr bool FULL = decltype(full_t)::value;
+        constexpr int ROLL = decltype(roll_c)::value;
+        static_assert(ROLL == 0 || FULL, "only full tiles are requested ahead");
+        if constexpr (ROLL == 0) {
+#pragma unroll
+            for (int f = 0; f < FR; f++) {
+                if (f < F) load_pxf<T, FULL>(pl.p[f], base, n, x[f]);
+                else {
+#pragma unroll
+                    for (int p = 0; p < PXL; p++) x[f][p] = (T)0;
+                }
+            }
+        }
+#pragma unroll
+        for (int f = 0; f < FR; f++) {
+            if (f < F) {
+                const T sc = sp->scale[f], mnv = sp->minv[f];
+#pragma unroll
+                for (int p = 0; p < PXL; p++)
+                    if (FULL || base + p < n) acc[f] += to_fixed40((double)scaled<T>(x[f][p], sc, mnv));
+            }
+            if constexpr (ROLL == 1) load_pxq<T>(pl, F, f, chunk0, noff, x[f]);   // x[f] is free: the next tile's plane f
+        }
+    };
+    T x[FR][PXL];
+    auto at = [&](int t) { return (uint32_t)(t * km_tile<T>() + (int)threadIdx.x * PXL); };   // pixel offset in the chunk
+    const int nfull = km_full_tiles<T>(chunk0, n);
+    if (nfull > 0) {
+#pragma unroll
+        for (int f = 0; f < FR; f++) load_pxq<T>(pl, F, f, chunk0, at(0), x[f]);
+#pragma clang loop unroll(disable)
+        for (int t = 0; t + 1 < nfull; t++) tile_body(std::true_type{}, ic<1>(), x, at(t), at(t + 1));
+        tile_body(std::true_type{}, ic<2>(), x, at(nfull - 1), 0);
+    }
+    if (nfull < KM_TILES_PER_CHUNK && chunk0 + (int64_t)nfull * km_tile<T>() < n) tile_body(std::false_type{}, ic<0>(), x, at(nfull), 0);
+    __shared__ long long sacc[4][FR];
+#pragma unroll
+    for (int f = 0; f < FR; f++) {
+        long long s = wave_sum(acc[f]);
+        if (lane_id() == 0) sacc[threadIdx.x >> 6][f] = s;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < F)
+        partial[(size_t)threadIdx.x * nchunks + blockIdx.x] = sacc[0][threadIdx.x] + sacc[1][threadIdx.x] + sacc[2][threadIdx.x] + sacc[3][threadIdx.x];
+}
+
 // ------------------------------------------------------------------------------------------------
 // gather one scaled+centred row (F values of T) at local pixel index idx
 // ------------------------------------------------------------------------------------------------
@@ -165,7 +227,10 @@ __global__ void km_gather_row(planes_t pl, int F, int64_t idx, const scaler_t<T>
 //                           nothing is written per pixel.
 //   MODE 1 (round 1):       closest <- d2(pending, x)
 //   MODE 2 (later rounds):  closest <- min(closest, d2(pending, x))            (np.minimum of the chosen candidate)
-//   MODE 1/2 then:          partial[l][chunk] = sum fixed(min(closest, d2(cand_l, x)))   for l < L
+//   MODE 2 where kpp_recompute<T>(NL, FR) — the RECOMPUTE form (see below): closest is min_j d2(chosen_j, x) over the nrec
+//                           slots of chosT, kept in registers; the plane is not read, and written (all of it) only if `store`.
+//                           MODE 3 is then the plane round described as MODE 2 above.
+//   MODE 1/2/3 then:        partial[l][chunk] = sum fixed(min(closest, d2(cand_l, x)))   for l < L
 // One workgroup per chunk (km_chunk<T>() pixels), so partial[l][] is at once the potential of candidate l and,
 // for the candidate the host picks, the prefix table used to locate the next sampled pixel (np.searchsorted on
 // stable_cumsum, _kmeans.py:243-246): the chosen candidate's min-plane is never stored, the next round
@@ -177,6 +242,36 @@ __global__ void km_gather_row(planes_t pl, int F, int64_t idx, const scaler_t<T>
 // ------------------------------------------------------------------------------------------------
 #define KPP_MAXL 8
 #define KPP_STRIDE (KPP_MAXL + 1)
+
+// ------------------------------------------------------------------------------------------------
+// RECOMPUTE form of the sampling rounds.  After round c the closest-distance plane holds min_j d2(centre_j, x) over the c
+// centres chosen so far, and nothing else: every d2 is kpp_close of a float64 fma chain over the features, and a minimum over
+// non-negative, non-NaN values is exact and independent of order.  A round that already holds a pixel's F values in
+// registers can therefore re-derive the value from the CHOSEN-CENTRE TABLE (chosT: [F][KPP_MAXREC] float64 rows in candT's
+// per-feature layout, then the KPP_MAXREC squared norms; kc_mean_apply writes slot 0, the head of kc_targets slot c - 1 — the
+// values that also go into the pending column) instead of reading and rewriting 2 x sizeof(T) B/px: same bits, a read-only
+// sweep.  The price is c float64 dot products per pixel in round c, and the sweeps are close enough to the VALU issue limit that
+// it shows: at 16384^2 x 15 float32 planes a round costs 2.56 / 2.7 / 2.82 ms with 1 / 2 / 3 slots (the plane rounds: 2.9 - 3.2 ms),
+// about 0.11 ms per slot, and the round that stores the whole plane costs 3.1 - 3.2 ms whichever it is.  So the
+// table has KPP_MAXREC = 4 slots, which fit beside the candidates' accumulators in ONE feature loop at the occupancy of the plane
+// round (a form with 8 slots needs two loops over the planes to stay within the registers and ran 0.1 - 0.2 ms slower per round),
+// and the depth is 3: rounds 1 and 2 read 4F B/px and write nothing, round 3 takes over the whole-plane store of round 1.
+//   rounds c <= depth recompute (km_kpp MODE 2 with nrec = c slots of the table; km_kpp_chunkq likewise);
+//   k - 1 <= depth: the plane is never touched and not carved from the workspace;
+//   otherwise round `depth` also stores its values as the whole plane, and the later rounds are the plane rounds (MODE 3).
+// depth = KPP_RECOMPUTE unless RSSEG_KPP_RECOMPUTE=0..KPP_MAXREC (read at each fit; 0: plane rounds throughout) says otherwise.
+// Which instantiations have the form is decided by their code objects, as for lloyd_pipelined: no scratch, no fewer waves per
+// SIMD than the plane round of the same (T, NL, FR) (profiles/kpp_recompute_code_objects.json).  The others, and km_kpp_blk,
+// keep the plane rounds.
+// ------------------------------------------------------------------------------------------------
+#define KPP_MAXREC 4
+#define KPP_RECOMPUTE 3
+// <double, 4, 8> would lose a wave per SIMD (86 against 74 registers: 6 -> 5) and <float, 8, 32> its second one (262 + 6 against 238): they
+// keep the plane rounds; every other form holds its occupancy without scratch (<float, 4, 16>: 157 registers, 3 waves as before).
+template <typename T> constexpr bool kpp_recompute(int NL, int FR)
+{
+    return !(std::is_same<T, double>::value && NL == 4 && FR == 8) && !(std::is_same<T, float>::value && NL == 8 && FR == 32);
+}
 
 // Distance closing, written once for the five places that need it (the pending update and the candidate potentials of km_kpp
 // and km_kpp_blk, and km_kpp_chunkq, which re-derives what the next round will store): euclidean_distances' float64
@@ -195,10 +290,13 @@ template <typename T, int NL, int FR, int MODE>
 __global__ __launch_bounds__(KM_THREADS) void km_kpp(planes_t pl, int F, int64_t n, const scaler_t<T> *__restrict__ sp,
                                                      const double *__restrict__ candT, const double *__restrict__ cc, int L,
                                                      T *__restrict__ closest, unsigned long long *__restrict__ partial, int64_t nchunks,
-                                                     int store)
+                                                     int store, const double *__restrict__ chosT, int nrec)
 {
+    static_assert(MODE != 3 || kpp_recompute<T>(NL, FR), "MODE 3 exists only where MODE 2 is the recompute form");
     constexpr int PXL = vt<T>::PXL;
     constexpr bool VAR = MODE == 0;
+    constexpr bool REC = MODE == 2 && kpp_recompute<T>(NL, FR);   // closest from the chosen-centre table
+    constexpr bool FOLD = MODE == 3 || (MODE == 2 && !REC);       // closest from the plane, the pending centre folded in
     constexpr bool PIPE = kpp_pipelined<T>(NL, FR);
     unsigned long long acc[NL];
 #pragma unroll
@@ -214,7 +312,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp(planes_t pl, int F, int64_t
     auto request = [&](T (&x)[FR][PXL], T (&cl)[PXL], uint32_t off) {
 #pragma unroll
         for (int f = 0; f < FR; f++) load_pxq<T>(pl, F, f, chunk0, off, x[f]);
-        if constexpr (MODE == 2) load_pxf<T, true>(closest, chunk0 + off, n, cl);
+        if constexpr (FOLD) load_pxf<T, true>(closest, chunk0 + off, n, cl);
     };
     auto tile_body = [&](auto full_t, auto roll_c, T (&x)[FR][PXL], T (&cl)[PXL], uint32_t off, uint32_t noff) {
         const int64_t base = chunk0 + off;
@@ -232,7 +330,86 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp(planes_t pl, int F, int64_t
             }
 #pragma unroll
             for (int p = 0; p < PXL; p++) cl[p] = (T)0;
-            if constexpr (MODE == 2) load_pxf<T, FULL>(closest, base, n, cl);
+            if constexpr (FOLD) load_pxf<T, FULL>(closest, base, n, cl);
+        }
+        if constexpr (REC) {
+            // one feature loop, as in the plane rounds: ||x||^2, the dot products with the L candidates and with the nrec chosen
+            // centres (a scalar test per slot; the table's rows are padded, so a row is one unconditional scalar load); x[f] is
+            // used once, and plane f of the next full tile is requested behind it
+            double dot[NL][PXL], dc[KPP_MAXREC][PXL], yy[PXL];
+#pragma unroll
+            for (int p = 0; p < PXL; p++) {
+                yy[p] = 0.0;
+#pragma unroll
+                for (int l = 0; l < NL; l++) dot[l][p] = 0.0;
+#pragma unroll
+                for (int j = 0; j < KPP_MAXREC; j++) dc[j][p] = 0.0;
+            }
+#pragma unroll
+            for (int f = 0; f < FR; f++) {
+                if (f < F) {
+                    const T sc = sp->scale[f], mnv = sp->minv[f], me = sp->mean[f];
+                    double cd[NL], cj[KPP_MAXREC];  // unconditional: the rows are padded (zeros beyond L / beyond the slots in use)
+#pragma unroll
+                    for (int l = 0; l < NL; l++) cd[l] = candT[f * KPP_STRIDE + l];
+#pragma unroll
+                    for (int j = 0; j < KPP_MAXREC; j++) cj[j] = chosT[f * KPP_MAXREC + j];
+                    double y[PXL];
+#pragma unroll
+                    for (int p = 0; p < PXL; p++) {
+                        y[p] = (double)(scaled<T>(x[f][p], sc, mnv) - me);
+                        yy[p] = fma(y[p], y[p], yy[p]);
+#pragma unroll
+                        for (int l = 0; l < NL; l++) dot[l][p] = fma(cd[l], y[p], dot[l][p]);
+                    }
+#pragma unroll
+                    for (int j = 0; j < KPP_MAXREC; j++) {
+                        if (j < nrec) {
+#pragma unroll
+                            for (int p = 0; p < PXL; p++) dc[j][p] = fma(cj[j], y[p], dc[j][p]);
+                        }
+                    }
+                }
+                if constexpr (ROLL == 1) load_pxq<T>(pl, F, f, chunk0, noff, x[f]);   // x[f] is free: the next tile's plane f
+            }
+            {
+                const double *chcc = chosT + (size_t)KPP_MAXREC * RSSEG_MAX_FEATURES;
+#pragma unroll
+                for (int j = 0; j < KPP_MAXREC; j++) {
+                    if (j == 0 || j < nrec) {
+                        const double ccj = chcc[j];
+#pragma unroll
+                        for (int p = 0; p < PXL; p++) {
+                            const T dt = kpp_close<T>(dc[j][p], ccj, yy[p]);
+                            cl[p] = j == 0 || dt < cl[p] ? dt : cl[p];
+                        }
+                    }
+                }
+            }
+            // the hand-over to the plane rounds (store != 0 in the last recompute round of a fit with more clusters): all of it
+            if (!store) {
+            } else if (FULL || base + PXL <= n) {
+                typename vt<T>::vec o;
+                if constexpr (PXL == 4) o = make_float4(cl[0], cl[1], cl[2], cl[3]);
+                else o = make_double2(cl[0], cl[1]);
+                *reinterpret_cast<typename vt<T>::vec *>(closest + base) = o;
+            } else {
+                for (int p = 0; p < PXL; p++)
+                    if (base + p < n) closest[base + p] = cl[p];
+            }
+#pragma unroll
+            for (int l = 0; l < NL; l++) {
+                if (l < L) {
+                    const double ccl = cc[l];
+#pragma unroll
+                    for (int p = 0; p < PXL; p++) {
+                        T dt = kpp_close<T>(dot[l][p], ccl, yy[p]);               // np.maximum(distances, 0)
+                        dt = cl[p] < dt ? cl[p] : dt;                             // np.minimum(closest, d)
+                        if (FULL || base + p < n) acc[l] += (unsigned long long)to_fixed40((double)dt);
+                    }
+                }
+            }
+            return;
         }
         double dot[NL][PXL], dotp[PXL], yy[PXL];
 #pragma unroll
@@ -268,11 +445,11 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp(planes_t pl, int F, int64_t
         }
         if constexpr (MODE != 0) {
             const double ccp = cc[KPP_MAXL];
-            bool moved = MODE != 2;   // MODE 2: did the pending centre come closer to any of the thread's pixels?
+            bool moved = !FOLD;   // plane round: did the pending centre come closer to any of the thread's pixels?
 #pragma unroll
             for (int p = 0; p < PXL; p++) {
                 T dt = kpp_close<T>(dotp[p], ccp, yy[p]);
-                if constexpr (MODE == 2) {
+                if constexpr (FOLD) {
                     moved = moved || dt < cl[p];
                     dt = cl[p] < dt ? cl[p] : dt;
                 }
@@ -306,7 +483,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp(planes_t pl, int F, int64_t
                 }
             }
         }
-        if constexpr (ROLL == 1 && MODE == 2) load_pxf<T, true>(closest, chunk0 + noff, n, cl);
+        if constexpr (ROLL == 1 && FOLD) load_pxf<T, true>(closest, chunk0 + noff, n, cl);
     };
     T x[FR][PXL], cl[PXL];
     auto at = [&](int t) { return (uint32_t)(t * km_tile<T>() + (int)threadIdx.x * PXL); };   // pixel offset in the chunk
@@ -373,7 +550,7 @@ template <typename T>
 __global__ __launch_bounds__(KM_THREADS) void km_kpp_chunkq(planes_t pl, int F, const scaler_t<T> *__restrict__ sp,
                                                             const double *__restrict__ candT, const double *__restrict__ cc,
                                                             const T *__restrict__ closest, const kpp_sample_args *__restrict__ ap,
-                                                            unsigned long long *__restrict__ qv)
+                                                            unsigned long long *__restrict__ qv, const double *__restrict__ chosT, int nrec)
 {
     const kpp_sample_args &a = *ap;
     const int l = blockIdx.y;
@@ -381,6 +558,31 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp_chunkq(planes_t pl, int F, 
     const int64_t c0 = a.c0[l], cn = a.cn[l];
     const int64_t i = (int64_t)blockIdx.x * KM_THREADS + threadIdx.x;
     if (i >= cn) return;
+    if (nrec > 0) {
+        // a recompute round follows: the minimum over the nrec chosen centres, as that round's loop 1 forms it
+        double yy = 0.0, dc[KPP_MAXREC];
+#pragma unroll
+        for (int j = 0; j < KPP_MAXREC; j++) dc[j] = 0.0;
+        for (int f = 0; f < F; f++) {
+            const T xv = reinterpret_cast<const T *>(pl.p[f])[c0 + i];
+            const T yt = scaled<T>(xv, sp->scale[f], sp->minv[f]) - sp->mean[f];
+            const double y = (double)yt;
+            yy = fma(y, y, yy);
+#pragma unroll
+            for (int j = 0; j < KPP_MAXREC; j++)
+                if (j < nrec) dc[j] = fma(chosT[f * KPP_MAXREC + j], y, dc[j]);
+        }
+        const double *chcc = chosT + (size_t)KPP_MAXREC * RSSEG_MAX_FEATURES;
+        T best = kpp_close<T>(dc[0], chcc[0], yy);
+#pragma unroll
+        for (int j = 1; j < KPP_MAXREC; j++)
+            if (j < nrec) {
+                const T dt = kpp_close<T>(dc[j], chcc[j], yy);
+                best = dt < best ? dt : best;
+            }
+        qv[(size_t)l * km_chunk<T>() + i] = (unsigned long long)to_fixed40((double)best);
+        return;
+    }
     const double ccp = cc[KPP_MAXL];
     double yy = 0.0, dotp = 0.0;
     for (int f = 0; f < F; f++) {
@@ -1307,11 +1509,13 @@ __global__ __launch_bounds__(64) void kc_mean_pack(const km_state<T> *__restrict
 // X.mean(axis=0) (-> the scaler on the device), the first centre, and the candidate table of the first k-means++ sweep
 template <typename T>
 __global__ __launch_bounds__(KM_THREADS) void kc_mean_apply(km_state<T> *__restrict__ st, scaler_t<T> *__restrict__ sp, const long long *__restrict__ x,
-                                                            double *__restrict__ candT)
+                                                            double *__restrict__ candT, double *__restrict__ chosT)
 {
     const int F = st->F;
     double *cc = candT + (size_t)KPP_STRIDE * RSSEG_MAX_FEATURES;
+    double *chcc = chosT + (size_t)KPP_MAXREC * RSSEG_MAX_FEATURES;
     for (int i = threadIdx.x; i < KPP_STRIDE * RSSEG_MAX_FEATURES + KPP_STRIDE; i += KM_THREADS) candT[i] = 0.0;
+    for (int i = threadIdx.x; i < KPP_MAXREC * RSSEG_MAX_FEATURES + KPP_MAXREC; i += KM_THREADS) chosT[i] = 0.0;   // padded rows
     __syncthreads();
     const T Nt = (T)st->N;
     if ((int)threadIdx.x < F) {
@@ -1324,12 +1528,14 @@ __global__ __launch_bounds__(KM_THREADS) void kc_mean_apply(km_state<T> *__restr
         const T c0 = raw - m;     // the centring the sweeps apply: fl(fl(fl(x * scale) + min) - mean)
         st->C[0][f] = c0;
         candT[f * KPP_STRIDE] = (double)c0;
+        chosT[f * KPP_MAXREC] = (double)c0;     // slot 0 of the chosen-centre table
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         double a = 0.0;
         for (int f = 0; f < F; f++) a = fma((double)st->C[0][f], (double)st->C[0][f], a);
         cc[0] = a;
+        chcc[0] = a;
     }
 }
 
@@ -1368,7 +1574,8 @@ template <typename T> __device__ __forceinline__ void kc_pick_body(km_state<T> *
 // for this round: xbuf (the sampled rows, filled by their owner) and lim (the potentials, filled per rank).
 template <typename T>
 __global__ __launch_bounds__(KM_THREADS) void kc_targets(km_state<T> *st, int c, int pick_c, const unsigned long long *__restrict__ part,
-                                                         double *__restrict__ candT, kpp_sample_args *__restrict__ sa_out, double *xbuf, long long *lim)
+                                                         double *__restrict__ candT, kpp_sample_args *__restrict__ sa_out, double *xbuf, long long *lim,
+                                                         double *__restrict__ chosT)
 {
     if (pick_c > 0) kc_pick_body<T>(st, pick_c, lim);
     for (int i = threadIdx.x; i < KPP_MAXL * (1 + RSSEG_MAX_FEATURES); i += KM_THREADS) xbuf[i] = 0.0;
@@ -1378,11 +1585,16 @@ __global__ __launch_bounds__(KM_THREADS) void kc_targets(km_state<T> *st, int c,
     double *cc = candT + (size_t)KPP_STRIDE * RSSEG_MAX_FEATURES;
     for (int i = threadIdx.x; i < KPP_STRIDE * RSSEG_MAX_FEATURES + KPP_STRIDE; i += KM_THREADS) candT[i] = 0.0;
     __syncthreads();
-    if ((int)threadIdx.x < F) candT[threadIdx.x * KPP_STRIDE + KPP_MAXL] = (double)st->C[c - 1][threadIdx.x];
+    const bool slot = c - 1 < KPP_MAXREC;   // the pending centre is also slot c - 1 of the chosen-centre table
+    if ((int)threadIdx.x < F) {
+        candT[threadIdx.x * KPP_STRIDE + KPP_MAXL] = (double)st->C[c - 1][threadIdx.x];
+        if (slot) chosT[threadIdx.x * KPP_MAXREC + c - 1] = (double)st->C[c - 1][threadIdx.x];
+    }
     if (threadIdx.x == 0) {
         double a = 0.0;
         for (int f = 0; f < F; f++) a = fma((double)st->C[c - 1][f], (double)st->C[c - 1][f], a);
         cc[KPP_MAXL] = a;
+        if (slot) chosT[(size_t)KPP_MAXREC * RSSEG_MAX_FEATURES + c - 1] = a;
     }
     __shared__ kpp_sample_args sa;
     __shared__ u128 ssum[KM_THREADS];   // sums of KM_THREADS contiguous slices of this rank's prefix table
@@ -1669,10 +1881,23 @@ int launch_lloyd(rsseg_ctx *ctx, bool update, int64_t nchunks, size_t lds, plane
     });
 }
 
-// mode 0: first centre (L == 1, no per-pixel output); 1: first sampling round; 2: later rounds
+// does the round kernel of (T, L, F) have the recompute form?
+template <typename T> bool kpp_has_recompute(int L, int F)
+{
+    const int NL = L <= 4 ? 4 : 8;
+    switch (km_width(F)) {
+    case 8: return kpp_recompute<T>(NL, 8);
+    case 16: return kpp_recompute<T>(NL, 16);
+    case 32: return kpp_recompute<T>(NL, 32);
+    default: return false;   // km_kpp_blk: plane rounds
+    }
+}
+
+// mode 0: first centre (L == 1, no per-pixel output); 1: first sampling round; 2: later rounds, the closest-distance plane read and
+// (store) rewritten;  nrec > 0: a recompute round over nrec chosen centres (only where kpp_has_recompute), the plane written if `store`
 template <typename T>
 void launch_kpp(rsseg_ctx *ctx, int64_t nchunks, planes_t pl, int F, int64_t n, const scaler_t<T> *sp, const double *cand, const double *cc,
-                int L, int mode, bool last, T *closest, unsigned long long *partial)
+                int L, int mode, bool store, T *closest, unsigned long long *partial, const double *chos, int nrec)
 {
     auto go = [&](auto nl_c, auto mode_c) {
         constexpr int NL = decltype(nl_c)::value, MODE = decltype(mode_c)::value;
@@ -1680,16 +1905,28 @@ void launch_kpp(rsseg_ctx *ctx, int64_t nchunks, planes_t pl, int F, int64_t n, 
             constexpr int FR = decltype(fr_c)::value;
             const dim3 grid((unsigned)nchunks), block(KM_THREADS);
             if constexpr (FR != KM_BLOCKED) {
-                hipLaunchKernelGGL((km_kpp<T, NL, FR, MODE>), grid, block, 0, ctx->stream, pl, F, n, sp, cand, cc, L, closest, partial, nchunks,
-                                   last ? 0 : 1);
+                // MODE 2 is the recompute form where the table gives one, and MODE 3 the plane round then
+                constexpr bool REC = kpp_recompute<T>(NL, FR);
+                if constexpr (MODE == 2 && REC) {
+                    if (nrec > 0)
+                        hipLaunchKernelGGL((km_kpp<T, NL, FR, 2>), grid, block, 0, ctx->stream, pl, F, n, sp, cand, cc, L, closest, partial, nchunks,
+                                           store ? 1 : 0, chos, nrec);
+                    else
+                        hipLaunchKernelGGL((km_kpp<T, NL, FR, 3>), grid, block, 0, ctx->stream, pl, F, n, sp, cand, cc, L, closest, partial, nchunks,
+                                           store ? 1 : 0, chos, 0);
+                } else {
+                    hipLaunchKernelGGL((km_kpp<T, NL, FR, MODE>), grid, block, 0, ctx->stream, pl, F, n, sp, cand, cc, L, closest, partial, nchunks,
+                                       store ? 1 : 0, chos, 0);
+                }
             } else {   // feature-blocked kernels; the variance rows of the first pass come from km_var
                 hipLaunchKernelGGL((km_kpp_blk<T, NL, MODE>), grid, block, 0, ctx->stream, pl, F, n, sp, cand, cc, L, closest, partial, nchunks,
-                                   last ? 0 : 1);
+                                   store ? 1 : 0);
                 if constexpr (MODE == 0)
                     hipLaunchKernelGGL((km_var<T>), dim3((unsigned)nchunks, F), block, 0, ctx->stream, pl, n, sp, partial, nchunks);
             }
         });
     };
+    if (nrec > 0) mode = 2;
     if (mode == 0) go(ic<1>(), ic<0>());
     else if (L <= 4) mode == 1 ? go(ic<4>(), ic<1>()) : go(ic<4>(), ic<2>());
     else mode == 1 ? go(ic<8>(), ic<1>()) : go(ic<8>(), ic<2>());
@@ -1723,6 +1960,7 @@ template <typename T> struct km_fit {
     int max_iter = 0;
     // ---- geometry (N, offset, n_all, last_rank: from scale_and_ranks) ----
     int F = 0, k = 0, KMAX = 0, L = 0, M = 0, nblk = 0;
+    int kpp_depth = 0;         // k-means++ rounds c <= kpp_depth recompute the closest distances (0: plane rounds throughout)
     int64_t n = 0, nchunks = 0, N = 0, offset = 0;
     int64_t n_all[RSSEG_MAX_RANKS] = {0};
     int last_rank = 0;
@@ -1731,6 +1969,7 @@ template <typename T> struct km_fit {
         scaler_t<T> *sp;
         T *cen, *csq;          // centres (transposed) + their squared norms, contiguous: one copy uploads both
         double *cand, *cc;     // k-means++ candidates + theirs, likewise
+        double *chos;          // k-means++ chosen-centre table: [RSSEG_MAX_FEATURES][KPP_MAXREC] rows, then KPP_MAXREC norms
         T *row;
         unsigned long long *qv;
         long long *red;        // the exchange area when no all-reduce is installed
@@ -1739,7 +1978,7 @@ template <typename T> struct km_fit {
         km_state<T> *lst;
         T *mm;
         long long *mom, *part;
-        T *closest;            // the ONE closest-distance plane of k-means++
+        T *closest;            // the ONE closest-distance plane of k-means++ (null when every round recomputes)
         uint8_t *lab;
     } d;
     // values that cross ranks: in the communication buffer when an all-reduce is installed (the hook reduces them in place),
@@ -1769,6 +2008,11 @@ template <typename T> struct km_fit {
         L = 2 + (int)std::log((double)k);
         if (L > KPP_MAXL) return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "kmeans: too many local trials");
         M = KMAX * F + KMAX + 1;
+        kpp_depth = kpp_has_recompute<T>(L, F) ? KPP_RECOMPUTE : 0;
+        if (const char *e = getenv("RSSEG_KPP_RECOMPUTE")) {   // diagnostic: measure every depth with one build, move the hand-over
+            const int v = atoi(e);
+            if (kpp_depth > 0 && v >= 0 && v <= KPP_MAXREC) kpp_depth = v;
+        }
         nchunks = std::max<int64_t>(1, ceil_div64(n, CHUNK));
         nblk = (int)std::min<int64_t>(2048, std::max<int64_t>(1, ceil_div64(n, (int64_t)KM_THREADS * vt<T>::PXL)));
         // Lloyd accumulator copies: 32 when they fit in ~48 KB (3 workgroups per CU), fewer for large k * F
@@ -1791,6 +2035,7 @@ template <typename T> struct km_fit {
         const size_t o_sp = carve(sizeof(scaler_t<T>));
         const size_t o_cen = carve(sizeof(T) * ((size_t)KMAX * RSSEG_MAX_FEATURES + KMAX));
         const size_t o_cand = carve(sizeof(double) * ((size_t)KPP_STRIDE * RSSEG_MAX_FEATURES + KPP_STRIDE));
+        const size_t o_chos = carve(sizeof(double) * ((size_t)KPP_MAXREC * RSSEG_MAX_FEATURES + KPP_MAXREC));
         const size_t o_row = carve(sizeof(T) * RSSEG_MAX_FEATURES);
         const size_t o_qv = carve(sizeof(unsigned long long) * KPP_MAXL * (size_t)CHUNK);
         const size_t o_red = carve(x_bytes);
@@ -1800,7 +2045,9 @@ template <typename T> struct km_fit {
         const size_t o_mm = carve(sizeof(T) * 2 * (size_t)nblk * F);
         const size_t o_mom = carve(sizeof(long long) * (size_t)nblk * F);
         const size_t o_part = carve(sizeof(long long) * std::max<size_t>((size_t)M, KPP_MAXL) * (size_t)nchunks);
-        const size_t o_closest = carve((sizeof(T) * (size_t)std::max<int64_t>(n, 1) + 255) & ~(size_t)255);
+        // no plane when every sampling round recomputes (k - 1 <= depth): sizeof(T) B/px less
+        const bool plane = k - 1 > kpp_depth;
+        const size_t o_closest = plane ? carve((sizeof(T) * (size_t)std::max<int64_t>(n, 1) + 255) & ~(size_t)255) : 0;
         const size_t o_lab = carve((size_t)std::max<int64_t>(n, 1) + 64);
         RSCHK(ws_reserve(ctx, off));
         char *ws = ctx->d_ws;
@@ -1818,7 +2065,8 @@ template <typename T> struct km_fit {
         d.mm = (T *)(ws + o_mm);
         d.mom = (long long *)(ws + o_mom);
         d.part = (long long *)(ws + o_part);
-        d.closest = (T *)(ws + o_closest);
+        d.closest = plane ? (T *)(ws + o_closest) : nullptr;
+        d.chos = (double *)(ws + o_chos);
         d.lab = (uint8_t *)(ws + o_lab);
         x = ctx->comm_on ? (long long *)ctx->d_comm : d.red;
         // host read-backs at the head of the pinned area, the upload ring behind them
@@ -1936,15 +2184,25 @@ template <typename T> struct km_fit {
         if (n > 0) {
             {
                 prof_scope ps(ctx, "moment");
-                hipLaunchKernelGGL((km_moment<T>), dim3(nblk, F), dim3(KM_THREADS), 0, st, pl, n, d.sp, d.mom);
+                // up to 32 planes: the chunk walk, one partial per plane and chunk in d.part (free until the first k-means++ sweep)
+                with_width(km_width(F), [&](auto fr_c) {
+                    constexpr int FR = decltype(fr_c)::value;
+                    if constexpr (FR != KM_BLOCKED)
+                        hipLaunchKernelGGL((km_moment_chunk<T, FR>), dim3((unsigned)nchunks), dim3(KM_THREADS), 0, st, pl, F, n, d.sp, d.part, nchunks);
+                    else
+                        hipLaunchKernelGGL((km_moment<T>), dim3(nblk, F), dim3(KM_THREADS), 0, st, pl, n, d.sp, d.mom);
+                });
             }
             if (own0) hipLaunchKernelGGL((km_gather_row<T>), dim3(1), dim3(64), 0, st, pl, F, li0, d.sp, d.row);
-            hipLaunchKernelGGL(km_reduce_cols, dim3(F), dim3(KM_THREADS), 0, st, (const long long *)d.mom, (int64_t)nblk, x, (const int *)nullptr, 1, 0);
+            if (km_width(F) != KM_BLOCKED)
+                hipLaunchKernelGGL(km_reduce_cols, dim3(F), dim3(KM_THREADS), 0, st, (const long long *)d.part, nchunks, x, (const int *)nullptr, 1, 0);
+            else
+                hipLaunchKernelGGL(km_reduce_cols, dim3(F), dim3(KM_THREADS), 0, st, (const long long *)d.mom, (int64_t)nblk, x, (const int *)nullptr, 1, 0);
         }
         hipLaunchKernelGGL((kc_mean_pack<T>), dim3(1), dim3(64), 0, st, (const km_state<T> *)d.lst, (const T *)d.row, own0 ? 1 : 0, x);
         HIPCHK(ctx, hipGetLastError());
         RSCHK(comm_allreduce_dev(ctx, 0, 3 * F, RSSEG_I64, RSSEG_SUM));
-        hipLaunchKernelGGL((kc_mean_apply<T>), dim3(1), dim3(KM_THREADS), 0, st, d.lst, d.sp, (const long long *)x, d.cand);
+        hipLaunchKernelGGL((kc_mean_apply<T>), dim3(1), dim3(KM_THREADS), 0, st, d.lst, d.sp, (const long long *)x, d.cand, d.chos);
         HIPCHK(ctx, hipGetLastError());
         return RSSEG_OK;
     }
@@ -1955,7 +2213,7 @@ template <typename T> struct km_fit {
         // first sweep: the potential of the first centre per chunk (row 0) and the np.var numerators (rows 1..F)
         if (n > 0) {
             prof_scope ps(ctx, "kpp");
-            launch_kpp<T>(ctx, nchunks, pl, F, n, d.sp, d.cand, d.cc, 1, 0, false, d.closest, (unsigned long long *)d.part);
+            launch_kpp<T>(ctx, nchunks, pl, F, n, d.sp, d.cand, d.cc, 1, 0, true, d.closest, (unsigned long long *)d.part, d.chos, 0);
         }
         HIPCHK(ctx, hipGetLastError());
         // np.var(X, axis=0) and every rank's total of row 0 in ONE all-reduce: x = [F limb pairs][world limb pairs]
@@ -1973,13 +2231,17 @@ template <typename T> struct km_fit {
         for (int c = 1; c < k; c++) {
             // centre c-1 is pending: its distances are folded into the closest plane by this round's sweep, and by
             // km_kpp_chunkq for the chunks the samples fall into.  (The previous round's choice is made at the head of this kernel.)
+            // A recompute round (c <= kpp_depth) takes the c chosen centres from the table instead, as does its km_kpp_chunkq; the
+            // last of them hands over to the plane rounds by storing its values, if a plane round follows.
+            const int nrec = c <= kpp_depth ? c : 0;
+            const bool store = nrec > 0 ? (c == kpp_depth && c < k - 1) : c < k - 1;
             hipLaunchKernelGGL((kc_targets<T>), dim3(1), dim3(KM_THREADS), 0, st, d.lst, c, c > 1 ? c - 1 : 0, (const unsigned long long *)d.part, d.cand, d.sa,
-                               xbuf, lim);
+                               xbuf, lim, d.chos);
             // xbuf[l] = {global pixel index, its F scaled+centred values}: filled by the rank that owns the pixel, zeros
             // elsewhere, so ONE sum all-reduce hands every rank both the sampled indices and the candidate rows
             if (n > 0) {
                 hipLaunchKernelGGL((km_kpp_chunkq<T>), dim3((unsigned)(CHUNK / KM_THREADS), L), dim3(KM_THREADS), 0, st, pl, F, d.sp, d.cand, d.cc,
-                                   (const T *)d.closest, (const kpp_sample_args *)d.sa, d.qv);
+                                   (const T *)d.closest, (const kpp_sample_args *)d.sa, d.qv, (const double *)d.chos, nrec);
                 hipLaunchKernelGGL((km_kpp_sample<T>), dim3(L), dim3(KM_THREADS), 0, st, pl, F, d.sp, (const unsigned long long *)d.qv, (const kpp_sample_args *)d.sa, xbuf);
             }
             HIPCHK(ctx, hipGetLastError());
@@ -1987,7 +2249,7 @@ template <typename T> struct km_fit {
             hipLaunchKernelGGL((kc_cands<T>), dim3(1), dim3(KM_THREADS), 0, st, d.lst, (const double *)xbuf, d.cand);
             if (n > 0) {
                 prof_scope ps(ctx, "kpp");
-                launch_kpp<T>(ctx, nchunks, pl, F, n, d.sp, d.cand, d.cc, L, c > 1 ? 2 : 1, c == k - 1, d.closest, (unsigned long long *)d.part);
+                launch_kpp<T>(ctx, nchunks, pl, F, n, d.sp, d.cand, d.cc, L, c > 1 ? 2 : 1, store, d.closest, (unsigned long long *)d.part, d.chos, nrec);
             }
             HIPCHK(ctx, hipGetLastError());
             // potentials of all L candidates with ONE all-reduce: slot [l][rank] = this rank's chunk-sum total
