@@ -666,6 +666,28 @@ int rsseg_segment_features(rsseg_ctx *ctx, const int32_t *d_seg, int H, int W, i
  * straight to d_table (for tests that place segments across the seams and force that path) */
 void rsseg_segment_features_plan(int P, int *tile_w, int *tile_h, int *lds_slots);
 
+/* ---- K27: the region adjacency graph of a segment map (no counterpart in the reference) -------- */
+/* d_edges (device, int64[max_edges][3 + P], 8-byte aligned): one row per unordered pair of segments that share a border.
+ * The effective label of a pixel is K25's: d_seg[i] where it is 1 ... n_segments and the d_mask byte (NULL: all) is non-zero,
+ * else 0.  A CROSSING is a pixel and its right or its lower neighbour (4-connectivity) whose effective labels a != b are both
+ * > 0; every crossing belongs to its left / upper pixel and is counted once.
+ * Columns: 0, 1 min(a, b), max(a, b); 2 the length: the number of crossings of the pair; 3 + p the contrast of uint8 plane p:
+ * the sum over the crossings of |v_p(pixel) - v_p(neighbour)|.  0 <= P <= 16.  *n_edges: the number of rows written; their
+ * ORDER IS UNSPECIFIED (Context.segment_adjacency sorts them).  Integer sums: one right answer, restated in
+ * tests/adjacency_ref.py.
+ * Capacity: the library builds its own open-addressing table in the context's workspace, max_edges + max_edges / 2 + 64 rows of
+ * 2 + P int64.  The call returns RSSEG_ERR_UNSUPPORTED ("more than max_edges ... distinct pairs") exactly when the raster holds
+ * more than max_edges distinct pairs, and succeeds with max_edges equal to their number; d_edges is then not to be read.
+ * RSSEG_ERR_INVALID, naming the argument, before any launch: a null or misaligned pointer, H or W < 1, H W > 2^31 - 1, P < 0,
+ * max_edges < 0; and after the pass a label outside 0 ... n_segments (never used as an index).  RSSEG_ERR_UNSUPPORTED: P > 16.
+ * RSSEG_ERR_NOMEM: the table could not be allocated.
+ * Whole raster on one GPU.  Synchronous.  Profiler names "segment_adjacency" (the pass) and "segment_adjacency_compact". */
+int rsseg_segment_adjacency(rsseg_ctx *ctx, const int32_t *d_seg, int H, int W, int64_t n_segments, const uint8_t *d_mask,
+                            const uint8_t *const *d_planes, int P, int64_t max_edges, int64_t *d_edges, int64_t *n_edges);
+/* host-only: the kernel's tile and the rows of its per-tile table in LDS; a tile that meets more pairs commits the surplus
+ * straight to the global table (for tests that place segments across the seams and force that path) */
+void rsseg_segment_adjacency_plan(int P, int *tile_w, int *tile_h, int *lds_slots);
+
 /* ---- K24: class signatures: per-label sums of 1, x and x x^T (no counterpart in the reference) -- */
 /* d_out (device, int64[n_classes][1 + F + F (F + 1) / 2], 8-byte aligned): per label the exact integer moments of F
  * feature planes (RSSEG_F32 or RSSEG_U8, band-planar, n_local pixels) over the counted pixels.  One right answer, restated in

@@ -176,6 +176,8 @@ SIGNATURES = {
     "rsseg_segment_paint": (_int, [_vp, _vp, _i64, _i64, _vp, _int, _vp]),
     "rsseg_segment_features": (_int, [_vp, _vp, _int, _int, _i64, _PP, _int, _int, _vp, _int, _vp]),
     "rsseg_segment_features_plan": (None, [_int, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int)]),
+    "rsseg_segment_adjacency": (_int, [_vp, _vp, _int, _int, _i64, _vp, _PP, _int, _i64, _vp, C.POINTER(_i64)]),
+    "rsseg_segment_adjacency_plan": (None, [_int, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int)]),
     "rsseg_class_moments": (_int, [_vp, _PP, _int, _int, _i64, _vp, _int, _int, _int, _vp, C.POINTER(_int), _int, _vp, C.POINTER(_i64)]),
     "rsseg_class_moments_plan": (None, [_int, _int, _int, C.POINTER(_int), C.POINTER(_int)]),
     "rsseg_isodata_sweep": (_int, [_vp, _PP, _int, _int, _i64, _vp, C.POINTER(_int), _int, C.POINTER(C.c_double), _int, C.POINTER(C.c_double), _vp,

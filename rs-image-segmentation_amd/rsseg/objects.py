@@ -189,7 +189,7 @@ def features_from_table(table: np.ndarray, plane_is_u8: Sequence[bool], names=No
 
 
 def object_features(segments, planes, names=None, stats=STATS, shape: bool = True, mask=None, n_segments: Optional[int] = None,
-                    ctx: Optional[Context] = None) -> ObjectFeatures:
+                    ctx: Optional[Context] = None, neighbours: bool = False) -> ObjectFeatures:
     """ObjectFeatures(table, X, columns, area): X is float64 [(n + 1), D] with, per plane, <name>_mean, _std, _min, _max (those
     named in `stats`; names default to p0, p1, ...) and, with shape, SHAPE_COLUMNS (shape_statistics).  Row 0 and segments
     without a counted pixel are NaN.
@@ -197,10 +197,21 @@ def object_features(segments, planes, names=None, stats=STATS, shape: bool = Tru
     sqrt(var).  For uint8 planes they are the exact population statistics of the pixels.  For float32 planes the table holds
     sum llrint(v 2^40) and sum llrint(v^2 2^24): per term the square is off by at most 2^-25 and the mean by at most 2^-41, so
     the variance is within 2^-24 of the population variance of the inputs.  _min / _max of a float32 plane are the extremes of
-    llrint(v 2^40) 2^-40: the value itself where |v| >= 2^-16, else rounded to 2^-40."""
+    llrint(v 2^40) 2^-40: the value itself where |v| >= 2^-16, else rounded to 2^-40.
+    neighbours: append the columns of rsseg.regions.neighbour_features (n_neighbours, shared_border, per plane
+    <name>_boundary_contrast and <name>_neighbour_diff) from the region adjacency graph of the segments (K27: at most 16 planes;
+    float planes cross a border as slic() quantises them, in 8-bit steps of their own finite range)."""
     pls = _planes_arg(planes, "object_features")
     table = object_table(segments, pls, mask=mask, n_segments=n_segments, ctx=ctx)
-    return features_from_table(table, [SG._is_u8(p) for p in pls], names=names, stats=stats, shape=shape)
+    feats = features_from_table(table, [SG._is_u8(p) for p in pls], names=names, stats=stats, shape=shape)
+    if not neighbours:
+        return feats
+    from . import regions as RG
+    graph = RG.adjacency(segments, pls, mask=mask, n_segments=table.shape[0] - 1, ctx=ctx)
+    X = np.concatenate([feats.X, RG.neighbour_features(graph, table, [SG._is_u8(p) for p in pls])], axis=1)
+    X[table[:, 0] == 0] = np.nan
+    cols = feats.columns + RG.neighbour_columns([f"p{i}" for i in range(len(pls))] if names is None else [str(s) for s in names])
+    return ObjectFeatures(table, X, cols, feats.area)
 
 
 # ---- training and classification ---------------------------------------------------------------------------------------------

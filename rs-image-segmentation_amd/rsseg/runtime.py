@@ -847,6 +847,45 @@ class Context:
                                                   L.OBJ_GEOMETRY if geometry else 0, C.c_void_p(out.data_ptr())))
         return out.reshape(int(n_segments) + 1, cols)
 
+    # ---- K27: the region adjacency graph (rsseg/regions.py) ----------------------------------------
+    def segment_adjacency_plan(self, P: int = 0) -> Tuple[int, int, int]:
+        """(tile columns, tile rows, rows of the per-tile LDS table) of rsseg_segment_adjacency."""
+        tw, th, ns = C.c_int(0), C.c_int(0), C.c_int(0)
+        self.lib.rsseg_segment_adjacency_plan(int(P), C.byref(tw), C.byref(th), C.byref(ns))
+        return tw.value, th.value, ns.value
+
+    def segment_adjacency(self, seg, H: int, W: int, n_segments: int, planes: Sequence = (), mask=None, max_edges: Optional[int] = None):
+        """int64 device table [E, 3 + P] of rsseg_segment_adjacency, sorted ascending by (a, b): per pair of adjacent segments
+        a < b the length of their border and, per uint8 plane, the summed absolute step across it.  max_edges: the rows the
+        call may fill (RssegUnsupported when the raster holds more pairs).  None: 4 n_segments + 64 rows, and on that refusal
+        once more with min(2 H W - H - W, n (n - 1) / 2), which no raster exceeds; MemoryError when that cannot be allocated."""
+        torch = _torch()
+        P = len(planes)
+        if any(not self._is_u8(p) for p in planes):
+            raise ValueError("segment_adjacency: planes must be uint8")
+        H, W, n = int(H), int(W), int(n_segments)
+        if max_edges is None:
+            tries = [4 * n + 64, max(0, min(2 * H * W - H - W, n * (n - 1) // 2))]
+        else:
+            tries = [int(max_edges)]
+        cols = 3 + P
+        for i, cap in enumerate(tries):
+            try:
+                out = torch.empty(max(cap, 1) * cols, dtype=torch.int64, device=self.device)
+            except torch.cuda.OutOfMemoryError as e:
+                raise MemoryError(f"segment_adjacency: {cap} rows of {cols} int64 could not be allocated") from e
+            ne = C.c_int64(0)
+            try:
+                self._chk(self.lib.rsseg_segment_adjacency(self.h, C.c_void_p(seg.data_ptr()), H, W, n, None if mask is None else C.c_void_p(mask.data_ptr()),
+                                                           self._pp(planes) if P else None, P, cap, C.c_void_p(out.data_ptr()), C.byref(ne)))
+            except RssegUnsupported:
+                if i + 1 < len(tries) and 0 <= P <= 16 and tries[i + 1] > cap:
+                    continue
+                raise
+            rows = out[:ne.value * cols].reshape(ne.value, cols)
+            order = torch.argsort((rows[:, 0] << 32) | rows[:, 1])
+            return rows[order].contiguous()
+
     # ---- K9/K10 --------------------------------------------------------------------------------
     def kmeans_fit_predict(self, planes: Sequence, n_clusters: int, seed: int = 42, max_iter: int = 300, tol: float = 1e-4):
         torch = _torch()

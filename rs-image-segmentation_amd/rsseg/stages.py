@@ -799,6 +799,61 @@ def run_object_features_stage(feature_file_path, segments, output_dir: str, meth
     return class_map, res, entry
 
 
+REGION_GRAPH_FILE = "region_graph.npz"
+REGION_STATS_FILE = "regions_stats.json"
+
+
+def run_region_merge_stage(feature_file_path, segments, output_dir: str, *, threshold=None, scales=None, criterion: str = "ward", min_area: int = 0,
+                           n_regions: Optional[int] = None, class_map=None, method: Optional[str] = None, valid_mask=None, transform=None,
+                           crs=None, ctx: Optional[Context] = None):
+    """Region merging of a segment map (rsseg.regions.merge_regions, K27; no counterpart in the reference) on the planes
+    run_segment_stage segmented: the first 16 of the feature file's (H, W, F) stack.  valid_mask: pixels outside it belong to no
+    region and stay 0.
+    Writes, beside the earlier files that stay as they are: <output_dir>/regions.npy (int32, 0 = masked), or regions_<i>.npy per
+    scale (i = 0 ...); region_graph.npz (the graph of the final regions, RegionGraph.save); regions_stats.json (the parameters,
+    segments_in, regions_out and the smallest / median / largest area per map, rounds, merges); and, with class_map and method,
+    classification_<method>_regions.npy and <method>_classification_map_regions.tif: the class map voted per region of the
+    (last) map (rsseg.segment.object_classify; uint8, nodata 0, LZW tiles).
+    Returns (rsseg.regions.RegionMerge, that dictionary, region class map or None)."""
+    from . import regions as RG
+    from . import segment as SG
+    if (class_map is None) != (method is None):
+        raise ValueError("run_region_merge_stage: class_map and method go together")
+    shape, arr, names = _supervised_stack(feature_file_path, output_dir, "run_region_merge_stage")
+    segments = np.asarray(segments)
+    if tuple(segments.shape) != shape:
+        raise ValueError(f"run_region_merge_stage: the segment map is {tuple(segments.shape)}, the features are {shape}")
+    valid_mask = _check_valid_mask(valid_mask, shape)
+    used = min(arr.shape[-1], SG.MAX_PLANES)
+    planes = [np.ascontiguousarray(arr[..., i]) for i in range(used)]
+    res = RG.merge_regions(segments, planes, threshold=threshold, scales=scales, criterion=criterion, min_area=min_area, n_regions=n_regions,
+                           mask=valid_mask, ctx=ctx)
+
+    def areas(labels):
+        area = np.bincount(labels.reshape(-1))[1:]
+        return {"regions_out": int(area.size), "area_min": int(area.min()) if area.size else 0,
+                "area_median": float(np.median(area)) if area.size else 0.0, "area_max": int(area.max()) if area.size else 0}
+
+    maps = res.scale_labels if scales is not None else [res.labels]
+    for i, labels in enumerate(maps):
+        np.save(os.path.join(output_dir, f"regions_{i}.npy" if scales is not None else "regions.npy"), labels.astype(np.int32))
+    res.graph.save(os.path.join(output_dir, REGION_GRAPH_FILE))
+    stats: Dict[str, object] = {"criterion": criterion, "threshold": None if threshold is None else float(threshold),
+                                "scales": None if scales is None else [float(t) for t in scales], "n_regions": n_regions, "min_area": int(min_area),
+                                "planes_in_stack": int(arr.shape[-1]), "planes_used": int(used), "segments_in": int((res.parent > 0).sum()),
+                                "regions_out": int(res.n_regions), "rounds": int(res.history["round"].max()) if res.history.size else 0,
+                                "merges": int(res.history.size), "maps": [areas(m) for m in maps]}
+    regions_cm = None
+    if class_map is not None:
+        regions_cm = SG.object_classify(res.labels, class_map, nodata=0, ctx=ctx)
+        np.save(os.path.join(output_dir, f"classification_{method}_regions.npy"), regions_cm)
+        _write_class_tif(os.path.join(output_dir, f"{method}_classification_map_regions.tif"), regions_cm, transform, crs)
+        stats["method"] = method
+        stats["pixels_changed_by_regions"] = int((regions_cm != np.asarray(class_map)).sum())
+    _write_json(os.path.join(output_dir, REGION_STATS_FILE), stats)
+    return res, stats, regions_cm
+
+
 ISODATA_HISTORY_FILE = "isodata_history.json"
 ISODATA_DEFAULTS = dict(init_clusters=None, max_std=0.06, min_dist=0.1, min_size=None, iterations=20, change=0.0)
 
