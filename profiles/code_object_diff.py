@@ -42,9 +42,13 @@ def short(demangled):
 
 
 def by_name(kn):
-    """mangled -> figures becomes demangled name without parameters -> figures"""
+    """mangled -> figures becomes demangled name without parameters -> figures; kernels that share that name (overloads, as in
+    k16_forest_fit.hip) keep their parameter list"""
     names = demangle(sorted(kn))
-    out = {short(names[m]): v for m, v in kn.items()}
+    count = {}
+    for m in kn:
+        count[short(names[m])] = count.get(short(names[m]), 0) + 1
+    out = {(short(names[m]) if count[short(names[m])] == 1 else names[m].replace("void ", "")): v for m, v in kn.items()}
     assert len(out) == len(kn), "two kernels share a name"
     return out
 

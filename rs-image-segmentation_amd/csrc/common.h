@@ -152,6 +152,32 @@ __device__ __forceinline__ V wave_sum(V v)
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// inclusive prefix sum over the 64 lanes of the wave
+template <typename V>
+__device__ __forceinline__ V wave_incl_scan(V v)
+{
+    const int l = lane_id();
+#pragma unroll
+    for (int o = 1; o < WAVE; o <<= 1) {
+        const V up = __shfl_up(v, o, WAVE);
+        if (l >= o) v += up;
+    }
+    return v;
+}
+// adds every thread's a into *cnt: one atomic per WORKGROUP of THREADS threads, and only when there is something to add
+// (every thread must call it)
+template <int THREADS>
+__device__ __forceinline__ void wg_count_commit(unsigned long long *cnt, unsigned a)
+{
+    __shared__ unsigned s_a[THREADS / WAVE];
+    a = wave_sum(a);
+    if (lane_id() == 0) s_a[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < THREADS / WAVE; w++) a += s_a[w];
+        if (a) atomicAdd(cnt, (unsigned long long)a);
+    }
+}
 __device__ __forceinline__ float wave_min(float v)
 {
 #pragma unroll
@@ -276,12 +302,14 @@ __device__ __forceinline__ void indices_pixel(const evi_coef_t &e, const float n
     }
 }
 
-// round-to-nearest-even fixed point, quantum 2^-40, exact for |x| < 2^11:
-// bits(fma(x, 2^40, 1.5*2^52)) - bits(1.5*2^52) == llrint(x * 2^40)
+// The magic-constant fixed point: for |x| < 2^51, bits(x + 1.5*2^52) - bits(1.5*2^52) == llrint(x), one rounding to
+// nearest-even.  fx_bits is the TERM a sum adds per value (x, or a * b with the product exact inside the fma); the constant is
+// taken off once per run of cnt terms (fx_bias), or at once (fx_round).
 #define FX_MAGIC 6755399441055744.0 /* 1.5 * 2^52 */
-__device__ __forceinline__ long long to_fixed40(double x)
-{
-    double d = fma(x, 1099511627776.0, FX_MAGIC);
-    return __double_as_longlong(d) - __double_as_longlong(FX_MAGIC);
-}
+__device__ __forceinline__ unsigned long long fx_bits(double x) { return (unsigned long long)__double_as_longlong(x + FX_MAGIC); }
+__device__ __forceinline__ unsigned long long fx_bits(double a, double b) { return (unsigned long long)__double_as_longlong(fma(a, b, FX_MAGIC)); }
+__device__ __forceinline__ unsigned long long fx_bias(unsigned long long cnt) { return cnt * (unsigned long long)__double_as_longlong(FX_MAGIC); }
+__device__ __forceinline__ long long fx_round(double a, double b) { return (long long)(fx_bits(a, b) - fx_bias(1)); }
+// quantum 2^-40, exact for |x| < 2^11: llrint(x * 2^40)
+__device__ __forceinline__ long long to_fixed40(double x) { return fx_round(x, 1099511627776.0); }
 #endif

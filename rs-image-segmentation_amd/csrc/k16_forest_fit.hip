@@ -96,17 +96,6 @@ __device__ __forceinline__ bool ff_close(float a, float b) { return b <= a; }
 
 __device__ __forceinline__ int ff_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
-__device__ __forceinline__ int wave_incl_scan(int v)
-{
-    const int l = lane_id();
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(v, d, 64);
-        if (l >= d) v += t;
-    }
-    return v;
-}
-
 // exclusive prefix of `flag` over the workgroup; returns the prefix, *total = the count (all threads)
 __device__ __forceinline__ int block_excl_count(int flag, int *s_w, int *total)
 {

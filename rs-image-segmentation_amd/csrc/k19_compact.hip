@@ -76,7 +76,7 @@ __device__ __forceinline__ unsigned k19_map(const uint8_t *__restrict__ mask, in
 // exclusive prefix of `c` over the workgroup's 256 threads; *total = the workgroup's sum.  s_w: 4 ints of LDS.  All threads.
 __device__ __forceinline__ int k19_wg_prefix(int c, int *s_w, int *total)
 {
-    int incl = c;
+    int incl = c;   // wave_incl_scan written out: the helper reorders k19_scan
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const int up = __shfl_up(incl, o, 64);

@@ -25,53 +25,30 @@
 // Reductions.  segment_sums / segment_majority walk runs of eight consecutive pixels and commit a run of equal segment (and
 // class) with one atomic per field; float32 planes are summed as to_fixed40 integers, exact for |x| < 2^11.
 #include <algorithm>
-#include <cmath>
 
 #include "cc.h"
-#include "common.h"
+#include "keyed_table.h"
 
-#define K23_THREADS 256
-#define K23_TW 64        // tile columns: 16 threads x 4 pixels
-#define K23_TH 16        // tile rows
-#define K23_PXT 4        // consecutive pixels of one row per thread
-#define K23_MAX_P 16
 #define K23_ROUNDS 8     // growth rounds queued per host read
 #define K23_RUN 8        // pixels per thread of the reductions
 #define K23_SCAN_TILE 4096
 
 extern "C" void rsseg_slic_tile(int *tw, int *th)
 {
-    if (tw) *tw = K23_TW;
-    if (th) *th = K23_TH;
+    if (tw) *tw = KT_TW;
+    if (th) *th = KT_TH;
 }
 
-struct k23_planes_t {
-    const void *p[K23_MAX_P];
-};
-
-// grid-stride kernels: at most K23_MAX_BLOCKS workgroups, so that the one atomic a workgroup commits its counter with stays rare
-// (a million same-address atomics per launch cost more than the pass itself)
+// grid-stride kernels: at most K23_MAX_BLOCKS workgroups, so that the one atomic a workgroup commits its counter with
+// (wg_count_commit) stays rare (a million same-address atomics per launch cost more than the pass itself)
 #define K23_MAX_BLOCKS 8192
-static inline unsigned k23_grid(int64_t n) { return (unsigned)std::min<int64_t>(K23_MAX_BLOCKS, std::max<int64_t>(1, ceil_div64(n, K23_THREADS))); }
-
-// adds every thread's a into *cnt: one atomic per WORKGROUP (every thread must call it)
-__device__ __forceinline__ void k23_commit(unsigned long long *cnt, unsigned a)
-{
-    __shared__ unsigned s_a[K23_THREADS / WAVE];
-    a = wave_sum(a);
-    if (lane_id() == 0) s_a[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < K23_THREADS / WAVE; w++) a += s_a[w];
-        if (a) atomicAdd(cnt, (unsigned long long)a);
-    }
-}
+static inline unsigned k23_grid(int64_t n) { return (unsigned)std::min<int64_t>(K23_MAX_BLOCKS, std::max<int64_t>(1, ceil_div64(n, KT_THREADS))); }
 
 // ---- assignment + accumulation ---------------------------------------------------------------------------------------
 // cen / acc: [K][F = P + 3] = {count, sum y, sum x, sum q_0 ...}; lcy x lcx: the local table of centres, whose entry (0, 0) is
 // grid cell (ty0 / S - 1, tx0 / S - 1).  Dynamic LDS: double[nloc * F] (not with INIT), then unsigned[nloc * F].
 template <int PMAX, bool INIT>
-__global__ __launch_bounds__(K23_THREADS) void k23_assign(k23_planes_t pl, int P, const uint8_t *__restrict__ mask, int H, int W, int S, int ny, int nx,
+__global__ __launch_bounds__(KT_THREADS) void k23_assign(kt_planes_t pl, int P, const uint8_t *__restrict__ mask, int H, int W, int S, int ny, int nx,
                                                           int tiles_x, int lcy, int lcx, double weight, const double *__restrict__ cen,
                                                           int *__restrict__ lab, unsigned long long *__restrict__ acc, unsigned long long *__restrict__ changed)
 {
@@ -79,9 +56,9 @@ __global__ __launch_bounds__(K23_THREADS) void k23_assign(k23_planes_t pl, int P
     const int F = P + 3, nloc = lcy * lcx, tid = threadIdx.x;
     double *s_cen = reinterpret_cast<double *>(k23_lds);
     unsigned *s_acc = reinterpret_cast<unsigned *>(k23_lds + (INIT ? (size_t)0 : (size_t)nloc * F * sizeof(double)));
-    const int tx0 = (int)(blockIdx.x % (unsigned)tiles_x) * K23_TW, ty0 = (int)(blockIdx.x / (unsigned)tiles_x) * K23_TH;
+    const int tx0 = (int)(blockIdx.x % (unsigned)tiles_x) * KT_TW, ty0 = (int)(blockIdx.x / (unsigned)tiles_x) * KT_TH;
     const int gy0 = ty0 / S - 1, gx0 = tx0 / S - 1;
-    for (int e = tid; e < nloc * F; e += K23_THREADS) {
+    for (int e = tid; e < nloc * F; e += KT_THREADS) {
         s_acc[e] = 0;
         if (!INIT) {
             const int li = e / F, f = e - li * F, gy = gy0 + li / lcx, gx = gx0 + li % lcx;
@@ -90,7 +67,7 @@ __global__ __launch_bounds__(K23_THREADS) void k23_assign(k23_planes_t pl, int P
         }
     }
     __syncthreads();
-    const int ry = tid / (K23_TW / K23_PXT), y = ty0 + ry, xb = tx0 + (tid % (K23_TW / K23_PXT)) * K23_PXT;
+    const int ry = kt_ry(tid), y = ty0 + ry, xb = tx0 + kt_cx(tid);
     unsigned nchanged = 0, rc = 0, rx = 0, rq[PMAX];
     int run_li = -1;
 #pragma unroll
@@ -108,7 +85,7 @@ __global__ __launch_bounds__(K23_THREADS) void k23_assign(k23_planes_t pl, int P
     };
     if (y < H) {
         const int cyp = y / S;
-        for (int j = 0; j < K23_PXT; j++) {
+        for (int j = 0; j < KT_PXT; j++) {
             const int x = xb + j;
             if (x >= W) break;
             const int64_t i = (int64_t)y * W + x;
@@ -178,7 +155,7 @@ __global__ __launch_bounds__(K23_THREADS) void k23_assign(k23_planes_t pl, int P
     flush();
     __syncthreads();
     // a tile holds 1024 pixels: its 32-bit sums are at most 1024 * 255; the tile origin is added in 64 bits here
-    for (int li = tid; li < nloc; li += K23_THREADS) {
+    for (int li = tid; li < nloc; li += KT_THREADS) {
         const unsigned c = s_acc[li * F];
         if (!c) continue;
         const int gy = gy0 + li / lcx, gx = gx0 + li % lcx;             // inside the grid: only such a centre can win
@@ -188,14 +165,14 @@ __global__ __launch_bounds__(K23_THREADS) void k23_assign(k23_planes_t pl, int P
         atomicAdd(g + 2, (unsigned long long)s_acc[li * F + 2] + (unsigned long long)c * (unsigned)tx0);
         for (int p = 0; p < P; p++) atomicAdd(g + 3 + p, (unsigned long long)s_acc[li * F + 3 + p]);
     }
-    if (!INIT) k23_commit(changed, nchanged);
+    if (!INIT) wg_count_commit<KT_THREADS>(changed, nchanged);
 }
 
 // cen[k][0] = count, cen[k][f] = float64(sum) / float64(count): one IEEE division per component (0 for a dead centre)
-__global__ __launch_bounds__(K23_THREADS) void k23_centres(const unsigned long long *__restrict__ acc, int64_t K, int F, double *__restrict__ cen)
+__global__ __launch_bounds__(KT_THREADS) void k23_centres(const unsigned long long *__restrict__ acc, int64_t K, int F, double *__restrict__ cen)
 {
     const int64_t total = K * F;
-    for (int64_t e = (int64_t)blockIdx.x * K23_THREADS + threadIdx.x; e < total; e += (int64_t)gridDim.x * K23_THREADS) {
+    for (int64_t e = (int64_t)blockIdx.x * KT_THREADS + threadIdx.x; e < total; e += (int64_t)gridDim.x * KT_THREADS) {
         const int64_t k = e / F;
         const long long c = (long long)acc[k * F];
         const double cd = (double)c;
@@ -204,17 +181,17 @@ __global__ __launch_bounds__(K23_THREADS) void k23_centres(const unsigned long l
 }
 
 // ---- connectivity ----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(K23_THREADS) void k23_cc_init(const int *__restrict__ lab, int64_t n, int *__restrict__ L, int *__restrict__ area)
+__global__ __launch_bounds__(KT_THREADS) void k23_cc_init(const int *__restrict__ lab, int64_t n, int *__restrict__ L, int *__restrict__ area)
 {
-    for (int64_t i = (int64_t)blockIdx.x * K23_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * K23_THREADS) {
+    for (int64_t i = (int64_t)blockIdx.x * KT_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * KT_THREADS) {
         L[i] = lab[i] >= 0 ? (int)i : -1;
         area[i] = 0;
     }
 }
-__global__ __launch_bounds__(K23_THREADS) void k23_cc_union(const int *__restrict__ lab, int H, int W, int *__restrict__ L)
+__global__ __launch_bounds__(KT_THREADS) void k23_cc_union(const int *__restrict__ lab, int H, int W, int *__restrict__ L)
 {
     const int64_t n = (int64_t)H * W;
-    for (int64_t i = (int64_t)blockIdx.x * K23_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * K23_THREADS) {
+    for (int64_t i = (int64_t)blockIdx.x * KT_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * KT_THREADS) {
         const int v = lab[i];
         if (v < 0) continue;
         const int y = (int)(i / W), x = (int)(i - (int64_t)y * W);
@@ -223,9 +200,9 @@ __global__ __launch_bounds__(K23_THREADS) void k23_cc_union(const int *__restric
     }
 }
 // flattens the parents and counts the areas: a thread walks K23_RUN consecutive pixels and adds a run of one root at once
-__global__ __launch_bounds__(K23_THREADS) void k23_cc_count(int64_t n, int *__restrict__ L, int *__restrict__ area)
+__global__ __launch_bounds__(KT_THREADS) void k23_cc_count(int64_t n, int *__restrict__ L, int *__restrict__ area)
 {
-    for (int64_t i0 = ((int64_t)blockIdx.x * K23_THREADS + threadIdx.x) * K23_RUN; i0 < n; i0 += (int64_t)gridDim.x * K23_THREADS * K23_RUN) {
+    for (int64_t i0 = ((int64_t)blockIdx.x * KT_THREADS + threadIdx.x) * K23_RUN; i0 < n; i0 += (int64_t)gridDim.x * KT_THREADS * K23_RUN) {
         int cur = -1, run = 0;
         for (int j = 0; j < K23_RUN; j++) {
             const int64_t i = i0 + j;
@@ -244,11 +221,11 @@ __global__ __launch_bounds__(K23_THREADS) void k23_cc_count(int64_t n, int *__re
     }
 }
 // A[i] = root (component of at least min_area pixels), -2 - root (a small one), -1 (masked); cnt[0] += pixels not assigned
-__global__ __launch_bounds__(K23_THREADS) void k23_mark(int64_t n, const int *__restrict__ L, const int *__restrict__ area, int min_area, int *__restrict__ A,
+__global__ __launch_bounds__(KT_THREADS) void k23_mark(int64_t n, const int *__restrict__ L, const int *__restrict__ area, int min_area, int *__restrict__ A,
                                                         unsigned long long *__restrict__ cnt)
 {
     unsigned open = 0;
-    for (int64_t i = (int64_t)blockIdx.x * K23_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * K23_THREADS) {
+    for (int64_t i = (int64_t)blockIdx.x * KT_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * KT_THREADS) {
         int a = -1;
         const int r = L[i];   // the root itself: k23_cc_count flattened every parent in a launch after the last union
         if (r >= 0) {
@@ -258,14 +235,14 @@ __global__ __launch_bounds__(K23_THREADS) void k23_mark(int64_t n, const int *__
         }
         A[i] = a;
     }
-    k23_commit(cnt, open);
+    wg_count_commit<KT_THREADS>(cnt, open);
 }
 // one Jacobi round: B = A, except that a pixel not assigned in A takes its first assigned neighbour (up, left, right, down)
-__global__ __launch_bounds__(K23_THREADS) void k23_grow(const int *__restrict__ A, int *__restrict__ B, int H, int W, unsigned long long *__restrict__ cnt)
+__global__ __launch_bounds__(KT_THREADS) void k23_grow(const int *__restrict__ A, int *__restrict__ B, int H, int W, unsigned long long *__restrict__ cnt)
 {
     const int64_t n = (int64_t)H * W;
     unsigned grown = 0;
-    for (int64_t i = (int64_t)blockIdx.x * K23_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * K23_THREADS) {
+    for (int64_t i = (int64_t)blockIdx.x * KT_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * KT_THREADS) {
         int a = A[i];
         if (a <= -2) {
             const int y = (int)(i / W), x = (int)(i - (int64_t)y * W);
@@ -278,7 +255,7 @@ __global__ __launch_bounds__(K23_THREADS) void k23_grow(const int *__restrict__ 
         }
         B[i] = a;
     }
-    k23_commit(cnt, grown);
+    wg_count_commit<KT_THREADS>(cnt, grown);
 }
 
 // the segment a pixel ends in.  A pixel still unassigned when the growth stops has no assigned neighbour; neither has any
@@ -286,37 +263,32 @@ __global__ __launch_bounds__(K23_THREADS) void k23_grow(const int *__restrict__ 
 // component, which is 4-connected, is unassigned as a whole and stays the segment it was.
 __device__ __forceinline__ int k23_key(int a) { return a >= 0 ? a : (a <= -2 ? -2 - a : -1); }
 
-__global__ __launch_bounds__(K23_THREADS) void k23_first(int64_t n, const int *__restrict__ A, unsigned *__restrict__ first)
+__global__ __launch_bounds__(KT_THREADS) void k23_first(int64_t n, const int *__restrict__ A, unsigned *__restrict__ first)
 {
-    for (int64_t i = (int64_t)blockIdx.x * K23_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * K23_THREADS) {
+    for (int64_t i = (int64_t)blockIdx.x * KT_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * KT_THREADS) {
         const int k = k23_key(A[i]);
         if (k >= 0 && first[k] > (unsigned)i) atomicMin(&first[k], (unsigned)i);
     }
 }
-__global__ __launch_bounds__(K23_THREADS) void k23_flag(int64_t n, const int *__restrict__ A, const unsigned *__restrict__ first, uint8_t *__restrict__ flag)
+__global__ __launch_bounds__(KT_THREADS) void k23_flag(int64_t n, const int *__restrict__ A, const unsigned *__restrict__ first, uint8_t *__restrict__ flag)
 {
-    for (int64_t i = (int64_t)blockIdx.x * K23_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * K23_THREADS) {
+    for (int64_t i = (int64_t)blockIdx.x * KT_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * KT_THREADS) {
         const int k = k23_key(A[i]);
         flag[i] = k >= 0 && first[k] == (unsigned)i ? 1 : 0;
     }
 }
 // num[i] = 1 + the number of flagged pixels before i, for every flagged i; off: the exclusive tile sums of rsseg_compact_plan.
 // One workgroup per tile of K23_SCAN_TILE pixels, 16 per thread.
-__global__ __launch_bounds__(K23_THREADS) void k23_number(const uint8_t *__restrict__ flag, const int64_t *__restrict__ off, int64_t n, int *__restrict__ num)
+__global__ __launch_bounds__(KT_THREADS) void k23_number(const uint8_t *__restrict__ flag, const int64_t *__restrict__ off, int64_t n, int *__restrict__ num)
 {
-    __shared__ int s_w[K23_THREADS / WAVE];
+    __shared__ int s_w[KT_THREADS / WAVE];
     const int64_t base = (int64_t)blockIdx.x * K23_SCAN_TILE + (int64_t)threadIdx.x * 16;
     unsigned m = 0;
 #pragma unroll
     for (int j = 0; j < 16; j++)
         if (base + j < n && flag[base + j]) m |= 1u << j;
     const int c = __popc(m);
-    int incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(incl, o, 64);
-        if (lane_id() >= o) incl += up;
-    }
+    const int incl = wave_incl_scan(c);
     const int w = threadIdx.x >> 6;
     if (lane_id() == 63) s_w[w] = incl;
     __syncthreads();
@@ -327,10 +299,10 @@ __global__ __launch_bounds__(K23_THREADS) void k23_number(const uint8_t *__restr
     for (int j = 0; j < 16; j++)
         if ((m >> j) & 1u) num[base + j] = ++r;
 }
-__global__ __launch_bounds__(K23_THREADS) void k23_final(int64_t n, const int *__restrict__ A, const unsigned *__restrict__ first, const int *__restrict__ num,
+__global__ __launch_bounds__(KT_THREADS) void k23_final(int64_t n, const int *__restrict__ A, const unsigned *__restrict__ first, const int *__restrict__ num,
                                                          int *__restrict__ out)
 {
-    for (int64_t i = (int64_t)blockIdx.x * K23_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * K23_THREADS) {
+    for (int64_t i = (int64_t)blockIdx.x * KT_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * KT_THREADS) {
         const int k = k23_key(A[i]);
         out[i] = k >= 0 ? num[first[k]] : 0;
     }
@@ -339,16 +311,16 @@ __global__ __launch_bounds__(K23_THREADS) void k23_final(int64_t n, const int *_
 // ---- reductions ------------------------------------------------------------------------------------------------------------
 // sums[s][0 .. 3 + P) += {1, y, x, plane values} over the pixels of segment s (1 ... nseg) whose mask byte is non-zero
 template <typename T>
-__global__ __launch_bounds__(K23_THREADS) void k23_seg_sums(const int *__restrict__ seg, const uint8_t *__restrict__ mask, int64_t n, int W, int64_t nseg,
-                                                            k23_planes_t pl, int P, unsigned long long *__restrict__ sums, unsigned long long *__restrict__ bad)
+__global__ __launch_bounds__(KT_THREADS) void k23_seg_sums(const int *__restrict__ seg, const uint8_t *__restrict__ mask, int64_t n, int W, int64_t nseg,
+                                                            kt_planes_t pl, int P, unsigned long long *__restrict__ sums, unsigned long long *__restrict__ bad)
 {
     const int F = P + 3;
     unsigned nbad = 0;
-    for (int64_t i0 = ((int64_t)blockIdx.x * K23_THREADS + threadIdx.x) * K23_RUN; i0 < n; i0 += (int64_t)gridDim.x * K23_THREADS * K23_RUN) {
+    for (int64_t i0 = ((int64_t)blockIdx.x * KT_THREADS + threadIdx.x) * K23_RUN; i0 < n; i0 += (int64_t)gridDim.x * KT_THREADS * K23_RUN) {
         int cur = 0;
-        long long rc = 0, ry = 0, rx = 0, rq[K23_MAX_P];
+        long long rc = 0, ry = 0, rx = 0, rq[KT_MAX_P];
 #pragma unroll
-        for (int p = 0; p < K23_MAX_P; p++) rq[p] = 0;
+        for (int p = 0; p < KT_MAX_P; p++) rq[p] = 0;
         auto flush = [&]() {
             if (cur > 0 && rc) {
                 unsigned long long *g = sums + (int64_t)cur * F;
@@ -356,14 +328,14 @@ __global__ __launch_bounds__(K23_THREADS) void k23_seg_sums(const int *__restric
                 atomicAdd(g + 1, (unsigned long long)ry);
                 atomicAdd(g + 2, (unsigned long long)rx);
 #pragma unroll
-                for (int p = 0; p < K23_MAX_P; p++)
+                for (int p = 0; p < KT_MAX_P; p++)
                     if (p < P) atomicAdd(g + 3 + p, (unsigned long long)rq[p]);
             }
         };
         for (int j = 0; j < K23_RUN; j++) {
             const int64_t i = i0 + j;
             if (i >= n) break;
-            const int s = seg[i];
+            const int s = seg[i];   // K25's rule for the effective label
             if (s < 0 || s > nseg) {
                 nbad++;
                 continue;
@@ -374,14 +346,14 @@ __global__ __launch_bounds__(K23_THREADS) void k23_seg_sums(const int *__restric
                 cur = s;
                 rc = ry = rx = 0;
 #pragma unroll
-                for (int p = 0; p < K23_MAX_P; p++) rq[p] = 0;
+                for (int p = 0; p < KT_MAX_P; p++) rq[p] = 0;
             }
             const int64_t y = i / W;
             rc++;
             ry += y;
             rx += i - y * W;
 #pragma unroll
-            for (int p = 0; p < K23_MAX_P; p++)
+            for (int p = 0; p < KT_MAX_P; p++)
                 if (p < P) {
                     const T v = reinterpret_cast<const T *>(pl.p[p])[i];
                     if constexpr (sizeof(T) == 1) rq[p] += (long long)v;
@@ -390,15 +362,15 @@ __global__ __launch_bounds__(K23_THREADS) void k23_seg_sums(const int *__restric
         }
         flush();
     }
-    k23_commit(bad, nbad);
+    wg_count_commit<KT_THREADS>(bad, nbad);
 }
 
 // votes[(s - 1) * NL + v] += 1 for every pixel of segment s whose class v is below NL and not `ignore`
-__global__ __launch_bounds__(K23_THREADS) void k23_seg_votes(const int *__restrict__ seg, const uint8_t *__restrict__ q, int64_t n, int64_t nseg, int NL,
+__global__ __launch_bounds__(KT_THREADS) void k23_seg_votes(const int *__restrict__ seg, const uint8_t *__restrict__ q, int64_t n, int64_t nseg, int NL,
                                                              int ignore, int *__restrict__ votes, unsigned long long *__restrict__ bad)
 {
     unsigned nbad = 0;
-    for (int64_t i0 = ((int64_t)blockIdx.x * K23_THREADS + threadIdx.x) * K23_RUN; i0 < n; i0 += (int64_t)gridDim.x * K23_THREADS * K23_RUN) {
+    for (int64_t i0 = ((int64_t)blockIdx.x * KT_THREADS + threadIdx.x) * K23_RUN; i0 < n; i0 += (int64_t)gridDim.x * KT_THREADS * K23_RUN) {
         int64_t cur = -1;
         int run = 0;
         for (int j = 0; j < K23_RUN; j++) {
@@ -421,12 +393,12 @@ __global__ __launch_bounds__(K23_THREADS) void k23_seg_votes(const int *__restri
         }
         if (run) atomicAdd(&votes[cur], run);
     }
-    k23_commit(bad, nbad);
+    wg_count_commit<KT_THREADS>(bad, nbad);
 }
 // table[s] = the label with the most votes (ties: the smallest), `fill` without a voter; table[0] = fill
-__global__ __launch_bounds__(K23_THREADS) void k23_seg_winner(const int *__restrict__ votes, int64_t nseg, int NL, int fill, uint8_t *__restrict__ table)
+__global__ __launch_bounds__(KT_THREADS) void k23_seg_winner(const int *__restrict__ votes, int64_t nseg, int NL, int fill, uint8_t *__restrict__ table)
 {
-    for (int64_t s = (int64_t)blockIdx.x * K23_THREADS + threadIdx.x; s <= nseg; s += (int64_t)gridDim.x * K23_THREADS) {
+    for (int64_t s = (int64_t)blockIdx.x * KT_THREADS + threadIdx.x; s <= nseg; s += (int64_t)gridDim.x * KT_THREADS) {
         int win = fill, most = 0;
         if (s > 0) {
             const int *row = votes + (s - 1) * NL;
@@ -442,17 +414,17 @@ __global__ __launch_bounds__(K23_THREADS) void k23_seg_winner(const int *__restr
     }
 }
 template <typename T>
-__global__ __launch_bounds__(K23_THREADS) void k23_paint(const int *__restrict__ seg, int64_t n, int64_t nseg, const T *__restrict__ table, T *__restrict__ out,
+__global__ __launch_bounds__(KT_THREADS) void k23_paint(const int *__restrict__ seg, int64_t n, int64_t nseg, const T *__restrict__ table, T *__restrict__ out,
                                                          unsigned long long *__restrict__ bad)
 {
     unsigned nbad = 0;
-    for (int64_t i = (int64_t)blockIdx.x * K23_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * K23_THREADS) {
+    for (int64_t i = (int64_t)blockIdx.x * KT_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * KT_THREADS) {
         const int s = seg[i];
         const bool ok = s >= 0 && s <= nseg;
         out[i] = table[ok ? s : 0];
         nbad += !ok;
     }
-    k23_commit(bad, nbad);
+    wg_count_commit<KT_THREADS>(bad, nbad);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
@@ -460,51 +432,33 @@ namespace {
 
 size_t k23_up(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// copies `count` 64-bit counters at d_src to the pinned buffer and waits
-int k23_read(rsseg_ctx *ctx, const unsigned long long *d_src, int count, unsigned long long *out)
-{
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d_src, sizeof(unsigned long long) * count, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, rs_sync(ctx));
-    memcpy(out, ctx->h_pin, sizeof(unsigned long long) * count);
-    return RSSEG_OK;
-}
-
 template <bool INIT>
-int k23_launch_assign(rsseg_ctx *ctx, const k23_planes_t &pl, int P, const uint8_t *d_mask, int H, int W, int S, int ny, int nx, double weight,
+int k23_launch_assign(rsseg_ctx *ctx, const kt_planes_t &pl, int P, const uint8_t *d_mask, int H, int W, int S, int ny, int nx, double weight,
                       const double *cen, int *lab, unsigned long long *acc, unsigned long long *changed)
 {
-    const int tiles_x = (W + K23_TW - 1) / K23_TW, tiles_y = (H + K23_TH - 1) / K23_TH;
-    const int lcy = (K23_TH - 1) / S + 4, lcx = (K23_TW - 1) / S + 4;
+    const int tiles_x = (W + KT_TW - 1) / KT_TW, tiles_y = (H + KT_TH - 1) / KT_TH;
+    const int lcy = (KT_TH - 1) / S + 4, lcx = (KT_TW - 1) / S + 4;
     const size_t lds = (size_t)lcy * lcx * (P + 3) * (INIT ? sizeof(unsigned) : sizeof(unsigned) + sizeof(double));
-    const dim3 grid((unsigned)((int64_t)tiles_x * tiles_y)), block(K23_THREADS);
-#define K23_GO(PM)                                                                                                                              \
-    do {                                                                                                                                        \
-        RSCHK(set_max_dyn_lds(ctx, (const void *)k23_assign<PM, INIT>, lds));                                                                   \
-        hipLaunchKernelGGL((k23_assign<PM, INIT>), grid, block, lds, ctx->stream, pl, P, d_mask, H, W, S, ny, nx, tiles_x, lcy, lcx, weight, cen, \
-                           lab, acc, changed);                                                                                                  \
-    } while (0)
-    if (P <= 4) K23_GO(4);
-    else if (P <= 8) K23_GO(8);
-    else K23_GO(16);
-#undef K23_GO
+    const dim3 grid((unsigned)((int64_t)tiles_x * tiles_y)), block(KT_THREADS);
+    const auto kernel = P <= 4 ? k23_assign<4, INIT> : P <= 8 ? k23_assign<8, INIT> : k23_assign<16, INIT>;
+    RSCHK(kt_launch(ctx, kernel, grid, block, lds, pl, P, d_mask, H, W, S, ny, nx, tiles_x, lcy, lcx, weight, cen, lab, acc, changed));
     HIPCHK(ctx, hipGetLastError());
     return RSSEG_OK;
 }
 
+// the flat segment map of the reductions: a segment holds a pixel, so there are at most n of them (the pointer is tested first)
 int k23_check_seg(rsseg_ctx *ctx, const char *what, const int32_t *d_seg, int64_t n, int64_t n_segments)
 {
-    if (!d_seg || ((uintptr_t)d_seg & 3)) return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: d_seg null or not aligned to its element", what);
-    if (n < 1 || n > 0x7fffffff) return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: %lld pixels, must be 1 ... 2^31 - 1", what, (long long)n);
-    if (n_segments < 0 || n_segments > n) return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: n_segments = %lld is not in 0 ... %lld", what, (long long)n_segments, (long long)n);
-    return RSSEG_OK;
+    RSCHK(kt_check_seg(ctx, what, d_seg));
+    RSCHK(kt_check_pixels(ctx, what, n));
+    return kt_check_nseg(ctx, what, n_segments, n, nullptr);
 }
 
 int k23_bad_labels(rsseg_ctx *ctx, const char *what, const unsigned long long *d_bad, int64_t n_segments)
 {
     unsigned long long bad = 0;
-    RSCHK(k23_read(ctx, d_bad, 1, &bad));
-    if (bad) return rs_fail(ctx, RSSEG_ERR_INVALID, "%s: d_seg holds %llu labels outside 0 ... n_segments = %lld", what, bad, (long long)n_segments);
-    return RSSEG_OK;
+    RSCHK(kt_read(ctx, d_bad, sizeof(bad), &bad));
+    return kt_bad_labels(ctx, what, bad, n_segments);
 }
 
 }  // namespace
@@ -514,10 +468,9 @@ extern "C" int rsseg_slic_u8(rsseg_ctx *ctx, const uint8_t *const *d_planes, int
 {
     if (!ctx) return RSSEG_ERR_INVALID;
     if (!d_planes) return rs_fail(ctx, RSSEG_ERR_INVALID, "slic: d_planes is null");
-    if (P < 1 || P > K23_MAX_P) return rs_fail(ctx, P < 1 ? RSSEG_ERR_INVALID : RSSEG_ERR_UNSUPPORTED, "slic: P = %d planes, must be 1 ... %d", P, K23_MAX_P);
-    for (int p = 0; p < P; p++)
-        if (!d_planes[p]) return rs_fail(ctx, RSSEG_ERR_INVALID, "slic: d_planes[%d] is null", p);
-    if (H < 1 || W < 1) return rs_fail(ctx, RSSEG_ERR_INVALID, "slic: H = %d, W = %d: both must be at least 1", H, W);
+    RSCHK(kt_check_planes(ctx, "slic", d_planes, P, 1));
+    for (int p = 0; p < P; p++) RSCHK(kt_check_plane_u8(ctx, "slic", d_planes, p));
+    RSCHK(kt_check_hw(ctx, "slic", H, W));
     if ((int64_t)H * W > 0x7fffffff) return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "slic: more than 2^31 - 1 pixels");
     if (S < 2 || S > 4096) return rs_fail(ctx, RSSEG_ERR_INVALID, "slic: S = %d is not in 2 ... 4096", S);
     if (!(weight >= 0.0) || !std::isfinite(weight)) return rs_fail(ctx, RSSEG_ERR_INVALID, "slic: weight = %g is not a finite non-negative number", weight);
@@ -549,7 +502,7 @@ extern "C" int rsseg_slic_u8(rsseg_ctx *ctx, const uint8_t *const *d_planes, int
     double *cen = (double *)w;
     w += b_acc;
     unsigned long long *cnt = (unsigned long long *)w;
-    k23_planes_t pl;
+    kt_planes_t pl;
     memset(&pl, 0, sizeof(pl));
     for (int p = 0; p < P; p++) pl.p[p] = d_planes[p];
     int *lab = d_labels;
@@ -565,13 +518,13 @@ extern "C" int rsseg_slic_u8(rsseg_ctx *ctx, const uint8_t *const *d_planes, int
     for (int t = 1; t <= max_iter; t++) {
         {
             prof_scope ps(ctx, "slic_assign");
-            hipLaunchKernelGGL(k23_centres, dim3(k23_grid(K * F)), dim3(K23_THREADS), 0, ctx->stream, (const unsigned long long *)acc, K, F, cen);
+            hipLaunchKernelGGL(k23_centres, dim3(k23_grid(K * F)), dim3(KT_THREADS), 0, ctx->stream, (const unsigned long long *)acc, K, F, cen);
             HIPCHK(ctx, hipMemsetAsync(acc, 0, sizeof(unsigned long long) * (size_t)K * F, ctx->stream));
             HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof(unsigned long long), ctx->stream));
             RSCHK(k23_launch_assign<false>(ctx, pl, P, nullptr, H, W, S, ny, nx, weight, cen, lab, acc, cnt));
         }
         unsigned long long changed = 0;
-        RSCHK(k23_read(ctx, cnt, 1, &changed));
+        RSCHK(kt_read(ctx, cnt, sizeof(changed), &changed));
         iters = t;
         if (!changed) break;
     }
@@ -582,26 +535,26 @@ extern "C" int rsseg_slic_u8(rsseg_ctx *ctx, const uint8_t *const *d_planes, int
     {
         prof_scope ps(ctx, "slic_enforce");
         HIPCHK(ctx, hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * (K23_ROUNDS + 2), ctx->stream));
-        hipLaunchKernelGGL(k23_cc_init, dim3(g), dim3(K23_THREADS), 0, ctx->stream, (const int *)lab, n, Lp, area);
-        hipLaunchKernelGGL(k23_cc_union, dim3(g), dim3(K23_THREADS), 0, ctx->stream, (const int *)lab, H, W, Lp);
-        hipLaunchKernelGGL(k23_cc_count, dim3(k23_grid(ceil_div64(n, K23_RUN))), dim3(K23_THREADS), 0, ctx->stream, n, Lp, area);
-        hipLaunchKernelGGL(k23_mark, dim3(g), dim3(K23_THREADS), 0, ctx->stream, n, (const int *)Lp, (const int *)area, min_area, A, cnt);
+        hipLaunchKernelGGL(k23_cc_init, dim3(g), dim3(KT_THREADS), 0, ctx->stream, (const int *)lab, n, Lp, area);
+        hipLaunchKernelGGL(k23_cc_union, dim3(g), dim3(KT_THREADS), 0, ctx->stream, (const int *)lab, H, W, Lp);
+        hipLaunchKernelGGL(k23_cc_count, dim3(k23_grid(ceil_div64(n, K23_RUN))), dim3(KT_THREADS), 0, ctx->stream, n, Lp, area);
+        hipLaunchKernelGGL(k23_mark, dim3(g), dim3(KT_THREADS), 0, ctx->stream, n, (const int *)Lp, (const int *)area, min_area, A, cnt);
         HIPCHK(ctx, hipGetLastError());
     }
     unsigned long long open = 0;
-    RSCHK(k23_read(ctx, cnt, 1, &open));
+    RSCHK(kt_read(ctx, cnt, sizeof(open), &open));
     while (open) {
         unsigned long long got[K23_ROUNDS];
         {
             prof_scope ps(ctx, "slic_enforce");
             HIPCHK(ctx, hipMemsetAsync(cnt + 1, 0, sizeof(unsigned long long) * K23_ROUNDS, ctx->stream));
             for (int r = 0; r < K23_ROUNDS; r++) {
-                hipLaunchKernelGGL(k23_grow, dim3(g), dim3(K23_THREADS), 0, ctx->stream, (const int *)cur, other, H, W, cnt + 1 + r);
+                hipLaunchKernelGGL(k23_grow, dim3(g), dim3(KT_THREADS), 0, ctx->stream, (const int *)cur, other, H, W, cnt + 1 + r);
                 std::swap(cur, other);
             }
             HIPCHK(ctx, hipGetLastError());
         }
-        RSCHK(k23_read(ctx, cnt + 1, K23_ROUNDS, got));
+        RSCHK(kt_read(ctx, cnt + 1, sizeof(got), got));
         bool stopped = false;
         for (int r = 0; r < K23_ROUNDS; r++) {
             regrown += got[r];
@@ -616,16 +569,16 @@ extern "C" int rsseg_slic_u8(rsseg_ctx *ctx, const uint8_t *const *d_planes, int
     {
         prof_scope ps(ctx, "slic_relabel");
         HIPCHK(ctx, hipMemsetAsync(first, 0xff, sizeof(unsigned) * (size_t)n, ctx->stream));
-        hipLaunchKernelGGL(k23_first, dim3(g), dim3(K23_THREADS), 0, ctx->stream, n, (const int *)cur, first);
-        hipLaunchKernelGGL(k23_flag, dim3(g), dim3(K23_THREADS), 0, ctx->stream, n, (const int *)cur, (const unsigned *)first, flag);
+        hipLaunchKernelGGL(k23_first, dim3(g), dim3(KT_THREADS), 0, ctx->stream, n, (const int *)cur, first);
+        hipLaunchKernelGGL(k23_flag, dim3(g), dim3(KT_THREADS), 0, ctx->stream, n, (const int *)cur, (const unsigned *)first, flag);
         HIPCHK(ctx, hipGetLastError());
     }
     int64_t nseg = 0;
     RSCHK(rsseg_compact_plan(ctx, flag, n, off, &nseg));
     {
         prof_scope ps(ctx, "slic_relabel");
-        hipLaunchKernelGGL(k23_number, dim3((unsigned)ntiles), dim3(K23_THREADS), 0, ctx->stream, (const uint8_t *)flag, (const int64_t *)off, n, num);
-        hipLaunchKernelGGL(k23_final, dim3(g), dim3(K23_THREADS), 0, ctx->stream, n, (const int *)cur, (const unsigned *)first, (const int *)num, d_labels);
+        hipLaunchKernelGGL(k23_number, dim3((unsigned)ntiles), dim3(KT_THREADS), 0, ctx->stream, (const uint8_t *)flag, (const int64_t *)off, n, num);
+        hipLaunchKernelGGL(k23_final, dim3(g), dim3(KT_THREADS), 0, ctx->stream, n, (const int *)cur, (const unsigned *)first, (const int *)num, d_labels);
         HIPCHK(ctx, hipGetLastError());
     }
     HIPCHK(ctx, rs_sync(ctx));
@@ -639,21 +592,18 @@ extern "C" int rsseg_segment_sums(rsseg_ctx *ctx, const int32_t *d_seg, int H, i
                                   const uint8_t *d_mask, int64_t *d_sums)
 {
     if (!ctx) return RSSEG_ERR_INVALID;
-    if (H < 1 || W < 1) return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_sums: H = %d, W = %d: both must be at least 1", H, W);
+    RSCHK(kt_check_hw(ctx, "segment_sums", H, W));
     const int64_t n = (int64_t)H * W;
     RSCHK(k23_check_seg(ctx, "segment_sums", d_seg, n, n_segments));
-    if (P < 0 || P > K23_MAX_P) return rs_fail(ctx, P < 0 ? RSSEG_ERR_INVALID : RSSEG_ERR_UNSUPPORTED, "segment_sums: P = %d planes, must be 0 ... %d", P, K23_MAX_P);
-    if (P > 0 && !d_planes) return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_sums: d_planes is null");
-    if (dtype != RSSEG_U8 && dtype != RSSEG_F32) return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_sums: dtype must be RSSEG_U8 or RSSEG_F32");
-    for (int p = 0; p < P; p++)
-        if (!d_planes[p] || (dtype == RSSEG_F32 && ((uintptr_t)d_planes[p] & 3)))
-            return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_sums: d_planes[%d] null or not aligned to its element", p);
+    RSCHK(kt_check_planes(ctx, "segment_sums", d_planes, P, 0));
+    RSCHK(kt_check_dtype(ctx, "segment_sums", dtype, "RSSEG_U8 or RSSEG_F32"));
+    for (int p = 0; p < P; p++) RSCHK(kt_check_plane(ctx, "segment_sums", d_planes, p, dtype));
     if (!d_sums || ((uintptr_t)d_sums & 7)) return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_sums: d_sums null or not 8-byte aligned");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     RSCHK(ws_reserve(ctx, 256));
     RSCHK(pin_reserve(ctx, 256));
     unsigned long long *d_bad = (unsigned long long *)ctx->d_ws;
-    k23_planes_t pl;
+    kt_planes_t pl;
     memset(&pl, 0, sizeof(pl));
     for (int p = 0; p < P; p++) pl.p[p] = d_planes[p];
     HIPCHK(ctx, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), ctx->stream));
@@ -662,10 +612,10 @@ extern "C" int rsseg_segment_sums(rsseg_ctx *ctx, const int32_t *d_seg, int H, i
         prof_scope ps(ctx, "segment_sums");
         const unsigned g = k23_grid(ceil_div64(n, K23_RUN));
         if (dtype == RSSEG_U8)
-            hipLaunchKernelGGL(k23_seg_sums<uint8_t>, dim3(g), dim3(K23_THREADS), 0, ctx->stream, d_seg, d_mask, n, W, n_segments, pl, P,
+            hipLaunchKernelGGL(k23_seg_sums<uint8_t>, dim3(g), dim3(KT_THREADS), 0, ctx->stream, d_seg, d_mask, n, W, n_segments, pl, P,
                                (unsigned long long *)d_sums, d_bad);
         else
-            hipLaunchKernelGGL(k23_seg_sums<float>, dim3(g), dim3(K23_THREADS), 0, ctx->stream, d_seg, d_mask, n, W, n_segments, pl, P,
+            hipLaunchKernelGGL(k23_seg_sums<float>, dim3(g), dim3(KT_THREADS), 0, ctx->stream, d_seg, d_mask, n, W, n_segments, pl, P,
                                (unsigned long long *)d_sums, d_bad);
         HIPCHK(ctx, hipGetLastError());
     }
@@ -699,9 +649,9 @@ extern "C" int rsseg_segment_majority_u8(rsseg_ctx *ctx, const int32_t *d_seg, i
     HIPCHK(ctx, hipMemsetAsync(votes, 0, b_votes + 256, ctx->stream));
     {
         prof_scope ps(ctx, "segment_majority");
-        hipLaunchKernelGGL(k23_seg_votes, dim3(k23_grid(ceil_div64(n, K23_RUN))), dim3(K23_THREADS), 0, ctx->stream, d_seg, d_class, n, n_segments, NL, ignore,
+        hipLaunchKernelGGL(k23_seg_votes, dim3(k23_grid(ceil_div64(n, K23_RUN))), dim3(KT_THREADS), 0, ctx->stream, d_seg, d_class, n, n_segments, NL, ignore,
                            votes, d_bad);
-        hipLaunchKernelGGL(k23_seg_winner, dim3(k23_grid(n_segments + 1)), dim3(K23_THREADS), 0, ctx->stream, (const int *)votes, n_segments, NL, fill,
+        hipLaunchKernelGGL(k23_seg_winner, dim3(k23_grid(n_segments + 1)), dim3(KT_THREADS), 0, ctx->stream, (const int *)votes, n_segments, NL, fill,
                            d_table);
         HIPCHK(ctx, hipGetLastError());
     }
@@ -723,10 +673,10 @@ extern "C" int rsseg_segment_paint(rsseg_ctx *ctx, const int32_t *d_seg, int64_t
     {
         prof_scope ps(ctx, "segment_paint");
         if (elem_bytes == 1)
-            hipLaunchKernelGGL(k23_paint<uint8_t>, dim3(k23_grid(n)), dim3(K23_THREADS), 0, ctx->stream, d_seg, n, n_segments, (const uint8_t *)d_table,
+            hipLaunchKernelGGL(k23_paint<uint8_t>, dim3(k23_grid(n)), dim3(KT_THREADS), 0, ctx->stream, d_seg, n, n_segments, (const uint8_t *)d_table,
                                (uint8_t *)d_out, d_bad);
         else
-            hipLaunchKernelGGL(k23_paint<uint32_t>, dim3(k23_grid(n)), dim3(K23_THREADS), 0, ctx->stream, d_seg, n, n_segments, (const uint32_t *)d_table,
+            hipLaunchKernelGGL(k23_paint<uint32_t>, dim3(k23_grid(n)), dim3(KT_THREADS), 0, ctx->stream, d_seg, n, n_segments, (const uint32_t *)d_table,
                                (uint32_t *)d_out, d_bad);
         HIPCHK(ctx, hipGetLastError());
     }

@@ -21,10 +21,8 @@
 //      at F = 64); neither is added.
 // The adds are 64-bit integer atomics: their order cannot change the sums.
 #include <algorithm>
-#include <cmath>
-#include <type_traits>
 
-#include "common.h"
+#include "keyed_table.h"
 
 #define MO_THREADS 256
 #define MO_R 4               // rows and columns of a thread's block
@@ -74,8 +72,7 @@ __global__ __launch_bounds__(MO_THREADS) void class_moments(mo_args a, int T, in
     unsigned long long *l_table = reinterpret_cast<unsigned long long *>(mo_lds);
     float *vals = reinterpret_cast<float *>(mo_lds + (GLOBAL ? 0 : (size_t)k * C * 8));
     uint32_t *sorted = reinterpret_cast<uint32_t *>(vals + (size_t)FA * T);
-    if (!GLOBAL)
-        for (int i = tid; i < k * C; i += MO_THREADS) l_table[i] = 0;
+    if (!GLOBAL) kt_table_zero<MO_THREADS>(l_table, k * C);
     if (tid <= F) s_scale[tid] = tid == 0 ? 1.0 : a.scale[tid - 1];
     __syncthreads();
 
@@ -102,7 +99,6 @@ __global__ __launch_bounds__(MO_THREADS) void class_moments(mo_args a, int T, in
         sa[r] = s_scale[min(a0 + r, F)] * a.two_q;
         sb[r] = s_scale[min(b0 + r, F)];
     }
-    const unsigned long long magic_bits = (unsigned long long)__double_as_longlong(FX_MAGIC);
     unsigned long long n_left = 0;
     bool bad = false;
     const int PPT = T / MO_THREADS;   // 1 or 2
@@ -165,7 +161,7 @@ __global__ __launch_bounds__(MO_THREADS) void class_moments(mo_args a, int T, in
 #pragma unroll
                     for (int u = 0; u < MO_LD; u++) {
                         if (f0 + u < F) {
-                            float v = (float)raw[j][u];
+                            float v = (float)raw[j][u];   // staging, as K26 step 1: NaN -> +0, the range test on the scaled value
                             if (std::is_same<PT, float>::value) {
                                 if (v != v) v = 0.0f;
                                 ok[j] = ok[j] && fabs((double)v * a.scale[f0 + u]) <= 1.0;
@@ -183,7 +179,7 @@ __global__ __launch_bounds__(MO_THREADS) void class_moments(mo_args a, int T, in
                 else { mylab[j] = -1; n_left++; }
             }
             __syncthreads();
-            {   // exclusive scan of the histogram (256 entries, one per thread)
+            {   // exclusive scan of the histogram (256 entries, one per thread); wave_incl_scan written out: the helper changes the kernel's code
                 const int h = s_hist[tid];
                 int inc = h;
 #pragma unroll
@@ -201,7 +197,7 @@ __global__ __launch_bounds__(MO_THREADS) void class_moments(mo_args a, int T, in
             __syncthreads();
 #pragma unroll
             for (int j = 0; j < 2; j++)
-                if (mylab[j] >= 0) sorted[s_start[mylab[j]] + mypos[j]] = ((uint32_t)mylab[j] << 16) | (uint32_t)(j * MO_THREADS + tid);
+                if (mylab[j] >= 0) sorted[s_start[mylab[j]] + mypos[j]] = kt_sorted_entry(mylab[j], j * MO_THREADS + tid);
             __syncthreads();
             // ---- 3: the runs
             const int total = s_total;
@@ -215,7 +211,7 @@ __global__ __launch_bounds__(MO_THREADS) void class_moments(mo_args a, int T, in
                     for (int c = 0; c < MO_R; c++) acc[r][c] = 0;
                 auto flush = [&]() {
                     if (cnt) {
-                        const unsigned long long bias = cnt * magic_bits;
+                        const unsigned long long bias = fx_bias(cnt);
                         unsigned long long *row = (GLOBAL ? g_table : l_table) + (size_t)cur * C;
 #pragma unroll
                         for (int r = 0; r < MO_R; r++)
@@ -239,22 +235,22 @@ __global__ __launch_bounds__(MO_THREADS) void class_moments(mo_args a, int T, in
 #pragma unroll
                     for (int r = 0; r < MO_R; r++)
 #pragma unroll
-                        for (int c = 0; c < MO_R; c++) acc[r][c] += (unsigned long long)__double_as_longlong(fma(xs[r], xb[c], FX_MAGIC));
+                        for (int c = 0; c < MO_R; c++) acc[r][c] += fx_bits(xs[r], xb[c]);
                 };
                 int p = (int)(((long long)piece * total) / PS);
                 const int end = (int)(((long long)(piece + 1) * total) / PS);
                 while (p < end) {
                     const uint32_t e0 = sorted[p];
                     const uint32_t e1 = sorted[min(p + 1, end - 1)];
-                    if ((int)(e0 >> 16) != cur) {
+                    if (kt_entry_label(e0) != cur) {
                         flush();
-                        cur = (int)(e0 >> 16);
+                        cur = kt_entry_label(e0);
                     }
-                    pixel((int)(e0 & 0xffffu));
+                    pixel(kt_entry_slot(e0));
                     cnt++;
                     p++;
-                    if (p < end && (int)(e1 >> 16) == cur) {   // the next pixel of the same run: its loads overlap the first one's fmas
-                        pixel((int)(e1 & 0xffffu));
+                    if (p < end && kt_entry_label(e1) == cur) {   // the next pixel of the same run: its loads overlap the first one's fmas
+                        pixel(kt_entry_slot(e1));
                         cnt++;
                         p++;
                     }
@@ -266,10 +262,7 @@ __global__ __launch_bounds__(MO_THREADS) void class_moments(mo_args a, int T, in
     }
     if (!GLOBAL) {
         __syncthreads();
-        for (int i = tid; i < k * C; i += MO_THREADS) {
-            const unsigned long long v = l_table[i];
-            if (v) atomicAdd(&g_table[i], v);
-        }
+        kt_table_flush<MO_THREADS>(l_table, g_table, k * C);
     }
     if (n_left) atomicAdd(&g_tail[0], n_left);
     if (bad) atomicAdd(&g_tail[1], 1ull);
@@ -284,16 +277,9 @@ __global__ void class_moments_counts(long long *__restrict__ table, int k, int C
 
 namespace {
 
-template <typename PT, typename LT, bool GLOBAL>
-int mo_launch3(rsseg_ctx *ctx, const mo_args &a, int grid, int T, int B, int PS, size_t lds, unsigned long long *table, unsigned long long *tail)
+template <typename PT, typename LT, typename... A> int mo_launch(rsseg_ctx *ctx, bool global, int grid, size_t lds, A... x)
 {
-    RSCHK(set_max_dyn_lds(ctx, (const void *)class_moments<PT, LT, GLOBAL>, lds));
-    hipLaunchKernelGGL((class_moments<PT, LT, GLOBAL>), dim3(grid), dim3(MO_THREADS), lds, ctx->stream, a, T, B, PS, table, tail);
-    return RSSEG_OK;
-}
-template <typename PT, typename LT, typename... A> int mo_launch2(rsseg_ctx *ctx, bool global, A... x)
-{
-    return global ? mo_launch3<PT, LT, true>(ctx, x...) : mo_launch3<PT, LT, false>(ctx, x...);
+    return kt_launch(ctx, global ? class_moments<PT, LT, true> : class_moments<PT, LT, false>, dim3(grid), dim3(MO_THREADS), lds, x...);
 }
 
 }  // namespace
@@ -314,23 +300,17 @@ extern "C" int rsseg_class_moments(rsseg_ctx *ctx, const void *const *d_planes, 
     if (n_classes < 1) return rs_fail(ctx, RSSEG_ERR_INVALID, "class_moments: n_classes=%d, must be >= 1", n_classes);
     if (F > RSSEG_MAX_FEATURES) return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "class_moments: F=%d feature planes, the kernel takes at most %d", F, RSSEG_MAX_FEATURES);
     if (n_classes > MO_MAX_CLASSES) return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "class_moments: n_classes=%d, the kernel takes at most %d", n_classes, MO_MAX_CLASSES);
-    if (dtype != RSSEG_F32 && dtype != RSSEG_U8) return rs_fail(ctx, RSSEG_ERR_INVALID, "class_moments: dtype must be RSSEG_F32 or RSSEG_U8");
+    RSCHK(kt_check_dtype(ctx, "class_moments", dtype, "RSSEG_F32 or RSSEG_U8"));
     if (label_dtype != RSSEG_U8 && label_dtype != RSSEG_I32) return rs_fail(ctx, RSSEG_ERR_INVALID, "class_moments: label_dtype must be RSSEG_U8 or RSSEG_I32");
     if (n_local < 0) return rs_fail(ctx, RSSEG_ERR_INVALID, "class_moments: n_local=%lld is negative", (long long)n_local);
-    if (Q < 0 || Q > 50) return rs_fail(ctx, RSSEG_ERR_INVALID, "class_moments: Q=%d, must be 0 ... 50", Q);
-    if (n_local >= ((int64_t)1 << (62 - Q))) return rs_fail(ctx, RSSEG_ERR_INVALID, "class_moments: n_local=%lld times 2^Q (Q=%d) reaches 2^62", (long long)n_local, Q);
-    if (dtype == RSSEG_U8 && (plane_exp || Q != 0)) return rs_fail(ctx, RSSEG_ERR_INVALID, "class_moments: RSSEG_U8 planes take plane_exp = NULL and Q = 0");
-    if (dtype == RSSEG_F32 && !plane_exp) return rs_fail(ctx, RSSEG_ERR_INVALID, "class_moments: plane_exp is null");
+    RSCHK(kt_check_fixed(ctx, "class_moments", dtype, plane_exp, Q, n_local));
     if (!d_out || ((uintptr_t)d_out & 7)) return rs_fail(ctx, RSSEG_ERR_INVALID, "class_moments: d_out null or not 8-byte aligned");
     if (!n_left_out) return rs_fail(ctx, RSSEG_ERR_INVALID, "class_moments: n_left_out is null");
     mo_args a;
     memset(&a, 0, sizeof(a));
     for (int f = 0; f < F; f++) {
-        if (plane_exp && (plane_exp[f] < -300 || plane_exp[f] > 300))
-            return rs_fail(ctx, RSSEG_ERR_INVALID, "class_moments: plane_exp[%d]=%d, must be -300 ... 300", f, plane_exp[f]);
-        a.scale[f] = plane_exp ? std::ldexp(1.0, plane_exp[f]) : 1.0;
-        if (n_local > 0 && (!d_planes[f] || (dtype == RSSEG_F32 && ((uintptr_t)d_planes[f] & 3))))
-            return rs_fail(ctx, RSSEG_ERR_INVALID, "class_moments: d_planes[%d] null or not aligned to its element", f);
+        RSCHK(kt_plane_scale(ctx, "class_moments", plane_exp, f, &a.scale[f]));
+        if (n_local > 0) RSCHK(kt_check_plane(ctx, "class_moments", d_planes, f, dtype));
         a.plane[f] = d_planes[f];
     }
     if (n_local > 0 && (!d_labels || (label_dtype == RSSEG_I32 && ((uintptr_t)d_labels & 3))))
@@ -359,11 +339,11 @@ extern "C" int rsseg_class_moments(rsseg_ctx *ctx, const void *const *d_planes, 
         const size_t lds = mo_tile_bytes(F) + (global ? 0 : (size_t)cells * 8);
         const int grid = (int)std::min<int64_t>(MO_MAX_BLOCKS, ceil_div64(n_local, MO_SPAN));
         if (dtype == RSSEG_F32) {
-            if (label_dtype == RSSEG_U8) RSCHK((mo_launch2<float, uint8_t>(ctx, global, a, grid, T, B, PS, lds, table, tail)));
-            else RSCHK((mo_launch2<float, int>(ctx, global, a, grid, T, B, PS, lds, table, tail)));
+            if (label_dtype == RSSEG_U8) RSCHK((mo_launch<float, uint8_t>(ctx, global, grid, lds, a, T, B, PS, table, tail)));
+            else RSCHK((mo_launch<float, int>(ctx, global, grid, lds, a, T, B, PS, table, tail)));
         } else {
-            if (label_dtype == RSSEG_U8) RSCHK((mo_launch2<uint8_t, uint8_t>(ctx, global, a, grid, T, B, PS, lds, table, tail)));
-            else RSCHK((mo_launch2<uint8_t, int>(ctx, global, a, grid, T, B, PS, lds, table, tail)));
+            if (label_dtype == RSSEG_U8) RSCHK((mo_launch<uint8_t, uint8_t>(ctx, global, grid, lds, a, T, B, PS, table, tail)));
+            else RSCHK((mo_launch<uint8_t, int>(ctx, global, grid, lds, a, T, B, PS, table, tail)));
         }
         if (Q > 0)
             hipLaunchKernelGGL(class_moments_counts, dim3((n_classes + 255) / 256), dim3(256), 0, ctx->stream, (long long *)table, n_classes, C, Q);
@@ -381,9 +361,8 @@ extern "C" int rsseg_class_moments(rsseg_ctx *ctx, const void *const *d_planes, 
         }
     }
     HIPCHK(ctx, hipMemcpyAsync(d_out, table, 8 * (size_t)cells, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, tail, 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, rs_sync(ctx));
-    const unsigned long long *h = reinterpret_cast<const unsigned long long *>(ctx->h_pin);
+    unsigned long long h[2];
+    RSCHK(kt_read(ctx, tail, sizeof(h), h));
     *n_left_out = (int64_t)h[0];
     if (h[1]) return rs_fail(ctx, RSSEG_ERR_INVALID, "class_moments: d_labels holds a counted label outside 0 ... %d", n_classes - 1);
     return RSSEG_OK;

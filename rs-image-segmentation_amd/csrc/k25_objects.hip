@@ -3,7 +3,7 @@
 // sum, minimum or maximum, so the table has one right answer whatever the order the atomics land in; it is restated in NumPy
 // in tests/objects_ref.py, to which the kernel is equal bit for bit.
 //
-// A workgroup walks 64 x 16 tiles (grid stride); a thread owns four consecutive pixels of a row.
+// A workgroup walks the 64 x 16 tiles of keyed_table.h (grid stride); a thread owns four consecutive pixels of a row.
 //   1. The EFFECTIVE labels of the tile and of a one-pixel ring around it are staged in LDS: the label where it is
 //      1 ... n_segments and the mask byte is non-zero, else 0 (outside the image: 0).  A label outside 0 ... n_segments is
 //      counted for the refusal and reads as 0, so it never becomes an index.
@@ -16,32 +16,23 @@
 // Empty pattern of a column: 0 for a sum, INT64_MAX / INT64_MIN (H / -1, W / -1 for the bounding box) for a minimum / maximum.
 #include <algorithm>
 
-#include "common.h"
+#include "keyed_table.h"
 
-#define K25_THREADS 256
-#define K25_TW 64        // tile columns: 16 threads x 4 pixels
-#define K25_TH 16        // tile rows
-#define K25_PXT 4        // consecutive pixels of one row per thread
 #define K25_SLOTS 64     // rows of the LDS table (a power of two); 64 x (11 + 4 * 16) x 8 B = 37.5 KiB at P = 16
-#define K25_MAX_P 16
 #define K25_GEO 11       // geometry columns
 #define K25_MAX_BLOCKS 8192
-#define K25_EW (K25_TW + 2)
-#define K25_EH (K25_TH + 2)
+#define K25_EW (KT_TW + 2)
+#define K25_EH (KT_TH + 2)
 static_assert(K25_SLOTS == 64, "the hash keeps the top six bits of the product: change the shift with the row count");
-static_assert(K25_SLOTS <= K25_THREADS && K25_TW * K25_TH == K25_THREADS * K25_PXT, "one thread per row of the list; four pixels per thread");
+static_assert(K25_SLOTS <= KT_THREADS && KT_TW * KT_TH == KT_THREADS * KT_PXT, "one thread per row of the list; four pixels per thread");
 
 extern "C" void rsseg_segment_features_plan(int P, int *tile_w, int *tile_h, int *lds_slots)
 {
     (void)P;   // the plan does not depend on the plane count: the row gets wider, the table keeps its rows
-    if (tile_w) *tile_w = K25_TW;
-    if (tile_h) *tile_h = K25_TH;
+    if (tile_w) *tile_w = KT_TW;
+    if (tile_h) *tile_h = KT_TH;
     if (lds_slots) *lds_slots = K25_SLOTS;
 }
-
-struct k25_planes_t {
-    const void *p[K25_MAX_P];
-};
 
 // what a column holds: 0 a sum, 1 a minimum, 2 a maximum
 __host__ __device__ __forceinline__ int k25_kind(int col)
@@ -65,24 +56,19 @@ __device__ __forceinline__ void k25_put(long long *cell, int kind, long long v)
     else atomicMax(cell, v);
 }
 
-// llrint(v * v * 2^24): the square of a float32 is exact in float64 and below 2^22, so the magic-number rounding of to_fixed40
-// applies (the scaled value stays below 2^51)
-__device__ __forceinline__ long long k25_sq_fixed24(double v)
-{
-    const double d = fma(v * v, 16777216.0, FX_MAGIC);
-    return __double_as_longlong(d) - __double_as_longlong(FX_MAGIC);
-}
+// llrint(v * v * 2^24): the square of a float32 is exact in float64 and below 2^22, so the scaled value stays below 2^51
+__device__ __forceinline__ long long k25_sq_fixed24(double v) { return fx_round(v * v, 16777216.0); }
 
-__global__ __launch_bounds__(K25_THREADS) void k25_init(long long *__restrict__ table, int64_t rows, int C, int H, int W)
+__global__ __launch_bounds__(KT_THREADS) void k25_init(long long *__restrict__ table, int64_t rows, int C, int H, int W)
 {
     const int64_t total = rows * C;
-    for (int64_t e = (int64_t)blockIdx.x * K25_THREADS + threadIdx.x; e < total; e += (int64_t)gridDim.x * K25_THREADS)
+    for (int64_t e = (int64_t)blockIdx.x * KT_THREADS + threadIdx.x; e < total; e += (int64_t)gridDim.x * KT_THREADS)
         table[e] = k25_empty((int)(e % C), H, W);
 }
 
 template <typename T, bool GEO>
-__global__ __launch_bounds__(K25_THREADS) void k25_features(const int *__restrict__ seg, const uint8_t *__restrict__ mask, int H, int W, int64_t nseg,
-                                                            k25_planes_t pl, int P, int vec, int tiles_x, int64_t ntiles, long long *__restrict__ table,
+__global__ __launch_bounds__(KT_THREADS) void k25_features(const int *__restrict__ seg, const uint8_t *__restrict__ mask, int H, int W, int64_t nseg,
+                                                            kt_planes_t pl, int P, int vec, int tiles_x, int64_t ntiles, long long *__restrict__ table,
                                                             unsigned long long *__restrict__ bad)
 {
     extern __shared__ __align__(8) unsigned char k25_lds[];
@@ -90,21 +76,20 @@ __global__ __launch_bounds__(K25_THREADS) void k25_features(const int *__restric
     __shared__ int s_key[K25_SLOTS];        // 0: free, else the label the row belongs to
     __shared__ int s_list[K25_SLOTS];       // the occupied rows, in the order they were claimed
     __shared__ int s_nocc;
-    __shared__ unsigned s_bad[K25_THREADS / WAVE];
     long long *s_tab = reinterpret_cast<long long *>(k25_lds);   // [K25_SLOTS][C]
     const int C = K25_GEO + 4 * P, tid = threadIdx.x;
-    for (int e = tid; e < K25_SLOTS * C; e += K25_THREADS) s_tab[e] = k25_empty(e % C, H, W);
+    for (int e = tid; e < K25_SLOTS * C; e += KT_THREADS) s_tab[e] = k25_empty(e % C, H, W);
     if (tid < K25_SLOTS) s_key[tid] = 0;
     if (tid == 0) s_nocc = 0;
-    const int ry = tid / (K25_TW / K25_PXT), cx = (tid % (K25_TW / K25_PXT)) * K25_PXT;
+    const int ry = kt_ry(tid), cx = kt_cx(tid);
     unsigned nbad = 0;
 
     for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const int tx0 = (int)(t % tiles_x) * K25_TW, ty0 = (int)(t / tiles_x) * K25_TH;
+        const int tx0 = (int)(t % tiles_x) * KT_TW, ty0 = (int)(t / tiles_x) * KT_TH;
         __syncthreads();   // the table is empty and the previous tile's labels are no longer read
-        for (int e = tid; e < K25_EH * K25_EW; e += K25_THREADS) {
+        for (int e = tid; e < K25_EH * K25_EW; e += KT_THREADS) {
             const int ly = e / K25_EW, lx = e - ly * K25_EW, gy = ty0 - 1 + ly, gx = tx0 - 1 + lx;
-            const bool inner = ly >= 1 && ly <= K25_TH && lx >= 1 && lx <= K25_TW;
+            const bool inner = ly >= 1 && ly <= KT_TH && lx >= 1 && lx <= KT_TW;
             int eff = 0;
             if ((GEO || inner) && gy >= 0 && gy < H && gx >= 0 && gx < W) {
                 const int64_t i = (int64_t)gy * W + gx;
@@ -117,23 +102,23 @@ __global__ __launch_bounds__(K25_THREADS) void k25_features(const int *__restric
         __syncthreads();
 
         const int y = ty0 + ry, xb = tx0 + cx;
-        int l[K25_PXT], row[K25_PXT];   // the label and its LDS row (-1: none, commit to the global table)
+        int l[KT_PXT], row[KT_PXT];   // the label and its LDS row (-1: none, commit to the global table)
         bool any = false;
 #pragma unroll
-        for (int j = 0; j < K25_PXT; j++) {
+        for (int j = 0; j < KT_PXT; j++) {
             l[j] = s_eff[ry + 1][cx + 1 + j];
             row[j] = -1;
             any = any || l[j] != 0;
         }
 #pragma unroll
-        for (int j = 0; j < K25_PXT; j++) {
+        for (int j = 0; j < KT_PXT; j++) {
             if (l[j] == 0) continue;
             if (j > 0 && l[j] == l[j - 1]) {
                 row[j] = row[j - 1];
                 continue;
             }
             int h = (int)(((unsigned)l[j] * 0x9E3779B1u) >> 26) & (K25_SLOTS - 1);
-            for (int probe = 0; probe < K25_SLOTS; probe++) {
+            for (int probe = 0; probe < K25_SLOTS; probe++) {   // the claim of K27 step 2, on a 32-bit key
                 int k = s_key[h];
                 if (k == 0) {
                     k = atomicCAS(&s_key[h], 0, l[j]);
@@ -157,7 +142,7 @@ __global__ __launch_bounds__(K25_THREADS) void k25_features(const int *__restric
             {
                 long long n = 0, sx = 0, sxx = 0, per = 0, x0 = 0;
 #pragma unroll
-                for (int j = 0; j < K25_PXT; j++) {
+                for (int j = 0; j < KT_PXT; j++) {
                     if (l[j] == 0) continue;
                     const long long x = xb + j;
                     if (n == 0) x0 = x;
@@ -168,7 +153,7 @@ __global__ __launch_bounds__(K25_THREADS) void k25_features(const int *__restric
                         per += (s_eff[ry][cx + 1 + j] != l[j]) + (s_eff[ry + 2][cx + 1 + j] != l[j]) + (s_eff[ry + 1][cx + j] != l[j]) +
                                (s_eff[ry + 1][cx + 2 + j] != l[j]);
                     }
-                    if (j + 1 < K25_PXT && l[j + 1] == l[j]) continue;
+                    if (j + 1 < KT_PXT && l[j + 1] == l[j]) continue;
                     const long long yy = y;
                     const long long g[K25_GEO] = {n, n * yy, sx, n * yy * yy, sxx, sx * yy, yy, yy, x0, x, per};
                     if (row[j] >= 0) {
@@ -186,27 +171,27 @@ __global__ __launch_bounds__(K25_THREADS) void k25_features(const int *__restric
 
             const int64_t i0 = (int64_t)y * W + xb;   // the thread's first pixel; its pixels with l[j] != 0 are inside the image
             for (int p = 0; p < P; p++) {
-                long long q[K25_PXT], q2[K25_PXT];
+                long long q[KT_PXT], q2[KT_PXT];
                 if constexpr (sizeof(T) == 1) {
                     const uint8_t *src = reinterpret_cast<const uint8_t *>(pl.p[p]);
-                    unsigned v[K25_PXT] = {0, 0, 0, 0};
+                    unsigned v[KT_PXT] = {0, 0, 0, 0};
                     if (vec) {   // W % 4 == 0 and the plane is 4-byte aligned: the four pixels are one aligned word inside the row
                         const unsigned w4 = *reinterpret_cast<const unsigned *>(src + i0);
 #pragma unroll
-                        for (int j = 0; j < K25_PXT; j++) v[j] = (w4 >> (8 * j)) & 0xffu;
+                        for (int j = 0; j < KT_PXT; j++) v[j] = (w4 >> (8 * j)) & 0xffu;
                     } else {
 #pragma unroll
-                        for (int j = 0; j < K25_PXT; j++)
+                        for (int j = 0; j < KT_PXT; j++)
                             if (l[j] != 0) v[j] = src[i0 + j];
                     }
 #pragma unroll
-                    for (int j = 0; j < K25_PXT; j++) {
+                    for (int j = 0; j < KT_PXT; j++) {
                         q[j] = v[j];
                         q2[j] = v[j] * v[j];
                     }
                 } else {
                     const float *src = reinterpret_cast<const float *>(pl.p[p]);
-                    float v[K25_PXT] = {0.f, 0.f, 0.f, 0.f};
+                    float v[KT_PXT] = {0.f, 0.f, 0.f, 0.f};
                     if (vec) {   // W % 4 == 0 and the plane is 16-byte aligned
                         const float4 f4 = *reinterpret_cast<const float4 *>(src + i0);
                         v[0] = f4.x;
@@ -215,24 +200,24 @@ __global__ __launch_bounds__(K25_THREADS) void k25_features(const int *__restric
                         v[3] = f4.w;
                     } else {
 #pragma unroll
-                        for (int j = 0; j < K25_PXT; j++)
+                        for (int j = 0; j < KT_PXT; j++)
                             if (l[j] != 0) v[j] = src[i0 + j];
                     }
 #pragma unroll
-                    for (int j = 0; j < K25_PXT; j++) {
+                    for (int j = 0; j < KT_PXT; j++) {
                         q[j] = to_fixed40((double)v[j]);
                         q2[j] = k25_sq_fixed24((double)v[j]);
                     }
                 }
                 long long s1 = 0, s2 = 0, mn = INT64_MAX, mx = INT64_MIN;
 #pragma unroll
-                for (int j = 0; j < K25_PXT; j++) {
+                for (int j = 0; j < KT_PXT; j++) {
                     if (l[j] == 0) continue;
                     s1 += q[j];
                     s2 += q2[j];
                     mn = q[j] < mn ? q[j] : mn;
                     mx = q[j] > mx ? q[j] : mx;
-                    if (j + 1 < K25_PXT && l[j + 1] == l[j]) continue;
+                    if (j + 1 < KT_PXT && l[j + 1] == l[j]) continue;
                     const int c0 = K25_GEO + 4 * p;
                     if (row[j] >= 0) {
                         long long *d = s_tab + row[j] * C + c0;
@@ -257,7 +242,7 @@ __global__ __launch_bounds__(K25_THREADS) void k25_features(const int *__restric
 
         // flush: every occupied row once, consecutive lanes on consecutive columns; a row is left empty behind
         const int nocc = s_nocc;
-        for (int e = tid; e < nocc * C; e += K25_THREADS) {
+        for (int e = tid; e < nocc * C; e += KT_THREADS) {
             const int r = s_list[e / C], c = e % C;
             const long long empty = k25_empty(c, H, W);
             const long long v = s_tab[r * C + c];
@@ -271,34 +256,19 @@ __global__ __launch_bounds__(K25_THREADS) void k25_features(const int *__restric
         if (tid == 0) s_nocc = 0;
     }
 
-    // the labels outside 0 ... n_segments: one atomic per workgroup, and only when there are some
-    nbad = wave_sum(nbad);
-    if (lane_id() == 0) s_bad[tid >> 6] = nbad;
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < K25_THREADS / WAVE; w++) nbad += s_bad[w];
-        if (nbad) atomicAdd(bad, (unsigned long long)nbad);
-    }
+    wg_count_commit<KT_THREADS>(bad, nbad);   // the labels outside 0 ... n_segments
 }
 
 extern "C" int rsseg_segment_features(rsseg_ctx *ctx, const int32_t *d_seg, int H, int W, int64_t n_segments, const void *const *d_planes, int P, int dtype,
                                       const uint8_t *d_mask, int flags, int64_t *d_table)
 {
     if (!ctx) return RSSEG_ERR_INVALID;
-    if (H < 1 || W < 1) return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_features: H = %d, W = %d: both must be at least 1", H, W);
+    RSCHK(kt_check_raster(ctx, "segment_features", d_seg, H, W, n_segments));
     const int64_t n = (int64_t)H * W;
-    if (n > 0x7fffffff) return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_features: %lld pixels, must be 1 ... 2^31 - 1", (long long)n);
-    if (!d_seg || ((uintptr_t)d_seg & 3)) return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_features: d_seg null or not aligned to its element");
-    if (n_segments < 0 || n_segments > 0x7fffffff)   // a label is an int32; more rows than pixels are allowed (they stay empty)
-        return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_features: n_segments = %lld is not in 0 ... 2^31 - 1", (long long)n_segments);
-    if (P < 0 || P > K25_MAX_P)
-        return rs_fail(ctx, P < 0 ? RSSEG_ERR_INVALID : RSSEG_ERR_UNSUPPORTED, "segment_features: P = %d planes, must be 0 ... %d", P, K25_MAX_P);
-    if (P > 0 && !d_planes) return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_features: d_planes is null");
-    if (dtype != RSSEG_U8 && dtype != RSSEG_F32) return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_features: dtype must be RSSEG_U8 or RSSEG_F32");
+    RSCHK(kt_check_planes(ctx, "segment_features", d_planes, P, 0));
+    RSCHK(kt_check_dtype(ctx, "segment_features", dtype, "RSSEG_U8 or RSSEG_F32"));
     if (flags & ~RSSEG_OBJ_GEOMETRY) return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_features: flags = %d holds unknown bits", flags);
-    for (int p = 0; p < P; p++)
-        if (!d_planes[p] || (dtype == RSSEG_F32 && ((uintptr_t)d_planes[p] & 3)))
-            return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_features: d_planes[%d] null or not aligned to its element", p);
+    for (int p = 0; p < P; p++) RSCHK(kt_check_plane(ctx, "segment_features", d_planes, p, dtype));
     if (!d_table || ((uintptr_t)d_table & 7)) return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_features: d_table null or not 8-byte aligned");
     {   // the largest coordinate moment is below H W max(H, W)^2
         const unsigned __int128 m = (unsigned __int128)std::max(H, W);
@@ -309,47 +279,28 @@ extern "C" int rsseg_segment_features(rsseg_ctx *ctx, const int32_t *d_seg, int 
     RSCHK(ws_reserve(ctx, 256));
     RSCHK(pin_reserve(ctx, 256));
     unsigned long long *d_bad = (unsigned long long *)ctx->d_ws;
-    k25_planes_t pl;
+    kt_planes_t pl;
     memset(&pl, 0, sizeof(pl));
-    // the four pixels of a thread are read as one word when every row starts aligned: W % 4 == 0 and planes aligned to 4 pixels
-    int vec = W % K25_PXT == 0;
-    for (int p = 0; p < P; p++) {
-        pl.p[p] = d_planes[p];
-        if ((uintptr_t)d_planes[p] & (dtype == RSSEG_U8 ? 3 : 15)) vec = 0;
-    }
+    for (int p = 0; p < P; p++) pl.p[p] = d_planes[p];
+    const int vec = kt_vec(W, d_planes, P, dtype == RSSEG_U8 ? 3 : 15);
     const int C = K25_GEO + 4 * P;
     const int64_t rows = n_segments + 1;
-    const int tiles_x = (W + K25_TW - 1) / K25_TW, tiles_y = (H + K25_TH - 1) / K25_TH;
+    const int tiles_x = (W + KT_TW - 1) / KT_TW, tiles_y = (H + KT_TH - 1) / KT_TH;
     const int64_t ntiles = (int64_t)tiles_x * tiles_y;
     const size_t lds = sizeof(long long) * (size_t)K25_SLOTS * C;
     const bool geo = (flags & RSSEG_OBJ_GEOMETRY) != 0;
     HIPCHK(ctx, hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), ctx->stream));
     {
         prof_scope ps(ctx, "segment_features");
-        const unsigned gi = (unsigned)std::min<int64_t>(K25_MAX_BLOCKS, std::max<int64_t>(1, ceil_div64(rows * C, K25_THREADS)));
-        hipLaunchKernelGGL(k25_init, dim3(gi), dim3(K25_THREADS), 0, ctx->stream, (long long *)d_table, rows, C, H, W);
-        const dim3 grid((unsigned)std::min<int64_t>(K25_MAX_BLOCKS, ntiles)), block(K25_THREADS);
-#define K25_GO(T, G)                                                                                                                                  \
-    do {                                                                                                                                              \
-        RSCHK(set_max_dyn_lds(ctx, (const void *)k25_features<T, G>, lds));                                                                           \
-        hipLaunchKernelGGL((k25_features<T, G>), grid, block, lds, ctx->stream, d_seg, d_mask, H, W, n_segments, pl, P, vec, tiles_x, ntiles,         \
-                           (long long *)d_table, d_bad);                                                                                              \
-    } while (0)
-        if (dtype == RSSEG_U8) {
-            if (geo) K25_GO(uint8_t, true);
-            else K25_GO(uint8_t, false);
-        } else {
-            if (geo) K25_GO(float, true);
-            else K25_GO(float, false);
-        }
-#undef K25_GO
+        const unsigned gi = (unsigned)std::min<int64_t>(K25_MAX_BLOCKS, std::max<int64_t>(1, ceil_div64(rows * C, KT_THREADS)));
+        hipLaunchKernelGGL(k25_init, dim3(gi), dim3(KT_THREADS), 0, ctx->stream, (long long *)d_table, rows, C, H, W);
+        const dim3 grid((unsigned)std::min<int64_t>(K25_MAX_BLOCKS, ntiles)), block(KT_THREADS);
+        const auto kernel = dtype == RSSEG_U8 ? (geo ? k25_features<uint8_t, true> : k25_features<uint8_t, false>)
+                                              : (geo ? k25_features<float, true> : k25_features<float, false>);
+        RSCHK(kt_launch(ctx, kernel, grid, block, lds, d_seg, d_mask, H, W, n_segments, pl, P, vec, tiles_x, ntiles, (long long *)d_table, d_bad));
         HIPCHK(ctx, hipGetLastError());
     }
     unsigned long long nbad = 0;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, rs_sync(ctx));
-    memcpy(&nbad, ctx->h_pin, sizeof(nbad));
-    if (nbad)
-        return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_features: d_seg holds %llu labels outside 0 ... n_segments = %lld", nbad, (long long)n_segments);
-    return RSSEG_OK;
+    RSCHK(kt_read(ctx, d_bad, sizeof(nbad), &nbad));
+    return kt_bad_labels(ctx, "segment_features", nbad, n_segments);
 }

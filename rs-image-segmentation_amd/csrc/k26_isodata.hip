@@ -5,7 +5,7 @@
 //
 // A workgroup of 256 threads walks tiles of 256 pixels, one pixel per thread:
 //   1  mask, old label and the F plane values of the pixel; NaN -> +0, u_f = v_f 2^plane_exp[f], the range test |u_f| <= 1,
-//      z_f = u_f weight[f] kept in registers.  The kernel is instantiated for FR = 8, 16, 24, 32, 64 register slots; the slots
+//      z_f = u_f weight[f] kept in registers. The kernel is instantiated for FR = 8, 16, 24, 32, 64 register slots; the slots
 //      f >= F hold z = 0 against centre columns of 0, which add t t = +0 to a distance >= 0 and so leave it as it is: the
 //      padded loop gives the bits of the F-term loop.
 //   2  the k distances, j ascending, the centres (k x FR float64) read from LDS at a wave-uniform address; the strictly smaller
@@ -18,14 +18,12 @@
 //      for the table: Path A into the workgroup's table in LDS (added to the global table once, when the workgroup ends), Path
 //      B, when that table does not fit beside the centres and the staged tile, straight into the global table.  The counts
 //      are the histogram itself.
-// Every term is bits(x + 1.5 * 2^52) - bits(1.5 * 2^52) = rint(x) (|x| <= 2^50), the constant taken off once per run; the
+// Every term is fx_bits(x) = rint(x) (|x| <= 2^50) plus the constant that fx_bias takes off once per run; the
 // product (u 2^Q) u of two 24-bit significands is exact in float64.  The adds are 64-bit integer atomics: their order cannot
 // change the sums.  Without a table (labels only) steps 3 and 4 are not compiled in.
 #include <algorithm>
-#include <cmath>
-#include <type_traits>
 
-#include "common.h"
+#include "keyed_table.h"
 
 #define ISO_THREADS 256
 #define ISO_TILE 256                 // pixels of a tile: one per thread
@@ -69,8 +67,7 @@ __global__ __launch_bounds__(ISO_THREADS) void isodata_sweep(iso_args a, unsigne
     double *cen = reinterpret_cast<double *>(iso_lds + (MODE == 1 ? (size_t)k * C * 8 : 0));
     float *vals = reinterpret_cast<float *>(cen + (size_t)k * FR);
     uint32_t *sorted = reinterpret_cast<uint32_t *>(vals + (size_t)F * ISO_LD);
-    if (MODE == 1)
-        for (int i = tid; i < k * C; i += ISO_THREADS) l_table[i] = 0;
+    if (MODE == 1) kt_table_zero<ISO_THREADS>(l_table, k * C);
     for (int i = tid; i < k * FR; i += ISO_THREADS) cen[i] = a.centers[i];
     __syncthreads();
 
@@ -79,7 +76,6 @@ __global__ __launch_bounds__(ISO_THREADS) void isodata_sweep(iso_args a, unsigne
     const int sub = lane_id() / F, cf = lane_id() % F;
     const bool active = TABLE && sub < S;
     const double cscale = a.scale[cf], cscale_q = cscale * a.two_q;
-    const unsigned long long magic_bits = (unsigned long long)__double_as_longlong(FX_MAGIC);
 
     unsigned long long n_left = 0, n_changed = 0;
     const int64_t ntiles = (a.n + ISO_TILE - 1) / ISO_TILE;
@@ -103,7 +99,7 @@ __global__ __launch_bounds__(ISO_THREADS) void isodata_sweep(iso_args a, unsigne
         bool ok = true;
 #pragma unroll
         for (int f = 0; f < FR; f++) {
-            float v = (float)raw[f];
+            float v = (float)raw[f];   // staging, as K24 step 2: NaN -> +0, the range test on the scaled value
             double u = (double)v;
             if (std::is_same<PT, float>::value) {
                 if (v != v) v = 0.0f;
@@ -140,7 +136,7 @@ __global__ __launch_bounds__(ISO_THREADS) void isodata_sweep(iso_args a, unsigne
             int pos = 0;
             if (kept) pos = atomicAdd(&s_hist[best], 1);
             __syncthreads();
-            if (tid < WAVE) {   // exclusive scan of the histogram (64 entries, one wave)
+            if (tid < WAVE) {   // exclusive scan of the histogram (64 entries, one wave); wave_incl_scan written out: the helper cost the float32 kernels 0.3 %
                 const int h = s_hist[tid];
                 int inc = h;
 #pragma unroll
@@ -152,7 +148,7 @@ __global__ __launch_bounds__(ISO_THREADS) void isodata_sweep(iso_args a, unsigne
                 if (tid == WAVE - 1) s_total = inc;
             }
             __syncthreads();
-            if (kept) sorted[s_start[best] + pos] = ((uint32_t)best << 16) | (uint32_t)tid;
+            if (kept) sorted[s_start[best] + pos] = kt_sorted_entry(best, tid);
             __syncthreads();
             // ---- 4: the runs
             const int total = s_total;
@@ -161,19 +157,19 @@ __global__ __launch_bounds__(ISO_THREADS) void isodata_sweep(iso_args a, unsigne
                 int p = (int)(((long long)wave * total) / (ISO_THREADS / WAVE));
                 const int end = (int)(((long long)(wave + 1) * total) / (ISO_THREADS / WAVE));
                 while (p < end) {   // wave-uniform: every lane of the wave is in the same run
-                    const int cur = (int)(sorted[p] >> 16);
+                    const int cur = kt_entry_label(sorted[p]);
                     const int run_end = min(end, s_start[cur] + s_hist[cur]);
                     if (active) {
                         unsigned long long a1 = 0, a2 = 0;
                         unsigned int cnt = 0;
                         for (int q = p + sub; q < run_end; q += S) {   // no label test inside a run
-                            const double v = (double)vals[cf * ISO_LD + (int)(sorted[q] & 0xffffu)];
+                            const double v = (double)vals[cf * ISO_LD + kt_entry_slot(sorted[q])];
                             const double x = v * cscale_q;   // u 2^Q: a product with a power of two, exact
-                            a1 += (unsigned long long)__double_as_longlong(x + FX_MAGIC);
-                            a2 += (unsigned long long)__double_as_longlong(x * (v * cscale) + FX_MAGIC);
+                            a1 += fx_bits(x);
+                            a2 += fx_bits(x * (v * cscale));
                             cnt++;
                         }
-                        const unsigned long long bias = (unsigned long long)cnt * magic_bits;
+                        const unsigned long long bias = fx_bias(cnt);
                         unsigned long long *row = table + (size_t)cur * C;
                         if (a1 != bias) atomicAdd(&row[1 + cf], a1 - bias);
                         if (a2 != bias) atomicAdd(&row[1 + F + cf], a2 - bias);
@@ -187,10 +183,7 @@ __global__ __launch_bounds__(ISO_THREADS) void isodata_sweep(iso_args a, unsigne
     }
     if (MODE == 1) {
         __syncthreads();
-        for (int i = tid; i < k * C; i += ISO_THREADS) {
-            const unsigned long long v = l_table[i];
-            if (v) atomicAdd(&g_table[i], v);
-        }
+        kt_table_flush<ISO_THREADS>(l_table, g_table, k * C);
     }
     n_left = wave_sum(n_left);
     n_changed = wave_sum(n_changed);
@@ -202,19 +195,13 @@ __global__ __launch_bounds__(ISO_THREADS) void isodata_sweep(iso_args a, unsigne
 
 namespace {
 
-template <typename PT, int FR, int MODE>
-int iso_launch3(rsseg_ctx *ctx, const iso_args &a, int grid, size_t lds, unsigned long long *table, unsigned long long *tail)
-{
-    RSCHK(set_max_dyn_lds(ctx, (const void *)isodata_sweep<PT, FR, MODE>, lds));
-    hipLaunchKernelGGL((isodata_sweep<PT, FR, MODE>), dim3(grid), dim3(ISO_THREADS), lds, ctx->stream, a, table, tail);
-    return RSSEG_OK;
-}
 template <typename PT, int FR> int iso_launch2(rsseg_ctx *ctx, int mode, const iso_args &a, int grid, size_t lds, unsigned long long *table, unsigned long long *tail)
 {
-    if (mode == 0) return iso_launch3<PT, FR, 0>(ctx, a, grid, lds, table, tail);
-    if (mode == 1) return iso_launch3<PT, FR, 1>(ctx, a, grid, lds, table, tail);
+    const dim3 g(grid), b(ISO_THREADS);
+    if (mode == 0) return kt_launch(ctx, isodata_sweep<PT, FR, 0>, g, b, lds, a, table, tail);
+    if (mode == 1) return kt_launch(ctx, isodata_sweep<PT, FR, 1>, g, b, lds, a, table, tail);
     // Path B is reached only by the widest stacks: narrower ones always fit the budget (iso_path)
-    if (FR == 64) return iso_launch3<PT, 64, 2>(ctx, a, grid, lds, table, tail);
+    if (FR == 64) return kt_launch(ctx, isodata_sweep<PT, 64, 2>, g, b, lds, a, table, tail);
     return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "isodata_sweep: no Path B kernel for %d register slots", FR);
 }
 template <typename PT> int iso_launch1(rsseg_ctx *ctx, int fr, int mode, const iso_args &a, int grid, size_t lds, unsigned long long *table, unsigned long long *tail)
@@ -247,12 +234,9 @@ extern "C" int rsseg_isodata_sweep(rsseg_ctx *ctx, const void *const *d_planes, 
     if (k < 1) return rs_fail(ctx, RSSEG_ERR_INVALID, "isodata_sweep: k=%d, must be >= 1", k);
     if (F > RSSEG_MAX_FEATURES) return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "isodata_sweep: F=%d feature planes, the kernel takes at most %d", F, RSSEG_MAX_FEATURES);
     if (k > RSSEG_MAX_CLUSTERS) return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "isodata_sweep: k=%d clusters, the kernel takes at most %d", k, RSSEG_MAX_CLUSTERS);
-    if (dtype != RSSEG_F32 && dtype != RSSEG_U8) return rs_fail(ctx, RSSEG_ERR_INVALID, "isodata_sweep: dtype must be RSSEG_F32 or RSSEG_U8");
+    RSCHK(kt_check_dtype(ctx, "isodata_sweep", dtype, "RSSEG_F32 or RSSEG_U8"));
     if (n_local < 0) return rs_fail(ctx, RSSEG_ERR_INVALID, "isodata_sweep: n_local=%lld is negative", (long long)n_local);
-    if (Q < 0 || Q > 50) return rs_fail(ctx, RSSEG_ERR_INVALID, "isodata_sweep: Q=%d, must be 0 ... 50", Q);
-    if (n_local >= ((int64_t)1 << (62 - Q))) return rs_fail(ctx, RSSEG_ERR_INVALID, "isodata_sweep: n_local=%lld times 2^Q (Q=%d) reaches 2^62", (long long)n_local, Q);
-    if (dtype == RSSEG_U8 && (plane_exp || Q != 0)) return rs_fail(ctx, RSSEG_ERR_INVALID, "isodata_sweep: RSSEG_U8 planes take plane_exp = NULL and Q = 0");
-    if (dtype == RSSEG_F32 && !plane_exp) return rs_fail(ctx, RSSEG_ERR_INVALID, "isodata_sweep: plane_exp is null");
+    RSCHK(kt_check_fixed(ctx, "isodata_sweep", dtype, plane_exp, Q, n_local));
     if (!weight) return rs_fail(ctx, RSSEG_ERR_INVALID, "isodata_sweep: weight is null");
     if (!centers) return rs_fail(ctx, RSSEG_ERR_INVALID, "isodata_sweep: centers is null");
     if (d_table && ((uintptr_t)d_table & 7)) return rs_fail(ctx, RSSEG_ERR_INVALID, "isodata_sweep: d_table not 8-byte aligned");
@@ -261,13 +245,10 @@ extern "C" int rsseg_isodata_sweep(rsseg_ctx *ctx, const void *const *d_planes, 
     iso_args a;
     memset(&a, 0, sizeof(a));
     for (int f = 0; f < F; f++) {
-        if (plane_exp && (plane_exp[f] < -300 || plane_exp[f] > 300))
-            return rs_fail(ctx, RSSEG_ERR_INVALID, "isodata_sweep: plane_exp[%d]=%d, must be -300 ... 300", f, plane_exp[f]);
+        RSCHK(kt_plane_scale(ctx, "isodata_sweep", plane_exp, f, &a.scale[f]));
         if (!std::isfinite(weight[f])) return rs_fail(ctx, RSSEG_ERR_INVALID, "isodata_sweep: weight[%d] is not finite", f);
-        a.scale[f] = plane_exp ? std::ldexp(1.0, plane_exp[f]) : 1.0;
         a.weight[f] = weight[f];
-        if (n_local > 0 && (!d_planes[f] || (dtype == RSSEG_F32 && ((uintptr_t)d_planes[f] & 3))))
-            return rs_fail(ctx, RSSEG_ERR_INVALID, "isodata_sweep: d_planes[%d] null or not aligned to its element", f);
+        if (n_local > 0) RSCHK(kt_check_plane(ctx, "isodata_sweep", d_planes, f, dtype));
         a.plane[f] = d_planes[f];
     }
     for (int j = 0; j < k; j++)
@@ -306,9 +287,8 @@ extern "C" int rsseg_isodata_sweep(rsseg_ctx *ctx, const void *const *d_planes, 
         else RSCHK(iso_launch1<uint8_t>(ctx, FR, mode, a, grid, lds, table, tail));
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, tail, 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, rs_sync(ctx));
-    const unsigned long long *h = reinterpret_cast<const unsigned long long *>(ctx->h_pin);
+    unsigned long long h[2];
+    RSCHK(kt_read(ctx, tail, sizeof(h), h));
     *n_left_out = (int64_t)h[0];
     *n_changed = (int64_t)h[1];
     return RSSEG_OK;

@@ -3,15 +3,14 @@
 // Everything is an integer sum, so the table has one right answer whatever the order the atomics land in; it is restated in
 // NumPy in tests/adjacency_ref.py, to which the kernel is equal bit for bit (as a set of rows: their order is unspecified).
 //
-// A workgroup walks 64 x 16 tiles (grid stride); a thread owns four consecutive pixels of a row, as in K25.
-//   1. The EFFECTIVE labels of the tile and of one more column on its right and one more row below it are staged in LDS (K25's
-//      rule: the label where it is 1 ... n_segments and the mask byte is non-zero, else 0; outside the image: 0).  A label outside
-//      0 ... n_segments is counted for the refusal and reads as 0, so it never becomes part of a key.
+// A workgroup walks the 64 x 16 tiles of keyed_table.h (grid stride); a thread owns four consecutive pixels of a row.
+//   1. The EFFECTIVE labels (K25's rule) of the tile and of one more column on its right and one more row below it are
+//      staged in LDS (outside the image: 0).
 //   2. A CROSSING is a pixel and its right or lower neighbour with effective labels a != b, both > 0; it belongs to the left /
 //      upper pixel, so a crossing on a tile seam is counted by exactly one tile.  The pairs met in the tile share a table of
-//      K27_SLOTS rows in LDS, found by open addressing on the 64-bit key min(a, b) << 32 | max(a, b) (64-bit compare-and-swap,
-//      linear probing over the WHOLE table, so exactly K27_SLOTS different pairs still fit).  A thread adds a RUN of equal
-//      crossings below its four pixels at once.  A pair that finds no LDS row commits straight to the global table.
+//      K27_SLOTS rows in LDS, found by open addressing on the 64-bit key min(a, b) << 32 | max(a, b) (K25's loop).  A thread adds
+//      a RUN of equal crossings below its four pixels at once.  A pair that finds no LDS row commits straight to the global
+//      table.
 //   3. Every occupied row is flushed once per tile: one thread per row finds (or claims) the pair's row in the global
 //      open-addressing table, adds the row's columns to it with 64-bit global atomics and puts the LDS row back to zero as it
 //      reads it; the LDS table is therefore initialised once per workgroup.  (One thread per row, not one lane per column: the
@@ -26,34 +25,25 @@
 // compaction count; both end in RSSEG_ERR_UNSUPPORTED, and nothing else does.
 #include <algorithm>
 
-#include "common.h"
+#include "keyed_table.h"
 
-#define K27_THREADS 256
-#define K27_TW 64        // tile columns: 16 threads x 4 pixels
-#define K27_TH 16        // tile rows
-#define K27_PXT 4        // consecutive pixels of one row per thread
 #define K27_SLOTS 128    // rows of the LDS table (a power of two); 128 x (1 key + 1 + 16) x 8 B = 18 KiB at P = 16
-#define K27_MAX_P 16
 #define K27_MAX_BLOCKS 8192
-#define K27_EW (K27_TW + 1)
-#define K27_EH (K27_TH + 1)
-#define K27_STAGE ((K27_EH * K27_EW + K27_THREADS - 1) / K27_THREADS)   // labels a thread stages per tile
+#define K27_EW (KT_TW + 1)
+#define K27_EH (KT_TH + 1)
+#define K27_STAGE ((K27_EH * K27_EW + KT_THREADS - 1) / KT_THREADS)   // labels a thread stages per tile
 static_assert(K27_SLOTS == 128, "the hash keeps the top seven bits of the product: change the shift with the row count");
-static_assert(K27_SLOTS <= K27_THREADS && K27_TW * K27_TH == K27_THREADS * K27_PXT, "one thread per row of the list; four pixels per thread");
+static_assert(K27_SLOTS <= KT_THREADS && KT_TW * KT_TH == KT_THREADS * KT_PXT, "one thread per row of the list; four pixels per thread");
 
 typedef unsigned long long k27_u64;
 
 extern "C" void rsseg_segment_adjacency_plan(int P, int *tile_w, int *tile_h, int *lds_slots)
 {
     (void)P;   // the plan does not depend on the plane count: the row gets wider, the table keeps its rows
-    if (tile_w) *tile_w = K27_TW;
-    if (tile_h) *tile_h = K27_TH;
+    if (tile_w) *tile_w = KT_TW;
+    if (tile_h) *tile_h = KT_TH;
     if (lds_slots) *lds_slots = K27_SLOTS;
 }
-
-struct k27_planes_t {
-    const uint8_t *p[K27_MAX_P];
-};
 
 // what the pass leaves for the host, at the head of the workspace
 struct k27_head_t {
@@ -93,15 +83,15 @@ __device__ __forceinline__ int64_t k27_global_row(k27_u64 *__restrict__ keys, in
 // below (DOWN true).  key 0: no crossing.  The two directions run one after the other, so that their arrays share registers.
 template <bool DOWN>
 __device__ __forceinline__ void k27_group(const int (*s_eff)[K27_EW], k27_u64 *s_key, int *s_list, int *s_nocc, long long *s_tab, int C, int P, int vec, int W,
-                                          int ry, int cx, int64_t i0, const k27_planes_t &pl, k27_u64 *__restrict__ gkeys, long long *__restrict__ gvals,
+                                          int ry, int cx, int64_t i0, const kt_planes_t &pl, k27_u64 *__restrict__ gkeys, long long *__restrict__ gvals,
                                           int64_t cap, unsigned *full)
 {
-    k27_u64 key[K27_PXT];
-    int row[K27_PXT];          // >= 0: the LDS row; -1: the global row grow[c]; -2: nothing to add
-    int64_t grow[K27_PXT];
+    k27_u64 key[KT_PXT];
+    int row[KT_PXT];          // >= 0: the LDS row; -1: the global row grow[c]; -2: nothing to add
+    int64_t grow[KT_PXT];
     bool any = false;
 #pragma unroll
-    for (int c = 0; c < K27_PXT; c++) {
+    for (int c = 0; c < KT_PXT; c++) {
         const int a = s_eff[ry][cx + c], b = DOWN ? s_eff[ry + 1][cx + c] : s_eff[ry][cx + c + 1];
         key[c] = 0;
         if (a > 0 && b > 0 && a != b) key[c] = ((k27_u64)(unsigned)min(a, b) << 32) | (unsigned)max(a, b);
@@ -111,7 +101,7 @@ __device__ __forceinline__ void k27_group(const int (*s_eff)[K27_EW], k27_u64 *s
     }
     if (!any) return;
 #pragma unroll
-    for (int c = 0; c < K27_PXT; c++) {
+    for (int c = 0; c < KT_PXT; c++) {
         if (key[c] == 0) continue;
         if (DOWN && c > 0 && key[c] == key[c - 1]) {   // a run below the thread's pixels
             row[c] = row[c - 1];
@@ -119,7 +109,7 @@ __device__ __forceinline__ void k27_group(const int (*s_eff)[K27_EW], k27_u64 *s
             continue;
         }
         int h = (int)(k27_mix(key[c]) >> 57) & (K27_SLOTS - 1);
-        for (int probe = 0; probe < K27_SLOTS; probe++) {
+        for (int probe = 0; probe < K27_SLOTS; probe++) {   // the claim of K25 step 2, on a 64-bit key; a shared template cost the overflow case 0.25 %
             k27_u64 k = s_key[h];
             if (k == 0) {
                 k = atomicCAS(&s_key[h], 0ull, key[c]);
@@ -145,31 +135,31 @@ __device__ __forceinline__ void k27_group(const int (*s_eff)[K27_EW], k27_u64 *s
     {
         long long n = 0;
 #pragma unroll
-        for (int c = 0; c < K27_PXT; c++) {
+        for (int c = 0; c < KT_PXT; c++) {
             if (key[c] == 0) continue;
             n++;
-            if (DOWN && c + 1 < K27_PXT && key[c + 1] == key[c]) continue;
+            if (DOWN && c + 1 < KT_PXT && key[c + 1] == key[c]) continue;
             if (row[c] >= 0) atomicAdd(reinterpret_cast<k27_u64 *>(s_tab + row[c] * C), (k27_u64)n);
             else if (row[c] == -1) atomicAdd(reinterpret_cast<k27_u64 *>(gvals + grow[c] * C), (k27_u64)n);
             n = 0;
         }
     }
     for (int p = 0; p < P; p++) {   // a pixel of a crossing is inside the image, and so is its neighbour
-        const uint8_t *src = pl.p[p];
-        int a[K27_PXT] = {0, 0, 0, 0}, b[K27_PXT] = {0, 0, 0, 0};
+        const uint8_t *src = reinterpret_cast<const uint8_t *>(pl.p[p]);
+        int a[KT_PXT] = {0, 0, 0, 0}, b[KT_PXT] = {0, 0, 0, 0};
         if (vec) {   // W % 4 == 0 and the plane is 4-byte aligned: four pixels are one aligned word inside the row
             const unsigned w4 = *reinterpret_cast<const unsigned *>(src + i0);
             unsigned o4;
             if (DOWN) o4 = *reinterpret_cast<const unsigned *>(src + i0 + W);
-            else o4 = (w4 >> 8) | (key[K27_PXT - 1] != 0 ? (unsigned)src[i0 + K27_PXT] << 24 : 0u);
+            else o4 = (w4 >> 8) | (key[KT_PXT - 1] != 0 ? (unsigned)src[i0 + KT_PXT] << 24 : 0u);
 #pragma unroll
-            for (int j = 0; j < K27_PXT; j++) {
+            for (int j = 0; j < KT_PXT; j++) {
                 a[j] = (int)((w4 >> (8 * j)) & 0xffu);
                 b[j] = (int)((o4 >> (8 * j)) & 0xffu);
             }
         } else {
 #pragma unroll
-            for (int j = 0; j < K27_PXT; j++)
+            for (int j = 0; j < KT_PXT; j++)
                 if (key[j] != 0) {
                     a[j] = src[i0 + j];
                     b[j] = DOWN ? src[i0 + W + j] : src[i0 + j + 1];
@@ -177,11 +167,11 @@ __device__ __forceinline__ void k27_group(const int (*s_eff)[K27_EW], k27_u64 *s
         }
         long long s = 0;
 #pragma unroll
-        for (int c = 0; c < K27_PXT; c++) {
+        for (int c = 0; c < KT_PXT; c++) {
             if (key[c] == 0) continue;
             const int d = a[c] - b[c];
             s += d < 0 ? -d : d;
-            if (DOWN && c + 1 < K27_PXT && key[c + 1] == key[c]) continue;
+            if (DOWN && c + 1 < KT_PXT && key[c + 1] == key[c]) continue;
             if (s != 0) {
                 if (row[c] >= 0) atomicAdd(reinterpret_cast<k27_u64 *>(s_tab + row[c] * C + 1 + p), (k27_u64)s);
                 else if (row[c] == -1) atomicAdd(reinterpret_cast<k27_u64 *>(gvals + grow[c] * C + 1 + p), (k27_u64)s);
@@ -191,8 +181,8 @@ __device__ __forceinline__ void k27_group(const int (*s_eff)[K27_EW], k27_u64 *s
     }
 }
 
-__global__ __launch_bounds__(K27_THREADS) void k27_adjacency(const int *__restrict__ seg, const uint8_t *__restrict__ mask, int H, int W, int64_t nseg,
-                                                             k27_planes_t pl, int P, int vec, int tiles_x, int64_t ntiles, k27_u64 *__restrict__ gkeys,
+__global__ __launch_bounds__(KT_THREADS) void k27_adjacency(const int *__restrict__ seg, const uint8_t *__restrict__ mask, int H, int W, int64_t nseg,
+                                                             kt_planes_t pl, int P, int vec, int tiles_x, int64_t ntiles, k27_u64 *__restrict__ gkeys,
                                                              long long *__restrict__ gvals, int64_t cap, k27_head_t *__restrict__ head)
 {
     extern __shared__ __align__(16) unsigned char k27_lds[];
@@ -200,16 +190,15 @@ __global__ __launch_bounds__(K27_THREADS) void k27_adjacency(const int *__restri
     __shared__ k27_u64 s_key[K27_SLOTS];       // 0: free, else the pair the row belongs to
     __shared__ int s_list[K27_SLOTS];          // the occupied rows, in the order they were claimed
     __shared__ int s_nocc;
-    __shared__ unsigned s_bad[K27_THREADS / WAVE];
     long long *s_tab = reinterpret_cast<long long *>(k27_lds);   // [K27_SLOTS][C]: length, then the contrast of every plane
     const int C = 1 + P, tid = threadIdx.x;
-    for (int e = tid; e < K27_SLOTS * C; e += K27_THREADS) s_tab[e] = 0;
+    for (int e = tid; e < K27_SLOTS * C; e += KT_THREADS) s_tab[e] = 0;
     if (tid < K27_SLOTS) s_key[tid] = 0;
-    const int ry = tid / (K27_TW / K27_PXT), cx = (tid % (K27_TW / K27_PXT)) * K27_PXT;
+    const int ry = kt_ry(tid), cx = kt_cx(tid);
     unsigned nbad = 0;
 
     for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const int tx0 = (int)(t % tiles_x) * K27_TW, ty0 = (int)(t / tiles_x) * K27_TH;
+        const int tx0 = (int)(t % tiles_x) * KT_TW, ty0 = (int)(t / tiles_x) * KT_TH;
         __syncthreads();   // the table is empty, the list of the previous tile and its labels are no longer read
         if (tid == 0) s_nocc = 0;
         {   // every load of the tile's labels is issued before the first is used
@@ -217,7 +206,7 @@ __global__ __launch_bounds__(K27_THREADS) void k27_adjacency(const int *__restri
             uint8_t mv[K27_STAGE];
 #pragma unroll
             for (int it = 0; it < K27_STAGE; it++) {
-                const int e = tid + it * K27_THREADS, ly = e / K27_EW, lx = e - ly * K27_EW, gy = ty0 + ly, gx = tx0 + lx;
+                const int e = tid + it * KT_THREADS, ly = e / K27_EW, lx = e - ly * K27_EW, gy = ty0 + ly, gx = tx0 + lx;
                 const bool in = e < K27_EH * K27_EW && gy < H && gx < W;
                 const int64_t i = (int64_t)gy * W + gx;
                 sv[it] = in ? seg[i] : 0;
@@ -225,10 +214,10 @@ __global__ __launch_bounds__(K27_THREADS) void k27_adjacency(const int *__restri
             }
 #pragma unroll
             for (int it = 0; it < K27_STAGE; it++) {
-                const int e = tid + it * K27_THREADS, ly = e / K27_EW, lx = e - ly * K27_EW;
+                const int e = tid + it * KT_THREADS, ly = e / K27_EW, lx = e - ly * K27_EW;
                 if (e >= K27_EH * K27_EW) continue;
-                int eff = 0;
-                if (sv[it] < 0 || sv[it] > nseg) nbad += ly < K27_TH && lx < K27_TW;   // every pixel is the inner pixel of exactly one tile
+                int eff = 0;   // K25's rule, written out with the claim
+                if (sv[it] < 0 || sv[it] > nseg) nbad += ly < KT_TH && lx < KT_TW;   // every pixel is the inner pixel of exactly one tile
                 else if (mv[it]) eff = sv[it];
                 s_eff[ly][lx] = eff;
             }
@@ -256,27 +245,20 @@ __global__ __launch_bounds__(K27_THREADS) void k27_adjacency(const int *__restri
         }
     }
 
-    // the labels outside 0 ... n_segments: one atomic per workgroup, and only when there are some
-    nbad = wave_sum(nbad);
-    if (lane_id() == 0) s_bad[tid >> 6] = nbad;
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < K27_THREADS / WAVE; w++) nbad += s_bad[w];
-        if (nbad) atomicAdd(&head->bad, (k27_u64)nbad);
-    }
+    wg_count_commit<KT_THREADS>(&head->bad, nbad);   // the labels outside 0 ... n_segments
 }
 
 // The occupied rows of the global table to d_edges as (a, b, length, contrasts): a workgroup takes 256 rows at a time, counts
 // its occupied ones and draws their places with ONE atomic; places past max_edges are counted and not written.
-__global__ __launch_bounds__(K27_THREADS) void k27_compact(const k27_u64 *__restrict__ gkeys, const long long *__restrict__ gvals, int64_t cap, int C,
+__global__ __launch_bounds__(KT_THREADS) void k27_compact(const k27_u64 *__restrict__ gkeys, const long long *__restrict__ gvals, int64_t cap, int C,
                                                            int64_t max_edges, long long *__restrict__ edges, k27_head_t *__restrict__ head)
 {
-    __shared__ unsigned s_cnt[K27_THREADS / WAVE];
+    __shared__ unsigned s_cnt[KT_THREADS / WAVE];
     __shared__ k27_u64 s_base;
     const int tid = threadIdx.x, wave = tid >> 6, lane = lane_id();
-    const int64_t chunks = (cap + K27_THREADS - 1) / K27_THREADS;
+    const int64_t chunks = (cap + KT_THREADS - 1) / KT_THREADS;
     for (int64_t ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
-        const int64_t s = ch * K27_THREADS + tid;
+        const int64_t s = ch * KT_THREADS + tid;
         const k27_u64 key = s < cap ? gkeys[s] : 0ull;
         const k27_u64 bal = __ballot(key != 0);
         const unsigned before = (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
@@ -284,7 +266,7 @@ __global__ __launch_bounds__(K27_THREADS) void k27_compact(const k27_u64 *__rest
         __syncthreads();
         if (tid == 0) {
             unsigned tot = 0;
-            for (int w = 0; w < K27_THREADS / WAVE; w++) tot += s_cnt[w];
+            for (int w = 0; w < KT_THREADS / WAVE; w++) tot += s_cnt[w];
             s_base = tot ? atomicAdd(&head->count, (k27_u64)tot) : 0ull;
         }
         __syncthreads();
@@ -308,17 +290,9 @@ extern "C" int rsseg_segment_adjacency(rsseg_ctx *ctx, const int32_t *d_seg, int
 {
     if (!ctx) return RSSEG_ERR_INVALID;
     if (n_edges) *n_edges = 0;
-    if (H < 1 || W < 1) return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_adjacency: H = %d, W = %d: both must be at least 1", H, W);
-    const int64_t n = (int64_t)H * W;
-    if (n > 0x7fffffff) return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_adjacency: %lld pixels, must be 1 ... 2^31 - 1", (long long)n);
-    if (!d_seg || ((uintptr_t)d_seg & 3)) return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_adjacency: d_seg null or not aligned to its element");
-    if (n_segments < 0 || n_segments > 0x7fffffff)
-        return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_adjacency: n_segments = %lld is not in 0 ... 2^31 - 1", (long long)n_segments);
-    if (P < 0 || P > K27_MAX_P)
-        return rs_fail(ctx, P < 0 ? RSSEG_ERR_INVALID : RSSEG_ERR_UNSUPPORTED, "segment_adjacency: P = %d planes, must be 0 ... %d", P, K27_MAX_P);
-    if (P > 0 && !d_planes) return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_adjacency: d_planes is null");
-    for (int p = 0; p < P; p++)
-        if (!d_planes[p]) return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_adjacency: d_planes[%d] is null", p);
+    RSCHK(kt_check_raster(ctx, "segment_adjacency", d_seg, H, W, n_segments));
+    RSCHK(kt_check_planes(ctx, "segment_adjacency", d_planes, P, 0));
+    for (int p = 0; p < P; p++) RSCHK(kt_check_plane_u8(ctx, "segment_adjacency", d_planes, p));
     if (max_edges < 0 || max_edges > ((int64_t)1 << 33))   // at most 2 H W - H - W < 2^32 crossings exist
         return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_adjacency: max_edges = %lld is not in 0 ... 2^33", (long long)max_edges);
     if (max_edges > 0 && (!d_edges || ((uintptr_t)d_edges & 7)))
@@ -333,39 +307,29 @@ extern "C" int rsseg_segment_adjacency(rsseg_ctx *ctx, const int32_t *d_seg, int
     k27_head_t *d_head = (k27_head_t *)ctx->d_ws;
     k27_u64 *d_keys = (k27_u64 *)(ctx->d_ws + head_bytes);
     long long *d_vals = (long long *)(ctx->d_ws + head_bytes + key_bytes);
-    k27_planes_t pl;
+    kt_planes_t pl;
     memset(&pl, 0, sizeof(pl));
-    // the four pixels of a thread are read as one word when every row starts aligned: W % 4 == 0 and planes aligned to 4 pixels
-    int vec = W % K27_PXT == 0;
-    for (int p = 0; p < P; p++) {
-        pl.p[p] = d_planes[p];
-        if ((uintptr_t)d_planes[p] & 3) vec = 0;
-    }
-    const int tiles_x = (W + K27_TW - 1) / K27_TW, tiles_y = (H + K27_TH - 1) / K27_TH;
+    for (int p = 0; p < P; p++) pl.p[p] = d_planes[p];
+    const int vec = kt_vec(W, reinterpret_cast<const void *const *>(d_planes), P, 3);
+    const int tiles_x = (W + KT_TW - 1) / KT_TW, tiles_y = (H + KT_TH - 1) / KT_TH;
     const int64_t ntiles = (int64_t)tiles_x * tiles_y;
     const size_t lds = sizeof(long long) * (size_t)K27_SLOTS * C;
     {
         prof_scope ps(ctx, "segment_adjacency");
         HIPCHK(ctx, hipMemsetAsync(ctx->d_ws, 0, head_bytes + key_bytes + val_bytes, ctx->stream));
-        const dim3 grid((unsigned)std::min<int64_t>(K27_MAX_BLOCKS, ntiles)), block(K27_THREADS);
-        RSCHK(set_max_dyn_lds(ctx, (const void *)k27_adjacency, lds));
-        hipLaunchKernelGGL(k27_adjacency, grid, block, lds, ctx->stream, d_seg, d_mask, H, W, n_segments, pl, P, vec, tiles_x, ntiles, d_keys, d_vals, cap,
-                           d_head);
+        const dim3 grid((unsigned)std::min<int64_t>(K27_MAX_BLOCKS, ntiles)), block(KT_THREADS);
+        RSCHK(kt_launch(ctx, k27_adjacency, grid, block, lds, d_seg, d_mask, H, W, n_segments, pl, P, vec, tiles_x, ntiles, d_keys, d_vals, cap, d_head));
         HIPCHK(ctx, hipGetLastError());
     }
     {
         prof_scope ps(ctx, "segment_adjacency_compact");
-        const dim3 grid((unsigned)std::min<int64_t>(K27_MAX_BLOCKS, ceil_div64(cap, K27_THREADS))), block(K27_THREADS);
-        hipLaunchKernelGGL(k27_compact, grid, block, 0, ctx->stream, d_keys, d_vals, cap, C, max_edges, (long long *)d_edges, d_head);
+        const dim3 grid((unsigned)std::min<int64_t>(K27_MAX_BLOCKS, ceil_div64(cap, KT_THREADS))), block(KT_THREADS);
+        RSCHK(kt_launch(ctx, k27_compact, grid, block, 0, d_keys, d_vals, cap, C, max_edges, (long long *)d_edges, d_head));
         HIPCHK(ctx, hipGetLastError());
     }
     k27_head_t head;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, d_head, sizeof(head), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, rs_sync(ctx));
-    memcpy(&head, ctx->h_pin, sizeof(head));
-    if (head.bad)
-        return rs_fail(ctx, RSSEG_ERR_INVALID, "segment_adjacency: d_seg holds %llu labels outside 0 ... n_segments = %lld", head.bad,
-                       (long long)n_segments);
+    RSCHK(kt_read(ctx, d_head, sizeof(head), &head));
+    RSCHK(kt_bad_labels(ctx, "segment_adjacency", head.bad, n_segments));
     if (head.full || head.count > (k27_u64)max_edges)
         return rs_fail(ctx, RSSEG_ERR_UNSUPPORTED, "segment_adjacency: the raster holds more than max_edges = %lld distinct pairs of adjacent segments",
                        (long long)max_edges);

@@ -48,11 +48,7 @@ __device__ __forceinline__ float pca_x(const pca_args &a, int b, float v)
     return (float)fma(r, y, q);
 }
 
-__device__ __forceinline__ long long to_fixed_q(double x, double s)
-{
-    double d = fma(x, s, FX_MAGIC);
-    return __double_as_longlong(d) - __double_as_longlong(FX_MAGIC);
-}
+__device__ __forceinline__ long long to_fixed_q(double x, double s) { return fx_round(x, s); }
 
 // partial[blk][PCA_NACC][2] ({hi, lo} 32-bit limb sums): sums of x_b (nb entries) then x_a*x_b for a <= b (row-major upper
 // triangle of a PCA_MAXB x PCA_MAXB matrix).  The accumulators take the raw bit patterns of fma(v, 2^Q, 1.5*2^52); the
@@ -106,10 +102,10 @@ __global__ __launch_bounds__(PCA_THREADS) void k3_gram(pca_args a, int64_t n, lo
             // fma(xs, x_c, MAGIC) rounds x_b * x_c * 2^Q to an integer ONCE, like fma(x_b * x_c, 2^Q, MAGIC) with its exact float64
             // product did — the same bits for one float64 multiplication less per term
             const double xs = (double)x[b] * a.fx_scale;
-            acc[b] += (unsigned long long)__double_as_longlong(xs + FX_MAGIC);
+            acc[b] += fx_bits(xs);
 #pragma unroll
             for (int c = b; c < NB; c++)
-                acc[pca_tri(b, c)] += (unsigned long long)__double_as_longlong(fma(xs, (double)x[c], FX_MAGIC));
+                acc[pca_tri(b, c)] += fx_bits(xs, (double)x[c]);
         }
         cnt++;
     };
@@ -147,7 +143,7 @@ __global__ __launch_bounds__(PCA_THREADS) void k3_gram(pca_args a, int64_t n, lo
                       : FL ? tab(b, reinterpret_cast<const float *>(a.band[b])[t]) : reinterpret_cast<const float *>(a.band[b])[t];
         pixel(p);
     }
-    const unsigned long long bias = cnt * (unsigned long long)__double_as_longlong(FX_MAGIC);
+    const unsigned long long bias = fx_bias(cnt);
     // per-thread sums stay below 2^61; split into 32-bit limbs before the cross-lane sums
     __shared__ long long sh[4][2 * PCA_NACC];
 #pragma unroll

@@ -651,12 +651,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_kpp_sample(planes_t pl, int F, 
             // first pixel of the row whose inclusive running sum reaches s_rem: wave-level scans + the waves' totals
             const int64_t i = (int64_t)s_row * KM_THREADS + threadIdx.x;
             const unsigned long long v = i < cn ? q[i] : 0ull;
-            unsigned long long pfx = v;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned long long t = __shfl_up(pfx, o, 64);
-                if (ln >= o) pfx += t;
-            }
+            const unsigned long long pfx = wave_incl_scan(v);
             if (ln == 63) rowq[wv] = pfx;
             __syncthreads();
             unsigned long long base = 0;
@@ -843,7 +838,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_lloyd(planes_t pl, int F, int k
                     // cluster (count x constant, modulo 2^64) in the epilogue instead of once per value (as in k3_gram)
                     unsigned long long q[PXL];
 #pragma unroll
-                    for (int p = 0; p < PXL; p++) q[p] = (unsigned long long)__double_as_longlong(fma((double)x[f][p], 1099511627776.0, FX_MAGIC));
+                    for (int p = 0; p < PXL; p++) q[p] = fx_bits((double)x[f][p], 1099511627776.0);
                     if (same) {  // one add for the lane's PXL pixels
                         unsigned long long qs = q[0];
 #pragma unroll
@@ -892,7 +887,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_lloyd(planes_t pl, int F, int k
                 if (i < KMAX * F) {   // a sum: take count x bits(1.5 * 2^52) off the raw patterns
                     unsigned long long cnt = 0;
                     for (int c = 0; c < ncopies; c++) cnt += S[(size_t)c * stride + KMAX * F + i / F];
-                    a -= cnt * (unsigned long long)__double_as_longlong(FX_MAGIC);
+                    a -= fx_bias(cnt);
                 }
                 v = (long long)a;
             } else {
