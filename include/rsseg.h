@@ -434,6 +434,49 @@ int rsseg_gauss_classify(rsseg_ctx *ctx, const void *const *d_planes, int F, int
                          const uint8_t *class_values, double max_dist2,
                          uint8_t *d_labels, float *d_dist2 /* or NULL */, float *d_margin /* or NULL */);
 
+/* ---- K28: support vector machine classification (one-vs-one, libsvm's decision rule) ----------- */
+#define RSSEG_SVM_RBF 0
+#define RSSEG_SVM_POLY 1
+#define RSSEG_SVM_LINEAR 2
+#define RSSEG_SVM_MAX_CLASSES 16
+#define RSSEG_SVM_MAX_SV 16384
+#define RSSEG_SVM_MAX_DEGREE 8
+/* One per-pixel sweep over F feature planes (RSSEG_F32 or RSSEG_F64, band-planar) for a model of k classes and S support
+ * vectors, all host arrays, float64 unless said otherwise: offset[F] and scale[F] (finite, scale != 0); sv[S][F], the support
+ * vectors in scaled units, grouped by class with the classes ascending (scikit-learn's order); n_support[k] (int, each >= 1,
+ * summing to S); coef[k - 1][S] (scikit-learn's _dual_coef_); bias[P], P = k (k - 1) / 2, libsvm's -rho (scikit-learn's
+ * _intercept_); class_values[k], distinct and 1..255; kernel, gamma, coef0, degree; w[P][F], the folded weights of the LINEAR
+ * kernel (NULL otherwise).
+ * Per pixel, in float64, every line one IEEE operation:
+ *   x_f = the plane value widened, a NaN read as 0; a pixel with any +-inf x_f gets label 0 and margin NaN
+ *   z_f = (x_f - offset_f) * scale_f
+ *   RBF, per support vector i:   q = +0; f ascending: d = z_f - sv_if, q = fma(d, d, q);  K_i = svm_exp(-(gamma * q))
+ *   POLY:   t = +0; f ascending: t = fma(sv_if, z_f, t);  u = fma(gamma, t, coef0);  K_i = u, then degree - 1 times K_i = K_i * u
+ *   pairs p = (a, b), a < b, in the order (0,1), (0,2), ..., (k-2,k-1):  s = +0; over class a's support vectors ascending
+ *   s = fma(coef[b-1][i], K_i, s), then over class b's s = fma(coef[a][i], K_i, s);  d_p = s + bias_p.  No term is skipped.
+ *   LINEAR: d_p = (t = +0; f ascending: t = fma(w_pf, z_f, t)) + bias_p
+ *   d_p > 0 is a vote for a, anything else (a NaN too) for b; the label is the lowest class index with the most votes
+ *   margin = float32(the smallest |d_p| over the pairs that hold the winner); a NaN |d_p| is never the smallest (all NaN: +inf)
+ * svm_exp(t), t <= 0:  t < -708 gives +0.  n = rint(t * LOG2E);  r = fma(-n, LN2_HI, t);  r = fma(-n, LN2_LO, r);  p = c_13,
+ *   then j = 12 ... 0: p = fma(p, r, c_j), c_j the double nearest 1 / j!;  the result is p * 2^n, 2^n built from its exponent
+ *   field (normal for every admitted t).  LOG2E = 0x3FF71547652B82FE, LN2_HI = 0x3FE62E42FEE00000, LN2_LO = 0x3DEA39EF35793C76.
+ *   d_labels  class_values[winner], 0 for a pixel with an infinite plane value
+ *   d_margin  NULL or float32
+ * The kernel equals tests/svm_ref.py bit for bit.  Limits: 1 <= F <= 64, 2 <= k <= 16, 1 <= S <= 16384, 1 <= degree <= 8; beyond
+ * them, or a kernel that is none of the three, RSSEG_ERR_UNSUPPORTED.  RSSEG_ERR_INVALID, naming the argument: k < 2, S < 1,
+ * degree < 1, a null or misaligned plane or output, a missing model array, a non-finite model value, a scale of 0, an
+ * n_support below 1 or not summing to S, a class value of 0 or one that occurs twice, an RBF gamma that is not > 0.
+ * n == 0 returns RSSEG_OK and touches nothing.  Planes and outputs may have any alignment that holds their element.
+ * Synchronous.  Profiler name "svm_classify". */
+int rsseg_svm_classify(rsseg_ctx *ctx, const void *const *d_planes, int F, int dtype /* RSSEG_F32 | RSSEG_F64 */, int64_t n, int k, int S,
+                       const double *offset, const double *scale, const double *sv, const int *n_support, const double *coef,
+                       const double *bias, const uint8_t *class_values, int kernel /* RSSEG_SVM_* */, double gamma, double coef0, int degree,
+                       const double *w /* LINEAR, else NULL */, uint8_t *d_labels, float *d_margin /* or NULL */);
+/* The LINEAR kernel's folded weights w[P][F] (host, no context): for the pair p = (a, b) and the feature f the fma chain from
+ * +0 of coef[b-1][i] * sv[i][f] over class a's support vectors ascending, then of coef[a][i] * sv[i][f] over class b's.
+ * RSSEG_ERR_INVALID for a null array, F < 1, k < 2, S < 1 or an n_support that does not sum to S; k > 16 RSSEG_ERR_UNSUPPORTED. */
+int rsseg_host_svm_fold_linear(int F, int k, int S, const double *sv, const int *n_support, const double *coef, double *w);
+
 /* ---- K11: random-forest inference ---------------------------------------------------------- */
 /* Flattened sklearn forest (tree_ arrays concatenated; children are tree-local, -1 = leaf).
  * value: (n_nodes_total x n_classes) float64 class fractions.  The forest is copied to the device

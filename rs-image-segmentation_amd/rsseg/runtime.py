@@ -1050,6 +1050,57 @@ class Context:
                                                 C.c_void_p(margin.data_ptr()) if want_margin else None))
         return labels[:n], (dist2[:n] if want_dist2 else None), (margin[:n] if want_margin else None)
 
+    # ---- K28: support vector machine classification (rsseg/svm.py) ---------------------------------
+    SVM_KERNELS = {"rbf": 0, "poly": 1, "linear": 2}   # RSSEG_SVM_*
+
+    def svm_classify(self, planes: Sequence, offset, scale, sv, n_support, coef, bias, class_values, kernel="rbf", gamma: float = 1.0,
+                     coef0: float = 0.0, degree: int = 3, w=None, want_margin: bool = False):
+        """rsseg_svm_classify (include/rsseg.h) on flat float32 / float64 device planes: (labels uint8, margin float32 or None).
+        offset, scale (F,); sv (S, F) in scaled units, grouped by class; n_support (k,); coef (k - 1, S); bias (k (k - 1) / 2,);
+        class_values (k,) distinct in 1..255; kernel 'rbf' | 'poly' | 'linear' (or its RSSEG_SVM_* number); w (P, F) for 'linear'."""
+        torch = _torch()
+        F = len(planes)
+        if F == 0:
+            raise ValueError("svm_classify: no feature planes")
+        dt, n = planes[0].dtype, planes[0].numel()
+        if any(p.dtype != dt or p.numel() != n for p in planes) or dt not in (torch.float32, torch.float64):
+            raise ValueError("svm_classify: planes must all be float32 or all float64, of one length")
+        if isinstance(kernel, str):
+            if kernel not in self.SVM_KERNELS:
+                raise ValueError(f"svm_classify: kernel {kernel!r}, must be one of {tuple(self.SVM_KERNELS)}")
+            kernel = self.SVM_KERNELS[kernel]
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)   # noqa: E731
+        offset, scale, bias = f64(offset).reshape(-1), f64(scale).reshape(-1), f64(bias).reshape(-1)
+        sv, coef = f64(sv), f64(coef)
+        ns = np.asarray(n_support).reshape(-1)
+        cv = np.asarray(class_values).reshape(-1)
+        k = ns.size
+        S = sv.shape[0] if sv.ndim == 2 else -1
+        P = k * (k - 1) // 2
+        if (offset.size != F or scale.size != F or sv.ndim != 2 or sv.shape[1] != F or coef.ndim != 2 or coef.shape != (k - 1, S) or bias.size != P
+                or cv.size != k):
+            raise ValueError(f"svm_classify: the model's shapes (offset {offset.shape}, scale {scale.shape}, sv {sv.shape}, n_support {ns.shape}, "
+                             f"coef {coef.shape}, bias {bias.shape}, class_values {cv.shape}) do not describe k classes over the call's {F} planes")
+        if np.any(ns != ns.astype(np.int32)):
+            raise ValueError("svm_classify: n_support must be integers")
+        if np.any(cv != cv.astype(np.uint8)):
+            raise ValueError("svm_classify: class_values must be integers in 1..255")
+        ns, cv = np.ascontiguousarray(ns, dtype=np.int32), np.ascontiguousarray(cv, dtype=np.uint8)
+        if w is not None:
+            w = f64(w)
+            if w.shape != (P, F):
+                raise ValueError(f"svm_classify: w {w.shape}, the folded weights of {k} classes over {F} planes are {(P, F)}")
+        labels = self.empty(max(n, 1), torch.uint8)
+        margin = self.empty(max(n, 1), torch.float32) if want_margin else None
+        dp = C.POINTER(C.c_double)
+        self._chk(self.lib.rsseg_svm_classify(self.h, self._pp(planes), F, L.F32 if dt == torch.float32 else L.F64, n, k, S,
+                                              offset.ctypes.data_as(dp), scale.ctypes.data_as(dp), sv.ctypes.data_as(dp),
+                                              ns.ctypes.data_as(C.POINTER(C.c_int)), coef.ctypes.data_as(dp), bias.ctypes.data_as(dp),
+                                              cv.ctypes.data_as(C.POINTER(C.c_uint8)), int(kernel), C.c_double(float(gamma)), C.c_double(float(coef0)),
+                                              int(degree), None if w is None else w.ctypes.data_as(dp), C.c_void_p(labels.data_ptr()),
+                                              C.c_void_p(margin.data_ptr()) if want_margin else None))
+        return labels[:n], (margin[:n] if want_margin else None)
+
     # ---- K24: class signatures (rsseg/signatures.py) ----------------------------------------------
     def class_moments_plan(self, F: int, n_classes: int, u8: bool = False) -> Tuple[int, int]:
         """(path, tile_pixels) of rsseg_class_moments for F planes and n_classes labels: path 0 keeps the workgroup's table in

@@ -854,6 +854,49 @@ def run_region_merge_stage(feature_file_path, segments, output_dir: str, *, thre
     return res, stats, regions_cm
 
 
+SVM_MODEL_FILE = "svm_model.npz"
+
+
+def run_svm_stage(feature_file_path, output_dir, *, labeled_roi_file="labeled_roi.tif", kernel="rbf", C=1.0, gamma="scale", degree=3, coef0=0.0,
+                  model_path=None, rule_image=False, valid_mask=None, ctx: Optional[Context] = None):
+    """Support vector machine classification (rsseg.svm.SVMClassifier, K28; no counterpart in the reference) of the (H, W, F)
+    feature stack the forest branch takes: trained on the pixels labeled_roi_file labels (0 = unlabelled; class labels 1..255),
+    or, with model_path, a saved model applied as it is.  valid_mask: pixels outside it stay class 0.
+    Writes, beside the earlier files that stay as they are: <output_dir>/classification_svm.npy (uint8), svm_classification_map.tif
+    (when the metadata is complete), svm_model.npz and, with rule_image, svm_margin.npy (float32: the smallest |decision| among
+    the winner's pairs, NaN where nothing was classified).  Returns the class map."""
+    from .svm import SVMClassifier
+    feats = _load_normalised(feature_file_path, output_dir)
+    if feats is None:
+        raise ValueError(f"run_svm_stage: {feature_file_path} holds no feature stack")
+    shape = (int(feats["height"]), int(feats["width"]))
+    arr, _ = _supervised_feature_array(feats, True, shape)
+    if arr is None:
+        raise ValueError(f"run_svm_stage: {feature_file_path} holds no plane of shape {shape}")
+    valid_mask = _check_valid_mask(valid_mask, shape)
+    if model_path is not None:
+        clf = SVMClassifier.load(model_path)
+    else:
+        from .tiff import read_tiff
+        if not os.path.exists(labeled_roi_file):
+            raise FileNotFoundError(f"run_svm_stage: the label raster '{labeled_roi_file}' was not found")
+        roi = read_tiff(labeled_roi_file)
+        roi = roi[0] if roi.ndim == 3 else roi
+        if roi.shape != shape:
+            raise ValueError(f"run_svm_stage: the label raster is {roi.shape}, the features are {shape}")
+        clf = SVMClassifier(kernel=kernel, C=C, gamma=gamma, degree=degree, coef0=coef0).fit_image(arr, roi)
+    if clf.classes_.min() < 1 or clf.classes_.max() > 255:
+        raise ValueError("run_svm_stage: class labels must be integers in 1..255 (0 is 'unclassified' in the class map)")
+    res = clf.predict_image(arr, mask=valid_mask, want_margin=bool(rule_image), ctx=ctx)
+    out = (res[0] if rule_image else res).astype(np.uint8)
+    np.save(os.path.join(output_dir, "classification_svm.npy"), out)
+    _save_class_tif(out, feats, output_dir, "svm")
+    print(f"svm 模型保存至: {clf.save(os.path.join(output_dir, SVM_MODEL_FILE))}")
+    if rule_image:
+        np.save(os.path.join(output_dir, "svm_margin.npy"), res[1])
+    return out
+
+
 ISODATA_HISTORY_FILE = "isodata_history.json"
 ISODATA_DEFAULTS = dict(init_clusters=None, max_std=0.06, min_dist=0.1, min_size=None, iterations=20, change=0.0)
 
