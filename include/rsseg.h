@@ -794,6 +794,58 @@ int rsseg_isodata_sweep(rsseg_ctx *ctx, const void *const *d_planes, int F, int 
  * outside the limits; *tile_pixels = the pixels a workgroup takes at a time.  For the tests that straddle the seams. */
 void rsseg_isodata_plan(int F, int k, int dtype, int *path, int *tile_pixels);
 
+/* ---- K29: Gaussian mixture: the E-step and the weighted moments of one EM iteration in one pass (no counterpart in the reference) -- */
+/* One pass over F feature planes (RSSEG_F32 or RSSEG_U8, band-planar, n_local pixels) and a mixture of k components.  One right
+ * answer, restated in tests/gmm_ref.py; the kernel gives it bit for bit whatever the workgroup count, tile or path.
+ * Counted: the mask byte is non-zero (d_mask NULL: all).
+ * RSSEG_F32: v_f = the plane value, a NaN read as +0; u_f = v_f * 2^plane_exp[f] (exact, in float64); a counted pixel with any
+ * |u_f| > 1 (+-inf included) is LEFT OUT.  RSSEG_U8: u_f = v_f, plane_exp must be NULL, and the moments carry no fraction bits
+ * (QM = 0 below; Q scales ll_sum alone).  RSSEG_F32: QM = Q.
+ * The model is in u units, in K22's layout: mean[k][F], whiten[k][F (F + 1) / 2] the rows of the lower-triangular W_j packed
+ * row-major, offset[k] = ln |S_j| - 2 ln w_j.
+ * Per counted pixel that is not left out, in float64, one IEEE operation per written operation, fma only where written:
+ *   1  g_j, j ascending, as rsseg_gauss_classify defines it with x_f = u_f:  d_f = u_f - mean[j][f];  z_i = the fma chain
+ *      z = fma(W_j[i][f], d_f, z) over f = 0 .. i from +0;  m_j = the fma chain m = fma(z_i, z_i, m) over i from +0;
+ *      g_j = m_j + offset[j].  diag != 0 evaluates z_i = fma(W_j[i][i], d_i, +0) alone (W_j is taken as diagonal).
+ *   2  best = +inf, win = none;  g_j < best: best = g_j, win = j (the lowest j keeps a tie).  A pixel whose best is not finite is
+ *      LEFT OUT.
+ *   3  e_j = gmm_exp(-0.5 * (g_j - best)), gmm_exp = K28's svm_exp, operation for operation
+ *   4  s = +0; j ascending: s = s + e_j
+ *   5  r_j = e_j / s
+ *   6  q_j = rint(r_j * 2^20)
+ *   7  ll = fma(-0.5, best, gmm_log(s))
+ * gmm_log(s), s in [1, 64]:  e = the exponent of s, m = its significand in [1, 2);  m > SQRT2 (0x3FF6A09E667F3BCD): m = m * 0.5,
+ *   e = e + 1;  f = m - 1;  t = f / (2 + f);  z = t * t;  R = Lg7, i = 6 .. 1: R = fma(R, z, Lg_i);  R = R * z;
+ *   hfsq = (0.5 * f) * f;  gmm_log = e * LN2_HI - ((hfsq - (t * (hfsq + R) + e * LN2_LO)) - f)
+ *   with Lg1 .. Lg7 = 0x3FE5555555555593, 0x3FD999999997FA04, 0x3FD2492494229359, 0x3FCC71C51D8E78AF, 0x3FC7466496CB03DE,
+ *   0x3FC39A09D078C69F, 0x3FC2F112DF3E5244 and K28's LN2_HI, LN2_LO.
+ * Row j of d_table takes, for every pixel with q_j != 0 (a zero q_j adds nothing):
+ *     column 0                   += q_j
+ *     column 1 + f               += rint(q_j * u_f * 2^QM)
+ *   diag == 0:  column 1 + F + tri(a, b)  += rint(q_j * u_a * u_b * 2^QM), a <= b, the row-major upper triangle (K24's columns)
+ *   diag != 0:  column 1 + F + f          += rint(q_j * u_f * u_f * 2^QM)
+ *   each term ONE rounding, to nearest-even, of the exact real product (q_j u_a 2^QM is exact in float64: 21 + 24 bits).
+ * tail[0] = n_counted (the pixels that entered), tail[1] = n_left_out, tail[2] = n_far, the entered pixels with |ll| >= 2^20 or
+ * ll NaN, which enter the moments but not tail[3] = ll_sum = the sum of rint(ll * 2^Q).
+ * Per-pixel outputs, each optional (NULL): d_labels = win + 1, 0 where the pixel did not enter; d_posterior = float32(r_win);
+ * d_loglik = float32(ll); d_proba: k planes of n_local float32, float32(r_j); NaN where the pixel did not enter.
+ * d_table NULL: the accumulation is not compiled into that kernel (predict).
+ * Limits: 1 <= F <= RSSEG_MAX_FEATURES, 1 <= k <= 32 (above: RSSEG_ERR_UNSUPPORTED); 0 <= Q <= 30 and n_local <= 2^(42 - Q), so
+ * that no term passes 2^50 and no sum 2^62 (RSSEG_U8: also n_local <= 2^26); |plane_exp[f]| <= 300; the model finite;
+ * RSSEG_ERR_INVALID, naming the argument, for these, a null pointer, a plane not aligned to its element or a table not 8-byte
+ * aligned.  n_local == 0 writes zeros.  The result is this context's own (the integers of the stripes of a sharded raster add).
+ * Synchronous.  Profiler name "gmm_sweep". */
+int rsseg_gmm_sweep(rsseg_ctx *ctx, const void *const *d_planes, int F, int dtype /* RSSEG_F32 | RSSEG_U8 */, int64_t n_local,
+                    const uint8_t *d_mask /* NULL or n_local bytes, 0 = not counted */,
+                    const int *plane_exp /* host, F; NULL for RSSEG_U8 */, int Q, int k, int diag,
+                    const double *mean, const double *whiten, const double *offset /* host */,
+                    int64_t *d_table /* device int64[k][diag ? 1 + 2 F : 1 + F + F (F + 1) / 2], or NULL */,
+                    uint8_t *d_labels, float *d_posterior, float *d_loglik, float *d_proba /* device, each may be NULL */,
+                    int64_t *tail /* host, 4 */);
+/* host-only: *path = 0 when the workgroup keeps its table in LDS (Path A), 1 when it adds into the global table (Path B), -1
+ * outside the limits; *tile_pixels = the pixels a workgroup takes at a time. */
+void rsseg_gmm_plan(int F, int k, int dtype, int diag, int *path, int *tile_pixels);
+
 /* ---- K13: remaining texture members of the feature dictionary ---------------- */
 /* calculate_lbp_features (indices.py:320-344): skimage.feature.local_binary_pattern(u8, n_points, radius, 'uniform');
  * d_out: the codes 0 .. n_points + 1 as uint8 (the caller divides by their maximum in float64, :342). */

@@ -187,6 +187,9 @@ SIGNATURES = {
     "rsseg_isodata_sweep": (_int, [_vp, _PP, _int, _int, _i64, _vp, C.POINTER(_int), _int, C.POINTER(C.c_double), _int, C.POINTER(C.c_double), _vp,
                                    _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "rsseg_isodata_plan": (None, [_int, _int, _int, C.POINTER(_int), C.POINTER(_int)]),
+    "rsseg_gmm_sweep": (_int, [_vp, _PP, _int, _int, _i64, _vp, C.POINTER(_int), _int, _int, _int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                               C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "rsseg_gmm_plan": (None, [_int, _int, _int, _int, C.POINTER(_int), C.POINTER(_int)]),
     "rsseg_lbp_uniform_u8":(_int, [_vp, _vp, _int, _int, _int, C.c_double, _vp]),
     "rsseg_rank_entropy_u8": (_int, [_vp, _vp, _int, _int, _int, _vp]),
     "rsseg_gaussian_blur_u8": (_int, [_vp, _vp, _int, _int, _int, _vp]),

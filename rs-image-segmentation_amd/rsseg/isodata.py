@@ -52,36 +52,38 @@ def _is_device(p) -> bool:
     return hasattr(p, "data_ptr")
 
 
-def _host_planes(features):
-    """features -> (list of flat host planes of one dtype (float32 or uint8), shape of one plane)"""
+def _host_planes(features, name: str = "isodata"):
+    """features -> (list of flat host planes of one dtype (float32 or uint8), shape of one plane); name: the caller, as its
+    errors call it"""
     if isinstance(features, np.ndarray):
         if features.ndim not in (2, 3):
-            raise ValueError("isodata: features must be an (F, H, W) or (F, n) array or a sequence of planes")
+            raise ValueError(f"{name}: features must be an (F, H, W) or (F, n) array or a sequence of planes")
         seq = [features[f] for f in range(features.shape[0])]
     else:
         seq = [p.cpu().numpy() if _is_device(p) else np.asarray(p) for p in features]
     if not seq:
-        raise ValueError("isodata: no feature planes")
+        raise ValueError(f"{name}: no feature planes")
     u8 = all(p.dtype == np.uint8 for p in seq)
     for p in seq:
         if p.dtype != np.uint8 and p.dtype.kind != "f":
-            raise ValueError(f"isodata: planes must be uint8, float32 or float64, not {p.dtype}")
+            raise ValueError(f"{name}: planes must be uint8, float32 or float64, not {p.dtype}")
         if p.shape != seq[0].shape:
-            raise ValueError("isodata: the planes differ in shape")
+            raise ValueError(f"{name}: the planes differ in shape")
     dt = np.uint8 if u8 else np.float32
     return [np.ascontiguousarray(p, dtype=dt).reshape(-1) for p in seq], seq[0].shape
 
 
 class _Raster:
     """The planes, the mask and the label plane where the sweep wants them: on the device for Context.isodata_sweep, on the
-    host for a sweep= callable."""
+    host for a sweep= callable.  name and device_sweep: the caller as its errors call it and the Context method that is its sweep
+    (rsseg.gmm shares this class)."""
 
-    def __init__(self, features, mask, ctx, sweep):
+    def __init__(self, features, mask, ctx, sweep, name: str = "isodata", device_sweep: str = "isodata_sweep"):
         self.on_device = sweep is None
         self.device_in = not isinstance(features, np.ndarray) and len(features) > 0 and all(_is_device(p) for p in features)
         if self.on_device:
             self.ctx = SIG._ctx(ctx)
-            self.sweep = self.ctx.isodata_sweep
+            self.sweep = getattr(self.ctx, device_sweep)
             if self.device_in:
                 torch = __import__("torch")
                 self.planes = [p.reshape(-1) for p in features]
@@ -90,22 +92,22 @@ class _Raster:
                 self.shape = tuple(features[0].shape)
                 if any(p.dtype != self.planes[0].dtype or p.dtype not in (torch.float32, torch.uint8) or p.numel() != self.planes[0].numel()
                        for p in self.planes):
-                    raise ValueError("isodata: planes must all be float32 or all uint8, of one size")
+                    raise ValueError(f"{name}: planes must all be float32 or all uint8, of one size")
                 self.u8 = self.planes[0].dtype == torch.uint8
             else:
-                host, self.shape = _host_planes(features)
+                host, self.shape = _host_planes(features, name)
                 self.u8 = host[0].dtype == np.uint8
                 self.planes = [self.ctx.to_device(p) for p in host]
             self.n = int(self.planes[0].numel())
         else:
             self.ctx = None
             self.sweep = sweep
-            self.planes, self.shape = _host_planes(features)
+            self.planes, self.shape = _host_planes(features, name)
             self.u8 = self.planes[0].dtype == np.uint8
             self.n = int(self.planes[0].size)
         self.F = len(self.planes)
         if self.F > MAX_FEATURES:
-            raise ValueError(f"isodata: {self.F} planes, at most {MAX_FEATURES}")
+            raise ValueError(f"{name}: {self.F} planes, at most {MAX_FEATURES}")
         self.mask = None
         if mask is not None:
             if self.on_device:

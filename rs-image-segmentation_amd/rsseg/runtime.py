@@ -1185,6 +1185,60 @@ class Context:
                                                C.c_void_p(table.data_ptr()) if want_table else None, C.byref(changed), C.byref(left)))
         return (table.reshape(k, cols) if want_table else None), changed.value, left.value
 
+    # ---- K29: Gaussian mixture (rsseg/gmm.py) ---------------------------------------------------------
+    def gmm_plan(self, F: int, k: int, u8: bool = False, diag: bool = False) -> Tuple[int, int]:
+        """(path, tile_pixels) of rsseg_gmm_sweep for F planes and k components: path 0 keeps the workgroup's table in LDS,
+        1 adds into the global table."""
+        path, tile = C.c_int(0), C.c_int(0)
+        self.lib.rsseg_gmm_plan(int(F), int(k), L.U8 if u8 else L.F32, int(bool(diag)), C.byref(path), C.byref(tile))
+        return path.value, tile.value
+
+    def gmm_sweep(self, planes: Sequence, model, mask=None, want_table: bool = True, want_labels: bool = False, want_posterior: bool = False,
+                  want_loglik: bool = False, want_proba: bool = False):
+        """rsseg_gmm_sweep (include/rsseg.h) on flat float32 or uint8 device planes.  model: a dict of mean (k, F), whiten
+        (k, F (F + 1) / 2), offset (k,) in u units, plane_exp (F ints; None for uint8 planes), Q, diag (bool).  -> a dict of
+        table (int64 device [k, columns] or None), labels (uint8), posterior, loglik (float32), proba (float32 [k, n]), each
+        None unless wanted, and the ints n_counted, n_left_out, n_far, ll_sum.  mask: None or a uint8 plane, 0 = not counted."""
+        torch = _torch()
+        F = len(planes)
+        if F == 0:
+            raise ValueError("gmm_sweep: no feature planes")
+        dt, n = planes[0].dtype, planes[0].numel()
+        if any(p.dtype != dt or p.numel() != n for p in planes) or dt not in (torch.float32, torch.uint8):
+            raise ValueError("gmm_sweep: planes must all be float32 or all uint8, of one length")
+        if mask is not None and (mask.dtype != torch.uint8 or mask.numel() != n):
+            raise ValueError("gmm_sweep: mask must be a uint8 plane of the planes' length")
+        mean = np.ascontiguousarray(model["mean"], dtype=np.float64)
+        offset = np.ascontiguousarray(model["offset"], dtype=np.float64).reshape(-1)
+        k = offset.size
+        whiten = np.ascontiguousarray(model["whiten"], dtype=np.float64).reshape(k, -1) if k else np.zeros((0, 0))
+        if mean.ndim != 2 or mean.shape != (k, F) or whiten.shape != (k, F * (F + 1) // 2):
+            raise ValueError(f"gmm_sweep: the model's shapes (mean {mean.shape}, whiten {whiten.shape}, offset {offset.shape}) do not "
+                             f"describe k components over the call's {F} planes")
+        pe = None
+        if model.get("plane_exp") is not None:
+            pe = np.ascontiguousarray(model["plane_exp"], dtype=np.int32).reshape(-1)
+            if pe.size != F:
+                raise ValueError(f"gmm_sweep: {pe.size} plane exponents for {F} planes")
+        diag = bool(model.get("diag", False))
+        cols = 1 + 2 * F if diag else 1 + F + F * (F + 1) // 2
+        table = self.empty(max(k, 1) * cols, torch.int64) if want_table else None
+        labels = self.empty(max(n, 1), torch.uint8) if want_labels else None
+        posterior = self.empty(max(n, 1), torch.float32) if want_posterior else None
+        loglik = self.empty(max(n, 1), torch.float32) if want_loglik else None
+        proba = self.empty(max(n * k, 1), torch.float32) if want_proba else None
+        tail = (C.c_int64 * 4)()
+        dp = C.POINTER(C.c_double)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+        self._chk(self.lib.rsseg_gmm_sweep(self.h, self._pp(planes), F, L.F32 if dt == torch.float32 else L.U8, n, ptr(mask),
+                                           None if pe is None else pe.ctypes.data_as(C.POINTER(C.c_int)), int(model["Q"]), k, int(diag),
+                                           mean.ctypes.data_as(dp), whiten.ctypes.data_as(dp), offset.ctypes.data_as(dp), ptr(table),
+                                           ptr(labels), ptr(posterior), ptr(loglik), ptr(proba), tail))
+        return dict(table=table.reshape(max(k, 1), cols)[:k] if want_table else None, labels=labels[:n] if want_labels else None,
+                    posterior=posterior[:n] if want_posterior else None, loglik=loglik[:n] if want_loglik else None,
+                    proba=proba[:n * k].reshape(k, n) if want_proba else None, n_counted=int(tail[0]), n_left_out=int(tail[1]),
+                    n_far=int(tail[2]), ll_sum=int(tail[3]))
+
     # ---- K11 -----------------------------------------------------------------------------------
     def forest_load(self, forest: dict):
         f = forest

@@ -971,6 +971,56 @@ def run_isodata_stage(feature_file_path, output_dir="segmentation_outputs", *, n
     return out
 
 
+GMM_HISTORY_FILE = "gmm_history.json"
+GMM_DEFAULTS = dict(covariance="full", iterations=100, tol=1e-3, reg_covar=1e-6, posterior=False, model_path=None)
+
+
+def run_gmm_stage(feature_file_path, output_dir="segmentation_outputs", *, n_clusters: int = 7, covariance: str = "full", iterations: int = 100,
+                  tol: float = 1e-3, reg_covar: float = 1e-6, posterior: bool = False, model_path: Optional[str] = None, feature_keys=None,
+                  valid_mask=None, random_state: int = 42, ctx: Optional[Context] = None) -> Optional[np.ndarray]:
+    """Gaussian mixture clustering of the feature stack (rsseg.gmm, K29; no counterpart in the reference) over the planes
+    run_isodata_stage clusters (isodata_planes): n_clusters components of the given covariance type, started from a k-means
+    label map.  model_path: a saved model (GaussianMixtureModel.save) is applied and nothing is fitted.
+    valid_mask ((H, W), non-zero = valid): only the valid pixels are clustered; the class map is 0 at the others.
+    Writes <output_dir>/classification_gmm.npy (component + 1 as uint8, 0 = nodata, the k-means layout),
+    gmm_classification_map.tif with complete metadata, gmm_model.npz and gmm_history.json; with posterior also gmm_posterior.npy
+    (the label's posterior probability) and gmm_loglik.npy (the log-density), float32, NaN at nodata.  Returns the class map."""
+    from . import gmm as GMM
+    feats = _load_normalised(feature_file_path, output_dir)
+    if feats is None:
+        return None
+    shape = (int(feats["height"]), int(feats["width"]))
+    planes, names = isodata_planes(feats, feature_keys)
+    if planes is None:
+        return None
+    valid_mask = _check_valid_mask(valid_mask, shape)
+    if model_path:
+        model = GMM.GaussianMixtureModel.load(model_path)
+        n_clusters = model.n_components   # the model's own count: --n-clusters plays no part
+        record = {"model": os.path.basename(str(model_path)), "fitted": False, "history": []}
+    else:
+        model = GMM.GaussianMixtureModel(n_components=n_clusters, covariance_type=covariance, tol=tol, reg_covar=reg_covar, max_iter=iterations,
+                                         init="kmeans", random_state=random_state)
+        res = model.fit(planes, mask=valid_mask, ctx=ctx)
+        record = {"fitted": True, "history": res.history, "converged": bool(model.converged_), "n_iter": int(model.n_iter_),
+                  "lower_bound": float(model.lower_bound_)}
+    labels, post, loglik = model.predict_with_posterior(planes, mask=valid_mask, ctx=ctx)
+    out = np.ascontiguousarray(labels, dtype=np.uint8).reshape(shape)
+    n_valid = out.size if valid_mask is None else int((np.asarray(valid_mask) != 0).sum())
+    np.save(os.path.join(output_dir, "classification_gmm.npy"), out)
+    _save_class_tif(out, feats, output_dir, "gmm")
+    model.save(os.path.join(output_dir, "gmm_model.npz"))
+    if posterior:
+        np.save(os.path.join(output_dir, "gmm_posterior.npy"), np.asarray(post, np.float32).reshape(shape))
+        np.save(os.path.join(output_dir, "gmm_loglik.npy"), np.asarray(loglik, np.float32).reshape(shape))
+    _write_json(os.path.join(output_dir, GMM_HISTORY_FILE),
+                {"n_clusters": int(n_clusters), "covariance": model.covariance_type, "iterations": int(iterations), "tol": tol,
+                 "reg_covar": reg_covar, "n_components": int(model.n_components), "feature_names": list(names),
+                 "weights": [float(w) for w in model.weights_], "counts": [int(c) for c in np.bincount(out.reshape(-1), minlength=256)[1:model.n_components + 1]],
+                 "n_left_out": n_valid - int((out != 0).sum()), **record})
+    return out
+
+
 @dataclass(frozen=True)
 class RunOptions:
     """What one run of the driver is asked for beside the image, the output directory and the context: run_scripts_2_3's arguments
@@ -1012,6 +1062,13 @@ class RunOptions:
     # classify='isodata': run_isodata_stage's keyword arguments beside n_clusters (init_clusters, max_std, min_dist, min_size, iterations,
     # change, model_path); the valid mask goes to the sweep as it is
     isodata: Optional[Dict[str, object]] = None
+
+
+@dataclass(frozen=True)
+class GmmRunOptions(RunOptions):
+    """RunOptions of a --classify gmm run: run_gmm_stage's keyword arguments beside n_clusters (covariance, iterations, tol,
+    reg_covar, posterior, model_path).  Every other run keeps the plain RunOptions."""
+    gmm: Optional[Dict[str, object]] = None
 
 
 def request_from_options(o: RunOptions, method: str, valid_mask, load_roi) -> ClassifyRequest:
@@ -1089,6 +1146,8 @@ def _run_scripts_2_3(image_path, output_dir, o: RunOptions, ctx: Optional[Contex
     sdir = os.path.join(output_dir, "segmentation_results")
     if classify == "isodata":
         cm = run_isodata_stage(paths["pkl"], sdir, n_clusters=o.n_clusters, valid_mask=valid_mask, ctx=ctx, **(o.isodata or {}))
+    elif classify == "gmm":
+        cm = run_gmm_stage(paths["pkl"], sdir, n_clusters=o.n_clusters, valid_mask=valid_mask, ctx=ctx, **(getattr(o, "gmm", None) or {}))
     elif classify == "kmeans" and o.kmeans_model:
         cm = run_kmeans_model_stage(paths["pkl"], o.kmeans_model, sdir, ctx=ctx, valid_mask=valid_mask)
     else:
@@ -1155,6 +1214,8 @@ def parse_args(ap, argv=None):
             v = getattr(a, f"isodata_{k}")
             if v is not None and not (v >= 0.0 and v < float("inf")):
                 ap.error(f"--isodata-{k.replace('_', '-')} takes a finite non-negative number")
+    if a.classify == "gmm" and not 1 <= a.n_clusters <= 32:
+        ap.error("--classify gmm takes --n-clusters in 1..32")
     if (a.ml_threshold is not None or a.rule_image) and a.classify not in GAUSS_METHODS:
         ap.error("--ml-threshold / --rule-image need --classify maximum_likelihood, mahalanobis or minimum_distance")
     if a.ml_threshold is not None and not (0.0 < a.ml_threshold < 1.0):
@@ -1194,11 +1255,14 @@ def parse_args(ap, argv=None):
 
 def build_parser():
     import argparse
-    ap = argparse.ArgumentParser(prog="python -m rsseg.stages",
-                                 description="feature extraction (scripts/2) and optionally classification (scripts/3) of one GeoTIFF on the GPU")
+    # the options of --classify gmm have a parser of their own (build_gmm_parser); its help is printed below this parser's
+    gmm_help = build_gmm_parser().format_help()
+    ap = argparse.ArgumentParser(prog="python -m rsseg.stages", formatter_class=argparse.RawDescriptionHelpFormatter,
+                                 description="feature extraction (scripts/2) and optionally classification (scripts/3) of one GeoTIFF on the GPU",
+                                 epilog="options of --classify gmm:\n" + gmm_help[gmm_help.index("\n  --gmm-covariance") + 1:])
     ap.add_argument("image")
     ap.add_argument("output_dir")
-    ap.add_argument("--classify", choices=["kmeans", "isodata", "rule_based", "random_forest", *GAUSS_METHODS])
+    ap.add_argument("--classify", choices=["kmeans", "isodata", "gmm", "rule_based", "random_forest", *GAUSS_METHODS])
     ap.add_argument("--n-clusters", type=int, default=7)
     ap.add_argument("--no-preprocessing", action="store_true")
     ap.add_argument("--evaluate", metavar="ROI_MASK", help="accuracy assessment (scripts/4) of the class map against this ROI mask (.npy / .tif)")
@@ -1328,9 +1392,52 @@ def _print_report(res, a) -> None:
     accuracy(" of the object-features map", "_object_features")
 
 
+def build_gmm_parser():
+    """The options of --classify gmm.  They are parsed on their own, before the driver's parser sees the rest of the command
+    line (split_gmm_args), and travel in GmmRunOptions.gmm."""
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m rsseg.stages", add_help=False, allow_abbrev=False)
+    ap.add_argument("--gmm-covariance", choices=["full", "tied", "diag", "spherical"], default=None,
+                    help="with --classify gmm (--n-clusters is the number of components): the covariance type (default full)")
+    ap.add_argument("--gmm-iterations", type=int, default=None, metavar="N", help="with --classify gmm: at most N EM iterations (default 100)")
+    ap.add_argument("--gmm-tol", type=float, default=None, metavar="T",
+                    help="with --classify gmm: stop once the mean log-likelihood moves by less than T (default 1e-3)")
+    ap.add_argument("--gmm-reg-covar", type=float, default=None, metavar="R", help="with --classify gmm: added to the covariances' diagonals (default 1e-6)")
+    ap.add_argument("--gmm-posterior", action="store_true", help="with --classify gmm: also write gmm_posterior.npy and gmm_loglik.npy")
+    ap.add_argument("--gmm-model", metavar="PATH", help="with --classify gmm: apply this saved model (gmm_model.npz of an earlier run) instead of fitting")
+    return ap
+
+
+def split_gmm_args(argv):
+    """(run_gmm_stage's keyword arguments or None when no --gmm-* option is given, the rest of the command line)"""
+    ap = build_gmm_parser()
+    g, rest = ap.parse_known_args(argv)
+    given = [f"--gmm-{k.replace('_', '-')}" for k in ("covariance", "iterations", "tol", "reg_covar") if getattr(g, f"gmm_{k}") is not None] + (
+        ["--gmm-posterior"] if g.gmm_posterior else []) + (["--gmm-model"] if g.gmm_model else [])
+    if g.gmm_iterations is not None and g.gmm_iterations < 1:
+        ap.error("--gmm-iterations takes a positive count")
+    for k in ("tol", "reg_covar"):
+        v = getattr(g, f"gmm_{k}")
+        if v is not None and not (v >= 0.0 and v < float("inf")):
+            ap.error(f"--gmm-{k.replace('_', '-')} takes a finite non-negative number")
+    kw = {k: (d if getattr(g, f"gmm_{k}", None) is None else getattr(g, f"gmm_{k}")) for k, d in GMM_DEFAULTS.items() if k != "model_path"}
+    kw["posterior"] = bool(g.gmm_posterior)
+    kw["model_path"] = g.gmm_model
+    return (kw if given else None), given, rest
+
+
 def main(argv=None) -> int:
-    a = parse_args(build_parser(), argv)
-    res = _run_scripts_2_3(a.image, a.output_dir, options_from_args(a), None)
+    import dataclasses
+    import sys
+    gmm, gmm_given, rest = split_gmm_args(sys.argv[1:] if argv is None else list(argv))
+    ap = build_parser()
+    a = parse_args(ap, rest)
+    if gmm_given and a.classify != "gmm":
+        ap.error(f"{' / '.join(gmm_given)} need --classify gmm")
+    o = options_from_args(a)
+    if a.classify == "gmm":
+        o = GmmRunOptions(**{f.name: getattr(o, f.name) for f in dataclasses.fields(o)}, gmm=gmm or dict(GMM_DEFAULTS))
+    res = _run_scripts_2_3(a.image, a.output_dir, o, None)
     _print_report(res, a)
     return 1 if a.classify and res.get("class_map") is None else 0
 
