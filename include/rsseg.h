@@ -477,6 +477,52 @@ int rsseg_svm_classify(rsseg_ctx *ctx, const void *const *d_planes, int F, int d
  * RSSEG_ERR_INVALID for a null array, F < 1, k < 2, S < 1 or an n_support that does not sum to S; k > 16 RSSEG_ERR_UNSUPPORTED. */
 int rsseg_host_svm_fold_linear(int F, int k, int S, const double *sv, const int *n_support, const double *coef, double *w);
 
+/* ---- K30: neural-network (multi-layer perceptron) classification --------------------------------- */
+#define RSSEG_MLP_RELU 0
+#define RSSEG_MLP_IDENTITY 1
+#define RSSEG_MLP_LOGISTIC 2
+#define RSSEG_MLP_TANH 3
+#define RSSEG_MLP_MAX_HIDDEN_LAYERS 3
+#define RSSEG_MLP_MAX_WIDTH 128
+#define RSSEG_MLP_MAX_CLASSES 32
+/* One pass over F feature planes (RSSEG_F32, band-planar, any element alignment) for a fitted scikit-learn MLPClassifier of k
+ * classes, all host arrays, float32: widths[n_layers + 1] with widths[0] = F, widths[1 .. n_layers - 1] the hidden widths and
+ * widths[n_layers] the output units, k for k >= 3 and 1 for k = 2 (scikit-learn's binary layout); weights, the concatenation
+ * of W_l[widths[l-1]][widths[l]], l = 1 .. n_layers, row-major (coefs_); biases, the concatenation of b_l[widths[l]]
+ * (intercepts_); offset[F] and scale[F] (finite, scale != 0); activation, RSSEG_MLP_*, of the hidden layers; class_values[k],
+ * distinct and 1..255.
+ * Per pixel, in float32 unless said otherwise, every line one IEEE operation:
+ *   x_f = the plane value, a NaN read as +0; a pixel with any +-inf x_f gets label 0 and margin, confidence, probabilities NaN
+ *   z_f = (x_f - offset_f) * scale_f;  h_0 = z
+ *   layer l, unit j:  a = b_l[j]; i ascending: a = fmaf(h_(l-1)[i], W_l[i][j], a).  The chain starts at the bias; no term is
+ *   skipped.  h_l[j] = activation(a) on the hidden layers:
+ *     relu      a > 0 ? a : +0 (a NaN gives +0);   identity  a
+ *     logistic  in float64 on the widened a: e = svm_exp(-|a|); d = 1 + e; a >= 0 ? 1 / d : e / d; rounded once to float32
+ *     tanh      |a| < 2^-13: a itself.  Otherwise in float64: e = svm_exp(-(2 |a|)); t = (1 - e) / (1 + e); a < 0 ? -t : t;
+ *               rounded once to float32.  A NaN passes through both.  svm_exp is K28's (above), operation for operation.
+ *   o_j = the last layer's a; for k = 2 the two logits are (+0, o_0)
+ *   winner: w = 0, then j = 1 .. k-1 ascending: j replaces w when o_j > o_w, or when o_w is a NaN and o_j is not (the lowest j
+ *   with the largest o_j; a NaN never beats anything; all NaN: j = 0).  second: the same rule over the logits without the winner.
+ *   d_labels  class_values[winner]
+ *   d_margin  NULL or float32: o_win - o_second, one float32 subtraction (|o_0| for k = 2)
+ *   in float64: d_j = double(o_j) - double(o_win);  s = +0; j ascending: s = s + svm_exp(d_j)
+ *   d_conf    NULL or float32(1 / s)
+ *   d_proba   NULL or k float32 planes of n, plane j at d_proba + j * n: float32(svm_exp(d_j) / s)
+ * Outputs are compared with tests/mlp_ref.py as values: -0 equals +0 and the NaN positions coincide (the kernel pads every chain
+ * to a multiple of 4 terms with zeros, which can change nothing but the sign of a zero).
+ * Limits: 1 <= F <= 64; 1 to 3 hidden layers (n_layers 2 .. 4), each 1 .. 128 wide; 2 <= k <= 32; the staged model must fit
+ * LDS beside one tile of pixels (rsseg_mlp_plan).  Beyond them, or an unknown activation: RSSEG_ERR_UNSUPPORTED.
+ * RSSEG_ERR_INVALID, naming the argument: a null or misaligned plane or output, a missing or non-finite model value, a scale of
+ * 0, a width below 1, widths[0] != F, output units that are not k's, k < 2, a class value of 0 or one that occurs twice, n < 0.
+ * n == 0 returns RSSEG_OK and touches nothing.  Synchronous.  Profiler name "mlp_classify". */
+int rsseg_mlp_classify(rsseg_ctx *ctx, const void *const *d_planes, int F, int64_t n, int n_layers, const int *widths, const float *weights,
+                       const float *biases, const float *offset, const float *scale, int activation /* RSSEG_MLP_* */, int k,
+                       const uint8_t *class_values, uint8_t *d_labels, float *d_margin /* or NULL */, float *d_conf /* or NULL */,
+                       float *d_proba /* or NULL: k float32 planes */);
+/* Host only, no context: *fits = 1 when rsseg_mlp_classify takes a model of these widths (0: beyond the limits, or it does not
+ * fit LDS), *tile_pixels = the pixels a workgroup takes at a time (0 when it does not fit).  Either pointer may be NULL. */
+void rsseg_mlp_plan(int F, int n_layers, const int *widths, int k, int *fits, int *tile_pixels);
+
 /* ---- K11: random-forest inference ---------------------------------------------------------- */
 /* Flattened sklearn forest (tree_ arrays concatenated; children are tree-local, -1 = leaf).
  * value: (n_nodes_total x n_classes) float64 class fractions.  The forest is copied to the device

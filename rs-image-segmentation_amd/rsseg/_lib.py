@@ -136,6 +136,9 @@ SIGNATURES = {
                                   C.POINTER(_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint8), _int, C.c_double,
                                   C.c_double, _int, C.POINTER(C.c_double), _vp, _vp]),
     "rsseg_host_svm_fold_linear": (_int, [_int, _int, _int, C.POINTER(C.c_double), C.POINTER(_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rsseg_mlp_classify": (_int, [_vp, _PP, _int, _i64, _int, C.POINTER(_int), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                  C.POINTER(C.c_float), _int, _int, C.POINTER(C.c_uint8), _vp, _vp, _vp, _vp]),
+    "rsseg_mlp_plan": (None, [_int, _int, C.POINTER(_int), _int, C.POINTER(_int), C.POINTER(_int)]),
     "rsseg_valid_mask": (_int, [_vp, _PP, _int, _int, _i64, _int, C.c_double, _vp, _vp, C.POINTER(_i64)]),
     "rsseg_compact_tile": (_int, []),
     "rsseg_compact_scan_span": (_int, []),

@@ -1101,6 +1101,62 @@ class Context:
                                               C.c_void_p(margin.data_ptr()) if want_margin else None))
         return labels[:n], (margin[:n] if want_margin else None)
 
+    # ---- K30: neural-network classification (rsseg/mlp.py) ------------------------------------------
+    MLP_ACTIVATIONS = {"relu": 0, "identity": 1, "logistic": 2, "tanh": 3}   # RSSEG_MLP_*
+
+    def mlp_plan(self, widths, k: int) -> Tuple[bool, int]:
+        """(fits, tile_pixels) of rsseg_mlp_classify for layers of these widths (F, the hidden widths, the output units) and k
+        classes: whether the staged model fits LDS, and the pixels a workgroup takes at a time (0 when it does not)."""
+        w = np.ascontiguousarray(widths, dtype=np.int32).reshape(-1)
+        fits, tile = C.c_int(0), C.c_int(0)
+        self.lib.rsseg_mlp_plan(int(w[0]) if w.size else 0, int(w.size) - 1, w.ctypes.data_as(C.POINTER(C.c_int)), int(k), C.byref(fits), C.byref(tile))
+        return bool(fits.value), tile.value
+
+    def mlp_classify(self, planes: Sequence, widths, weights, biases, offset, scale, activation, class_values, want_margin: bool = False,
+                     want_conf: bool = False, want_proba: bool = False):
+        """rsseg_mlp_classify (include/rsseg.h) on flat float32 device planes: (labels uint8, margin, conf float32 (n,), proba
+        float32 (k, n)), each of the last three None unless wanted.  widths: F, the hidden widths, the output units (1 for two
+        classes); weights / biases: the layers' coefs_ / intercepts_ flattened and concatenated (float32); offset, scale (F,);
+        activation 'relu' | 'identity' | 'logistic' | 'tanh' (or its RSSEG_MLP_* number); class_values (k,) distinct in 1..255."""
+        torch = _torch()
+        F = len(planes)
+        if F == 0:
+            raise ValueError("mlp_classify: no feature planes")
+        n = planes[0].numel()
+        if any(p.dtype != torch.float32 or p.numel() != n for p in planes):
+            raise ValueError("mlp_classify: planes must all be float32, of one length")
+        if isinstance(activation, str):
+            if activation not in self.MLP_ACTIVATIONS:
+                raise ValueError(f"mlp_classify: activation {activation!r}, must be one of {tuple(self.MLP_ACTIVATIONS)}")
+            activation = self.MLP_ACTIVATIONS[activation]
+        f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32).reshape(-1)   # noqa: E731
+        weights, biases, offset, scale = f32(weights), f32(biases), f32(offset), f32(scale)
+        w = np.asarray(widths).reshape(-1)
+        cv = np.asarray(class_values).reshape(-1)
+        k = cv.size
+        if w.size < 2 or np.any(w != w.astype(np.int32)):
+            raise ValueError(f"mlp_classify: widths {w.tolist()} are not the integer widths of an input and at least one more layer")
+        w = np.ascontiguousarray(w, dtype=np.int32)
+        n_w, n_b = int((w[:-1].astype(np.int64) * w[1:]).sum()), int(w[1:].sum())
+        if offset.size != F or scale.size != F or weights.size != n_w or biases.size != n_b or int(w[0]) != F:
+            raise ValueError(f"mlp_classify: the model's shapes (widths {w.tolist()}, {weights.size} weights, {biases.size} biases, offset {offset.shape}, "
+                             f"scale {scale.shape}) do not describe layers over the call's {F} planes")
+        if np.any(cv != cv.astype(np.uint8)):
+            raise ValueError("mlp_classify: class_values must be integers in 1..255")
+        cv = np.ascontiguousarray(cv, dtype=np.uint8)
+        labels = self.empty(max(n, 1), torch.uint8)
+        margin = self.empty(max(n, 1), torch.float32) if want_margin else None
+        conf = self.empty(max(n, 1), torch.float32) if want_conf else None
+        proba = self.empty(max(n, 1) * max(k, 1), torch.float32) if want_proba else None
+        fp = C.POINTER(C.c_float)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+        self._chk(self.lib.rsseg_mlp_classify(self.h, self._pp(planes), F, n, int(w.size) - 1, w.ctypes.data_as(C.POINTER(C.c_int)),
+                                              weights.ctypes.data_as(fp), biases.ctypes.data_as(fp), offset.ctypes.data_as(fp),
+                                              scale.ctypes.data_as(fp), int(activation), k, cv.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                              ptr(labels), ptr(margin), ptr(conf), ptr(proba)))
+        return (labels[:n], margin[:n] if want_margin else None, conf[:n] if want_conf else None,
+                proba[:k * n].reshape(k, n) if want_proba else None)
+
     # ---- K24: class signatures (rsseg/signatures.py) ----------------------------------------------
     def class_moments_plan(self, F: int, n_classes: int, u8: bool = False) -> Tuple[int, int]:
         """(path, tile_pixels) of rsseg_class_moments for F planes and n_classes labels: path 0 keeps the workgroup's table in

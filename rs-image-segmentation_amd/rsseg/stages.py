@@ -897,6 +897,52 @@ def run_svm_stage(feature_file_path, output_dir, *, labeled_roi_file="labeled_ro
     return out
 
 
+MLP_MODEL_FILE = "mlp_model.npz"
+
+
+def run_mlp_stage(feature_file_path, output_dir, *, labeled_roi_file="labeled_roi.tif", hidden_layer_sizes=(100,), activation="relu", alpha=1e-4,
+                  max_iter=500, random_state=42, model_path=None, rule_image=False, valid_mask=None, ctx: Optional[Context] = None):
+    """Neural-network classification (rsseg.mlp.NeuralNetClassifier, K30; no counterpart in the reference) of the (H, W, F)
+    feature stack the forest branch takes: trained on the pixels labeled_roi_file labels (0 = unlabelled; class labels 1..255),
+    or, with model_path, a saved model applied as it is.  valid_mask: pixels outside it stay class 0.
+    Writes, beside the earlier files that stay as they are: <output_dir>/classification_mlp.npy (uint8), mlp_classification_map.tif
+    (when the metadata is complete), mlp_model.npz and, with rule_image, mlp_margin.npy (float32: the winner's logit minus the
+    runner-up's) and mlp_confidence.npy (float32: the winner's probability), both NaN where nothing was classified.  Returns the
+    class map."""
+    from .mlp import NeuralNetClassifier
+    feats = _load_normalised(feature_file_path, output_dir)
+    if feats is None:
+        raise ValueError(f"run_mlp_stage: {feature_file_path} holds no feature stack")
+    shape = (int(feats["height"]), int(feats["width"]))
+    arr, _ = _supervised_feature_array(feats, True, shape)
+    if arr is None:
+        raise ValueError(f"run_mlp_stage: {feature_file_path} holds no plane of shape {shape}")
+    valid_mask = _check_valid_mask(valid_mask, shape)
+    if model_path is not None:
+        clf = NeuralNetClassifier.load(model_path)
+    else:
+        from .tiff import read_tiff
+        if not os.path.exists(labeled_roi_file):
+            raise FileNotFoundError(f"run_mlp_stage: the label raster '{labeled_roi_file}' was not found")
+        roi = read_tiff(labeled_roi_file)
+        roi = roi[0] if roi.ndim == 3 else roi
+        if roi.shape != shape:
+            raise ValueError(f"run_mlp_stage: the label raster is {roi.shape}, the features are {shape}")
+        clf = NeuralNetClassifier(hidden_layer_sizes=hidden_layer_sizes, activation=activation, alpha=alpha, max_iter=max_iter,
+                                  random_state=random_state).fit_image(arr, roi)
+    if clf.classes_.min() < 1 or clf.classes_.max() > 255:
+        raise ValueError("run_mlp_stage: class labels must be integers in 1..255 (0 is 'unclassified' in the class map)")
+    res = clf.predict_image(arr, mask=valid_mask, want_margin=bool(rule_image), want_conf=bool(rule_image), ctx=ctx)
+    out = (res[0] if rule_image else res).astype(np.uint8)
+    np.save(os.path.join(output_dir, "classification_mlp.npy"), out)
+    _save_class_tif(out, feats, output_dir, "mlp")
+    print(f"mlp 模型保存至: {clf.save(os.path.join(output_dir, MLP_MODEL_FILE))}")
+    if rule_image:
+        np.save(os.path.join(output_dir, "mlp_margin.npy"), res[1])
+        np.save(os.path.join(output_dir, "mlp_confidence.npy"), res[2])
+    return out
+
+
 ISODATA_HISTORY_FILE = "isodata_history.json"
 ISODATA_DEFAULTS = dict(init_clusters=None, max_std=0.06, min_dist=0.1, min_size=None, iterations=20, change=0.0)
 
